@@ -28,6 +28,16 @@ The input is synthesised on the GPU by the product's own multichanneltx (txgen.h
 against the oracle's transmitter in tests/test_gpu_tx.py).  The CPU oracle (oracle/) appears only as the
 `cpu_baseline` leg: timed on the first slab on one host thread, and its decoded frames / equalised symbols are
 compared with the GPU's for that slab.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what `value` needs: it synthesises the slabs, warms up,
+times exactly N steps (one repetition), writes `--dump-outputs` if asked and prints the line.  Everything else -- the
+serial per-kernel pass and the `roofline` block, the overlapped kernel durations, the verification step, the harvested /
+ragged-traffic / variant legs, the `configs` block, the default-queues leg and `cpu_baseline` -- runs with `--full`
+(five repetitions of the timed region by default there).
+
+`--dump-outputs DIR`: the last timed step keeps its frames for the caller (mcrx_hip_poll between its slabs instead of
+mcrx_hip_discard); after the clock stops they are flushed to the host and written as float arrays to DIR/<name>.npy
+(dump_outputs).  The slabs are seeded, so two builds run with the same arguments see the same samples.
 """
 import argparse
 import json
@@ -74,7 +84,15 @@ def parse():
     ap.add_argument("--scout-build", type=int, default=0, help="mcrx_hip_config::scout_build for the headline receiver (A/B runs: 2 = the lean segment waves of csrc/acq_lean.hpp; 0 = the general state machine's, the default)")
     ap.add_argument("--no-variants", action="store_true", help="skip the headline's variants (30 dB AWGN on the wideband samples; equalised symbols not stored)")
     ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE.json configurations (the `configs` block)")
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed region of --steps steps: value = median, value_min / value_max beside it")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed region of --steps steps (default 1; 5 with --full): "
+                                                           "value = median, value_min / value_max beside it")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: the serial per-kernel pass (roofline block), "
+                                                        "the overlapped kernel durations, the verification step, the harvested / ragged / variant "
+                                                        "legs, the configs block, the default-queues leg and the CPU baseline (the --no-* options "
+                                                        "still drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames of the last timed step to DIR/<name>.npy (float32 / float64; see dump_outputs).  That step "
+                         "keeps its frames (polls instead of discarding them on the device); they are flushed after the clock stops")
     ap.add_argument("--aperiodic-steps", type=int, default=20)
     ap.add_argument("--slab-blocks", type=int, default=0)
     ap.add_argument("--chunk-blocks", type=int, default=0, help="split every push into sub-slabs of this many blocks")
@@ -93,7 +111,10 @@ def parse():
                     help="--gpus N > 1 with every rank on device 0 and the exchange staged through host memory under gloo (RCCL refuses two ranks on one "
                          "device): executes the whole multi-process code path -- sub-slab cut, halos, pipeline, verification -- on a one-GPU lease.  "
                          "The value it prints is NOT a scaling number")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    return args
 
 
 LEG_CFG = {}           # receiver configuration the command line adds to every leg (--acquisition)
@@ -144,6 +165,56 @@ def frame_index(sent):
     return [{(h[0] << 8) | h[1]: (h, p) for (h, p) in ch} for ch in sent]
 
 
+DUMP_SEED = 20250601                    # the sample of frames whose payloads / equalised symbols are written whole
+DUMP_BYTES = 48 << 20                   # all arrays together (the whole step's symbols: 1.5 GB at the defaults); a third of what the
+                                        # per-frame rows leave goes to payloads, the rest to symbols
+
+
+def dump_outputs(path, frames, period_blocks):
+    """--dump-outputs: what the caller received from the last timed step, one frame per row, ordered by where the frame ends within
+    the step (channel-rate samples; a step is one period of the stream) and then by channel.  Every frame: channel, end_sample,
+    header_valid, payload_valid, payload_len, num_framesyms, payload_crc32 (zlib CRC-32 of the payload bytes), evm, rssi, cfo and
+    its 8 header bytes.  A fixed, seeded sample of the frames (rows *_sample_index) whole: payload bytes (payload_sample) and
+    equalised symbols (framesyms_sample, [frame, symbol, re/im]); shorter rows are zero-padded.  float64 / float32 only."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    fr = sorted(frames, key=lambda f: (f.end_sample % period_blocks, f.channel))
+    n = len(fr)
+    arrays = {
+        "channel": np.array([f.channel for f in fr], np.float64),
+        "end_sample": np.array([f.end_sample % period_blocks for f in fr], np.float64),
+        "header_valid": np.array([f.header_valid for f in fr], np.float64),
+        "payload_valid": np.array([f.payload_valid for f in fr], np.float64),
+        "payload_len": np.array([len(f.payload) for f in fr], np.float64),
+        "num_framesyms": np.array([len(f.framesyms) for f in fr], np.float64),
+        "payload_crc32": np.array([zlib.crc32(f.payload) for f in fr], np.float64),
+        "evm": np.array([f.evm for f in fr], np.float32),
+        "rssi": np.array([f.rssi for f in fr], np.float32),
+        "cfo": np.array([f.cfo for f in fr], np.float32),
+        "header": np.array([list(f.header) for f in fr], np.float32).reshape(n, 8),
+    }
+    rest = max(0, DUMP_BYTES - sum(a.nbytes for a in arrays.values()))
+    rng = np.random.default_rng(DUMP_SEED)
+    plen = max([len(f.payload) for f in fr] or [0])
+    k = min(n, rest // 3 // (4 * max(plen, 1) + 8))
+    idx = np.sort(rng.choice(n, k, replace=False)) if k else np.zeros(0, np.int64)
+    pay = np.zeros((k, plen), np.float32)
+    for r, i in enumerate(idx):
+        pay[r, :len(fr[i].payload)] = np.frombuffer(fr[i].payload, np.uint8)
+    arrays["payload_sample_index"], arrays["payload_sample"] = idx.astype(np.float64), pay
+    nsym = max([len(f.framesyms) for f in fr] or [0])
+    k = min(n, (rest - pay.nbytes - 8 * len(idx)) // (8 * max(nsym, 1) + 8))
+    idx = np.sort(rng.choice(n, k, replace=False)) if k else np.zeros(0, np.int64)
+    syms = np.zeros((k, nsym, 2), np.float32)
+    for r, i in enumerate(idx):
+        s = fr[i].framesyms
+        syms[r, :len(s), 0], syms[r, :len(s), 1] = s.real, s.imag
+    arrays["framesyms_sample_index"], arrays["framesyms_sample"] = idx.astype(np.float64), syms
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "frames": n, "arrays": len(arrays), "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def main():
     args = parse()
     if args.acquisition:
@@ -185,7 +256,7 @@ def main():
             ranks_seen = int(one.item())
         assert ranks_seen == world, "all_reduce saw %d of %d ranks" % (ranks_seen, world)
 
-    prod, ora = load_product(), load_oracle()
+    prod = load_product()
     from liquid_usrp_amd import sharding
     N, M, cp, taper = args.channels, 64, 8, 4
     K = 2 * N
@@ -237,31 +308,34 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- every kernel alone (serial handle, HIP events on the launch stream): the roofline block's durations.
+    # ---- every kernel alone (serial handle, HIP events on the launch stream): the roofline block's durations (--full).
     # Runs first, so it also brings the clocks up before the timed region.
-    ser = prod.multichannelrx(N, M, cp, taper, serial=1, channel_first=c0, channel_count=cg, **cfg)
-    ser.kernel_timing(True)                             # (HIP-event pairs around every kernel: off in a new receiver, include/mcrx_hip.h)
-    for k in range(args.serial_steps + 2):
-        if k == 2:
-            torch.cuda.synchronize(); ser.kernel_stats(reset=True)
-        for d in slabs[:args.slabs]:
-            ser.Execute(d)
-            ser.Discard()
-    torch.cuda.synchronize()
-    ser_stats = ser.kernel_stats()
-    ser.close()
+    ser_stats = None
+    if args.full:
+        ser = prod.multichannelrx(N, M, cp, taper, serial=1, channel_first=c0, channel_count=cg, **cfg)
+        ser.kernel_timing(True)                         # (HIP-event pairs around every kernel: off in a new receiver, include/mcrx_hip.h)
+        for k in range(args.serial_steps + 2):
+            if k == 2:
+                torch.cuda.synchronize(); ser.kernel_stats(reset=True)
+            for d in slabs[:args.slabs]:
+                ser.Execute(d)
+                ser.Discard()
+        torch.cuda.synchronize()
+        ser_stats = ser.kernel_stats()
+        ser.close()
 
     if world == 1 and not args.pipeline:
         rx = prod.multichannelrx(N, M, cp, taper, serial=1 if args.serial else 0, **cfg)
 
-        def step(harvest_rx=None):
-            h = harvest_rx or rx
-            for d in slabs:
-                h.Execute(d)
-                if harvest_rx is None:
-                    h.Discard()
-                else:
-                    h.Poll()                        # a result generation holds one slab's frames
+        def step(harvest=False, deliver=True):
+            for i, d in enumerate(slabs):
+                rx.Execute(d)
+                if not harvest:
+                    rx.Discard()
+                elif deliver or i < len(slabs) - 1:
+                    rx.Poll(deliver=deliver)        # a result generation holds one slab's frames
+                # (deliver=False: the last slab's generation stays open and a poll collects only what was closed before the previous
+                #  one, so at three slabs per step no frame crosses the host link until the caller flushes)
         samples_per_step = period_blocks * K
         pipe, trial_steps = None, 0
     else:
@@ -344,14 +418,14 @@ def main():
         if not use_c:
             pipe = sharding.Pipeline(rx, rank, world, dist, N, Tc, rx.hist_tiles, device=dev, nbuf=nbuf)
 
-        def step(harvest_rx=None):
+        def step(harvest=False, deliver=True):
             for c in range(rounds):
                 if use_c:
                     pipe.push(mine[c], None if first_push[0] else halos[c], ready=True)      # (resident since the fence behind the generator)
                 else:
                     pipe.push(mine[c], None if first_push[0] else halos[c])
                 first_push[0] = False
-            if harvest_rx is None:
+            if not harvest:
                 rx.Discard()
         samples_per_step = world * rounds * Tc * K
 
@@ -364,12 +438,22 @@ def main():
     # the timed region, --reps times over: every repetition is exactly --steps steps between two fences;
     # value = the median repetition, the spread is reported beside it
     rep_s = []
-    for r in range(max(1, args.reps)):
+    nreps = max(1, args.reps)
+    for r in range(nreps):
         t0 = time.perf_counter()
         for k in range(args.steps):
-            step()
+            # --dump-outputs: the very last timed step keeps its frames (polls instead of discards) rather than dropping them on the
+            # device; they reach the host in the flush after the clock stops
+            last = args.dump_outputs is not None and r == nreps - 1 and k == args.steps - 1
+            step(harvest=last, deliver=False)
         fence()
         rep_s.append(time.perf_counter() - t0)
+    dumped = None
+    if args.dump_outputs is not None:
+        rx.Flush()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, rx.frames, period_blocks)
+        rx.frames.clear()
     if world > 1:                                      # a repetition takes as long as its slowest rank
         tt = torch.tensor(rep_s, dtype=torch.float64, device="cpu" if rehearsal else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -399,31 +483,33 @@ def main():
                     "what": ("RCCL, HIP events on the exchange stream of rank 0 (%s)" % ("grouped ncclSend/ncclRecv behind the C-ABI" if use_c else "torch.distributed all_to_all_single")) if world > 1
                             else "local copy standing in for the exchange (one GPU)"}
     walked, adopted = rx.spec_stats()
-    # the kernels' durations while they overlap: a few more steps of the same loop with the receiver's event timing switched on,
-    # outside the timed region (the event pairs are ten more packets per push; the timed region runs the receiver as it is made)
-    stat_steps = 4
-    rx.kernel_timing(True); rx.kernel_stats(reset=True)
-    for k in range(stat_steps):
-        step()
-    fence()
-    ovl_stats = rx.kernel_stats()
-    rx.kernel_timing(False)
+    verified = None
+    if args.full:
+        # the kernels' durations while they overlap: a few more steps of the same loop with the receiver's event timing switched on,
+        # outside the timed region (the event pairs are ten more packets per push; the timed region runs the receiver as it is made)
+        stat_steps = 4
+        rx.kernel_timing(True); rx.kernel_stats(reset=True)
+        for k in range(stat_steps):
+            step()
+        fence()
+        ovl_stats = rx.kernel_stats()
+        rx.kernel_timing(False)
 
-    # ---- verification (untimed): one more step of the continuing stream, harvested; every frame of the step
-    # decoded, valid and equal to what the transmitter sent
-    rx.Flush(); rx.frames.clear()
-    step_first = int(args.warmup + nsteps_timed + trial_steps + stat_steps) * period_blocks         # channel-rate sample index where this step starts
-    step(harvest_rx=rx)
-    rx.Flush()
-    nfr, n_ok = len(rx.frames), 0
-    for f in rx.frames:
-        pos = (f.end_sample - step_first) % period_blocks
-        si = int(np.searchsorted(slab_start, pos, side="right") - 1)
-        want = sents[min(si, nslab - 1)][f.channel].get((f.header[0] << 8) | f.header[1])
-        n_ok += 1 if (f.header_valid and f.payload_valid and want == (f.header, f.payload)) else 0
-    expect = cg * args.frames * nslab
-    verified = (nfr == expect and n_ok == expect)
-    rx.frames.clear()
+        # ---- verification (untimed): one more step of the continuing stream, harvested; every frame of the step
+        # decoded, valid and equal to what the transmitter sent
+        rx.Flush(); rx.frames.clear()
+        step_first = int(args.warmup + nsteps_timed + trial_steps + stat_steps) * period_blocks         # channel-rate sample index where this step starts
+        step(harvest=True)
+        rx.Flush()
+        nfr, n_ok = len(rx.frames), 0
+        for f in rx.frames:
+            pos = (f.end_sample - step_first) % period_blocks
+            si = int(np.searchsorted(slab_start, pos, side="right") - 1)
+            want = sents[min(si, nslab - 1)][f.channel].get((f.header[0] << 8) | f.header[1])
+            n_ok += 1 if (f.header_valid and f.payload_valid and want == (f.header, f.payload)) else 0
+        expect = cg * args.frames * nslab
+        verified = (nfr == expect and n_ok == expect)
+        rx.frames.clear()
 
     value = samples_per_step * args.steps / elapsed / 1e6
     out = None
@@ -431,19 +517,21 @@ def main():
         # (the legs below make their own receivers: this one's four streams go first, so that theirs do not share hardware queues with
         #  them -- HIP maps a process's streams onto GPU_MAX_HW_QUEUES queues in turn)
         rx.close(); rx = None
+    # ---- everything beside the headline (--full)
     harvest = None
-    if world == 1 and not args.no_harvest and not args.pipeline:
+    if args.full and world == 1 and not args.no_harvest and not args.pipeline:
         harvest = harvest_legs(prod, N, M, cp, taper, cfg, slabs, K, args, torch)
     aper = None
-    if world == 1 and not args.no_aperiodic and not args.pipeline:
+    if args.full and world == 1 and not args.no_aperiodic and not args.pipeline:
         aper = aperiodic_leg(prod, N, M, cp, taper, slab_blocks[:args.slabs], K, args, torch, dev)
     variants = None
-    if world == 1 and not args.no_variants and not args.pipeline and not args.serial:
+    if args.full and world == 1 and not args.no_variants and not args.pipeline and not args.serial:
         variants = variant_legs(prod, N, M, cp, taper, cfg, slabs, sents, args, torch, dev)
     cfgs = None
-    if world == 1 and not args.no_configs and not args.pipeline:
+    if args.full and world == 1 and not args.no_configs and not args.pipeline:
         cfgs = configs_block(prod, torch, dev, args)
-    if rank == 0:
+    roofline = None
+    if rank == 0 and args.full:
         per = {k: v[0] / max(v[1], 1) for k, v in ser_stats.items()}          # mean ms per launch, kernel alone
         ovl = {k: v[0] / max(v[1], 1) for k, v in ovl_stats.items()}
         blocks0 = slab_blocks[0] if world == 1 else None
@@ -468,6 +556,23 @@ def main():
         kms = per[kname]
         achieved = kbytes[kname] / (kms * 1e-3) / 1e9
         traffic = measured_traffic(kname, N, args.frames, args.payload)
+        roofline = {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                    "ms_per_launch": round(kms, 4),
+                    "measured": "kernel alone: serial receiver, %d steps, HIP events on the launch stream" % args.serial_steps,
+                    "algorithmic_bytes_per_launch": round(kbytes[kname], 0),
+                    "traffic_source": traffic_source(),
+                    "kernels_ms": {k: round(v, 4) for k, v in per.items()},
+                    "kernels_frac_of_peak": {k: round(v, 5) for k, v in fracs.items()},
+                    "kernels_ms_overlapped": {k: round(v, 4) for k, v in ovl.items()},
+                    "serial_sum_ms_per_slab": round(sum(per.values()), 4),
+                    "vector_issue": safely(vector_issue, value, world, N, args.frames, args.payload, samples_per_step / max(1, args.slabs) / world),
+                    "pipeline_frac_of_16B_roofline": round(value * 1e6 * 16.0 / (world * HBM_PEAK_GBS * 1e9), 5),
+                    "per_gpu": {"Msamples_per_s": round(value / world, 3), "GBps_at_16B_per_sample": round(value / world * 16e-3, 2),
+                                "peak_GBps": HBM_PEAK_GBS},
+                    "aggregate": {"Msamples_per_s": round(value, 3), "GBps_at_16B_per_sample": round(value * 16e-3, 2),
+                                  "peak_GBps": world * HBM_PEAK_GBS}}
+    if rank == 0:
         total = walked + adopted
         out = {
             "metric": "complex Msamples/s through multichannelrx",
@@ -502,26 +607,14 @@ def main():
                                        "exchange overlapped" % (cg, args.rounds)) if world > 1 else "single GPU"},
             "spec_hit_rate": round(adopted / total, 4) if total else None,
             "frames_acquired": {"by_scout_walk": walked, "adopted_from_speculation": adopted},
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                         "ms_per_launch": round(kms, 4),
-                         "measured": "kernel alone: serial receiver, %d steps, HIP events on the launch stream" % args.serial_steps,
-                         "algorithmic_bytes_per_launch": round(kbytes[kname], 0),
-                         "traffic_source": traffic_source(),
-                         "kernels_ms": {k: round(v, 4) for k, v in per.items()},
-                         "kernels_frac_of_peak": {k: round(v, 5) for k, v in fracs.items()},
-                         "kernels_ms_overlapped": {k: round(v, 4) for k, v in ovl.items()},
-                         "serial_sum_ms_per_slab": round(sum(per.values()), 4),
-                         "vector_issue": safely(vector_issue, value, world, N, args.frames, args.payload, samples_per_step / max(1, args.slabs) / world),
-                         "pipeline_frac_of_16B_roofline": round(value * 1e6 * 16.0 / (world * HBM_PEAK_GBS * 1e9), 5),
-                         "per_gpu": {"Msamples_per_s": round(value / world, 3), "GBps_at_16B_per_sample": round(value / world * 16e-3, 2),
-                                     "peak_GBps": HBM_PEAK_GBS},
-                         "aggregate": {"Msamples_per_s": round(value, 3), "GBps_at_16B_per_sample": round(value * 16e-3, 2),
-                                       "peak_GBps": world * HBM_PEAK_GBS}},
-            "verified": {"frames": nfr, "expected": expect, "bit_exact_payloads": n_ok, "ok": verified,
-                         "note": "the step after the timed region, same continuing stream"},
-            "setup_s": {"iq_generation": round(gen_s, 2)},
         }
+        if args.full:
+            out["roofline"] = roofline
+            out["verified"] = {"frames": nfr, "expected": expect, "bit_exact_payloads": n_ok, "ok": verified,
+                               "note": "the step after the timed region, same continuing stream"}
+        if dumped:
+            out["outputs_dumped"] = dumped
+        out["setup_s"] = {"iq_generation": round(gen_s, 2)}
         if xchg:
             out["exchange"] = xchg
         if harvest:
@@ -533,11 +626,11 @@ def main():
             out.update(variants)
         if cfgs:
             out["configs"] = cfgs
-        if world == 1 and not args.no_variants and not args.pipeline and not args.serial and not os.environ.get("BENCH_DEFAULT_HW_QUEUES") and QUEUES_BEFORE is None:
+        if args.full and world == 1 and not args.no_variants and not args.pipeline and not args.serial and not os.environ.get("BENCH_DEFAULT_HW_QUEUES") and QUEUES_BEFORE is None:
             dq = safely(default_queues_leg, args)
             out.update(dq if "error" not in dq else {"value_default_hw_queues": None, "value_default_hw_queues_note": dq["error"]})
-        if not args.no_cpu and world == 1:                     # the CPU leg is reported at N = 1 only
-            out["cpu_baseline"] = cpu_baseline(ora, prod, slabs[0] if slabs is not None else slabs_keep0, N, M, cp, taper, args.cpu_reps, cfg)
+        if args.full and not args.no_cpu and world == 1:       # the CPU leg is reported at N = 1 only
+            out["cpu_baseline"] = cpu_baseline(load_oracle(), prod, slabs[0] if slabs is not None else slabs_keep0, N, M, cp, taper, args.cpu_reps, cfg)
     if rx is not None:
         rx.close()
     if world > 1:
@@ -545,7 +638,7 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(out))
-    if not verified:
+    if verified is False:
         sys.exit("rank %d: verification failed (%d/%d frames, %d ok)" % (rank, nfr, expect, n_ok))
 
 
@@ -556,7 +649,7 @@ def default_queues_leg(args):
     env = dict(os.environ); env.pop("GPU_MAX_HW_QUEUES", None); env["BENCH_DEFAULT_HW_QUEUES"] = "1"
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(max(10, args.steps // 2)), "--warmup", str(args.warmup), "--reps", "3",
            "--channels", str(args.channels), "--frames", str(args.frames), "--slabs", str(args.slabs), "--payload", str(args.payload),
-           "--no-cpu", "--no-harvest", "--no-aperiodic", "--no-variants", "--no-configs", "--serial-steps", "2"]
+           "--full", "--no-cpu", "--no-harvest", "--no-aperiodic", "--no-variants", "--no-configs", "--serial-steps", "2"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600)
     d = json.loads(r.stdout.decode().strip().split("\n")[-1])
     return {"value_default_hw_queues": d["value"], "value_default_hw_queues_note": "the same loop, same library, GPU_MAX_HW_QUEUES unset (%s), a process of its own; verified %s"

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT; O=gpurun_out/r4g; mkdir -p $O
 for v in ${VARIANTS:-cadence new}; do
   if [ $v = new ]; then unset MCRX_LIB; else export MCRX_LIB=$GRAFT_REPO_ROOT/scratch/libs/libmcrx_$v.so; fi
   echo "== $v"
-  timeout 900 python bench.py --no-cpu --steps 20 --warmup 5 2>$O/bench_$v.err | tail -1 > $O/bench_$v.json
+  timeout 900 python bench.py --full --no-cpu --steps 20 --warmup 5 2>$O/bench_$v.err | tail -1 > $O/bench_$v.json
   python - <<PY
 import json
 d = json.loads(open("$O/bench_$v.json").read())

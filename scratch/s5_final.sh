@@ -1,8 +1,8 @@
 # final lines of the session: python bench.py (default), the driver's form, the C-ABI pipeline on one GPU, bench_duplex.py
 cd $GRAFT_REPO_ROOT; O=gpurun_out/s5/final; mkdir -p $O
-timeout 900 python bench.py 2>/dev/null | tail -1 > $O/bench.json
-timeout 600 python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_steps20.json
-timeout 600 python bench.py --pipeline --steps 20 --warmup 5 --no-cpu 2>/dev/null | tail -1 > $O/bench_pipeline.json
+timeout 900 python bench.py --full 2>/dev/null | tail -1 > $O/bench.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_steps20.json
+timeout 600 python bench.py --full --pipeline --steps 20 --warmup 5 --no-cpu 2>/dev/null | tail -1 > $O/bench_pipeline.json
 timeout 600 python bench_duplex.py 2>/dev/null | tail -1 > $O/duplex.json
 python - <<PY
 import json

@@ -23,7 +23,7 @@ def clean_env():
 @pytest.mark.parametrize("world", [2, 4])
 def test_bench_two_ranks_rehearsed_on_one_gpu(world):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rehearse-on-one-gpu", "--steps", "2", "--warmup", "1",
-           "--reps", "2", "--no-cpu", "--frames", "4", "--slabs", "2", "--serial-steps", "1"]
+           "--reps", "2", "--full", "--no-cpu", "--frames", "4", "--slabs", "2", "--serial-steps", "1"]
     r = subprocess.run(cmd, env=clean_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])          # (a rank whose verification fails exits non-zero)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -61,7 +61,7 @@ def test_c_pipeline_failure_falls_back_on_every_rank():
     pipeline on a fresh receiver everywhere if any rank failed.  Two ranks on ONE device make RCCL refuse the communicator
     (BENCH_REHEARSE_C=1 lets the rehearsal try it): the fall-back has to carry the run, with the reason in the line."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--steps", "2", "--warmup", "1",
-           "--reps", "1", "--no-cpu", "--frames", "4", "--slabs", "2", "--serial-steps", "1"]
+           "--reps", "1", "--full", "--no-cpu", "--frames", "4", "--slabs", "2", "--serial-steps", "1"]
     r = subprocess.run(cmd, env=dict(clean_env(), BENCH_REHEARSE_C="1"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

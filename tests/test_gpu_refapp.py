@@ -10,7 +10,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "liquid-usrp_amd", "lib", "multichannel_rx_ref")
+EXE = os.path.join(ROOT, "oracle", "_ref", "multichannel_rx_ref")
 
 
 @pytest.mark.skipif(not os.path.exists(EXE), reason="reference app binary not built")
@@ -159,7 +159,7 @@ def test_sharded_class_reset_inside_a_payload_delivers_nothing_from_the_padding(
         assert got == want, (mode, [g for g in got if g not in want], [w for w in want if w not in got])
 
 
-TXEXE = os.path.join(ROOT, "liquid-usrp_amd", "lib", "multichannel_tx_ref")
+TXEXE = os.path.join(ROOT, "oracle", "_ref", "multichannel_tx_ref")
 
 
 @pytest.mark.skipif(not os.path.exists(TXEXE), reason="reference app binary not built")
@@ -191,8 +191,8 @@ def test_unchanged_reference_tx_app_feeds_both_receivers(oracle, product, tmp_pa
     rx.close()
 
 
-OTX = os.path.join(ROOT, "liquid-usrp_amd", "lib", "ofdmflexframe_tx_ref")
-ORX = os.path.join(ROOT, "liquid-usrp_amd", "lib", "ofdmflexframe_rx_ref")
+OTX = os.path.join(ROOT, "oracle", "_ref", "ofdmflexframe_tx_ref")
+ORX = os.path.join(ROOT, "oracle", "_ref", "ofdmflexframe_rx_ref")
 
 
 @pytest.mark.skipif(not (os.path.exists(OTX) and os.path.exists(ORX)), reason="reference app binaries not built")
@@ -250,7 +250,7 @@ def test_unchanged_ofdmflexframe_tx_and_rx_apps_loop_back(oracle, product, tmp_p
     assert m and m.group(1) == m.group(2) == m.group(3) and int(m.group(1)) == len(ids)
 
 
-TXRX = os.path.join(ROOT, "liquid-usrp_amd", "lib", "multichannel_txrx_ref")
+TXRX = os.path.join(ROOT, "oracle", "_ref", "multichannel_txrx_ref")
 
 
 @pytest.mark.skipif(not os.path.exists(TXRX), reason="reference app binary not built")
@@ -337,7 +337,7 @@ def test_unchanged_multichannel_txrx_app_hears_its_own_bursts(oracle, product, t
     assert len(got) >= 0.98 * len(sent) and set(got) <= set(sent)
 
 
-FDX = os.path.join(ROOT, "liquid-usrp_amd", "lib", "fullduplex_txrx_ref")
+FDX = os.path.join(ROOT, "oracle", "_ref", "fullduplex_txrx_ref")
 
 
 @pytest.mark.skipif(not os.path.exists(FDX), reason="reference app binary not built")
