@@ -178,6 +178,34 @@ int  mcrx_hip_next_frame(mcrx_hip_t q, mcrx_frame *out);      /* 1 = frame writt
 int  mcrx_hip_drain_count(mcrx_hip_t q, uint64_t *frames, uint64_t *valid, uint64_t *payload_bytes);
 uint64_t mcrx_hip_frames_dropped(mcrx_hip_t q);
 
+/* ---- channel monitor: "what is on the air?" ---------------------------------------------
+ * Per channel of the handle's shard (channel_count, else all N): mean power, peak power and an averaged periodogram of the channel's
+ * own sample stream, taken on the GPU from the channel tiles the synchronizers read -- whether or not anything decodes there.  It
+ * stands in for the two small observation tools among the reference's applications: the text spectrogram that runs a 64-bin transform
+ * behind the front-end resampler, and the program that logs the received signal level.  Definition ("Channel monitor"):
+ * with x_c[n] the channel-rate samples counted from the last enable / reset (stage-level callers: from the first sample they pass),
+ *   segment s = x_c[s nfft .. (s+1) nfft): aligned to the sample index, not to a push; one that straddles two pushes is completed by
+ *   the later push, a trailing partial one is held back until its samples arrive;
+ *   psd[c][k] = mean over whole segments of |sum_n w[n] x_c[s nfft + n] e^{-2 pi i k n / nfft}|^2 / sum_n w[n]^2, k in FFT order (0 = centre);
+ *   level[c] = mean |x_c[n]|^2 and peak[c] = max |x_c[n]|^2 over every sample pushed.
+ * Transform in fp32, sums in fp64, folded in a fixed order: the same pushes give the same bits.  Off in a new handle; while it is off
+ * nothing is launched, recorded or allocated. */
+typedef struct {
+    uint32_t struct_size;        /* sizeof(mcrx_hip_monitor_config) */
+    uint32_t nfft;               /* segment length: 16, 32, 64, 128 or 256; 0 -> 64 */
+    uint32_t window;             /* 0 = rectangular, 1 = Hann 0.5 - 0.5 cos(2 pi n / nfft), 2 = Hamming 0.54 - 0.46 cos(2 pi n / nfft) */
+} mcrx_hip_monitor_config;
+/* switch the monitor on (NULL = defaults: 64 bins, rectangular).  MCRX_EINVAL on a bad nfft / window / handle.  Enabling a monitor
+ * that is on starts it over: sums and the unfinished segment are dropped.  mcrx_hip_reset / _reset_at / _restart do the same. */
+int  mcrx_hip_monitor_enable(mcrx_hip_t q, const mcrx_hip_monitor_config *cfg);
+int  mcrx_hip_monitor_disable(mcrx_hip_t q);
+/* level[nch], peak[nch], psd[nch][nfft] (any may be NULL), the whole segments and the samples they were taken over.  Waits for the
+ * monitor's own launches only, not for the synchronizers.  MCRX_EINVAL while the monitor is off.  reset = 1 starts a new averaging
+ * interval but KEEPS the unfinished segment, so that consecutive intervals tile the stream: one call per display interval is one row
+ * of a waterfall. */
+int  mcrx_hip_monitor_read(mcrx_hip_t q, double *level, float *peak, double *psd, uint64_t *nseg, uint64_t *nsamp, int reset);
+unsigned mcrx_hip_monitor_nfft(mcrx_hip_t q);          /* segment length of the running monitor, 0 = off */
+
 /* ---- stage level (multi-GPU split, parity tests, benchmarks) ------------------------- */
 /* NCO + analysis bank on `nblocks` blocks of 2N samples.  `first_sample` is the absolute
  * index of d_iq[0] (NCO phase); d_halo holds the mcrx_hip_history_blocks() blocks preceding d_iq -- 13 = 2m - 1 for the

@@ -88,6 +88,10 @@ _EXPORTS = {
     "mcrx_hip_kernel_time_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mcrx_hip_kernel_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]),
     "mcrx_hip_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
+    "mcrx_hip_monitor_enable": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mcrx_hip_monitor_disable": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_monitor_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
+    "mcrx_hip_monitor_nfft": (C.c_uint, [C.c_void_p]),
     "mcrx_hip_last_error": (C.c_char_p, []),
     "msresamp_hip_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_float, C.c_float]),
     "msresamp_hip_destroy": (C.c_int, [C.c_void_p]),
@@ -206,6 +210,43 @@ def _stream_ptr(stream):
     return C.c_void_p(stream.cuda_stream)
 
 
+class MonitorConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("nfft", C.c_uint32), ("window", C.c_uint32)]
+
+
+MONITOR_WINDOWS = {"rect": 0, "rectangular": 0, "hann": 1, "hamming": 2}
+
+
+def monitor_omega(num_channels, nfft, channel, kp):
+    """Wideband frequency [radians per wideband sample] of signed bin kp, in (-nfft/2, nfft/2], of `channel`'s spectrum."""
+    N = float(num_channels)
+    return np.pi * (np.asarray(channel, np.float64) - (N - 1.0) / 2.0) / N + 2.0 * np.pi * np.asarray(kp, np.float64) / (nfft * 2.0 * N)
+
+
+class MonitorReading(object):
+    """One reading of the channel monitor: level[nch], peak[nch] (mean / largest |x|^2 per channel), psd[nch, nfft] (averaged
+    periodogram, FFT order: bin 0 is the channel's centre), over nseg whole segments and nsamp samples per channel."""
+
+    def __init__(self, level, peak, psd, nseg, nsamp, num_channels, channel_first=0):
+        self.level, self.peak, self.psd = np.asarray(level, np.float64), np.asarray(peak, np.float32), np.asarray(psd, np.float64)
+        self.nseg, self.nsamp, self.N, self.channel_first = int(nseg), int(nsamp), int(num_channels), int(channel_first)
+
+    def level_db(self):
+        return 10.0 * np.log10(np.maximum(self.level, 1e-300))
+
+    def occupied(self, threshold_db):
+        return self.level_db() > threshold_db
+
+    def wideband(self):
+        """(row, omega): the channels' spectra side by side in wideband frequency order -- per channel the signed bins
+        -nfft/2 + 1 .. nfft/2 -- and the frequency of every bin.  The bank is critically sampled: the rows tile the band."""
+        nch, nfft = self.psd.shape
+        kp = np.arange(-nfft // 2 + 1, nfft // 2 + 1)
+        row = self.psd[:, kp % nfft].reshape(-1)
+        ch = self.channel_first + np.arange(nch)
+        return row, monitor_omega(self.N, nfft, ch[:, None], kp[None, :]).reshape(-1)
+
+
 class multichannelrx(object):
     """GPU multichannel OFDM receiver with the reference class's interface.
 
@@ -239,6 +280,8 @@ class multichannelrx(object):
         self.userdata = list(userdata) if userdata is not None else [None] * num_channels
         self.callback = list(callback) if callback is not None else [None] * num_channels
         self.frames = []            # every frame delivered so far (also handed to the callbacks)
+        self.channel_first = int(c.channel_first)
+        self.nch = int(c.channel_count) if c.channel_count else num_channels - self.channel_first
 
     # ---- reference API -----------------------------------------------------------------
     def GetNumChannels(self):
@@ -377,6 +420,35 @@ class multichannelrx(object):
 
     def frames_dropped(self):
         return int(lib().mcrx_hip_frames_dropped(self._h))
+
+    # ---- channel monitor: level, peak and power spectrum per channel, on the GPU ------------
+    def monitor_enable(self, nfft=64, window="hann"):
+        """Switch the monitor on (or start a running one over).  window: "rect", "hann", "hamming" or the C-ABI's number."""
+        c = MonitorConfig()
+        c.struct_size, c.nfft = C.sizeof(MonitorConfig), int(nfft)
+        c.window = MONITOR_WINDOWS[window] if isinstance(window, str) else int(window)
+        rc = lib().mcrx_hip_monitor_enable(self._h, C.addressof(c))
+        if rc == MCRX_EINVAL:
+            raise ValueError(lib().mcrx_hip_last_error().decode())
+        _check(rc)
+
+    def monitor_disable(self):
+        _check(lib().mcrx_hip_monitor_disable(self._h))
+
+    def monitor_nfft(self):
+        return int(lib().mcrx_hip_monitor_nfft(self._h))
+
+    def monitor_read(self, reset=False):
+        """What the monitor has seen since the last reset (waits for the monitor's launches only).  reset=True starts a new averaging
+        interval and keeps the unfinished segment: one call per display interval gives one waterfall row."""
+        nfft = self.monitor_nfft()
+        if not nfft:
+            raise ValueError("the monitor is off (monitor_enable)")
+        level, peak, psd = np.zeros(self.nch, np.float64), np.zeros(self.nch, np.float32), np.zeros((self.nch, nfft), np.float64)
+        nseg, nsamp = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().mcrx_hip_monitor_read(self._h, level.ctypes.data, peak.ctypes.data, psd.ctypes.data,
+                                           C.byref(nseg), C.byref(nsamp), 1 if reset else 0))
+        return MonitorReading(level, peak, psd, nseg.value, nsamp.value, self.N, self.channel_first)
 
     def close(self):
         if self._h:

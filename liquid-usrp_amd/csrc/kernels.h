@@ -278,4 +278,17 @@ bool sync_payload_splits(const SyncArgs &a);                         // the payl
 hipError_t sync_reset_launch(ChanState *st, uint32_t nch, int64_t cur, float2 *hist0, float2 *hist1, size_t hist_n,
                              uint32_t *nrec, unsigned long long *arena_used, uint32_t *pred_n, hipStream_t stream);
 
+// ---- channel monitor (monitor.hip): level, peak and averaged periodogram per channel over the new tiles of one launch
+struct MonArgs {
+    const float2 *chan;          // [tile][stride][MCRX_TILE_S] granules; the handle's channel c is column off + c
+    uint32_t stride, off, t0, ntiles;      // ... and the new tiles are t0 .. t0 + ntiles - 1
+    uint32_t nch, nfft, window;  // window: 0 rectangular, 1 Hann, 2 Hamming
+    uint32_t carry_len, carry_cap;         // samples per channel in carry_in (< nfft, whole granules); row length of both carries
+    const float2 *carry_in; float2 *carry_out;      // [nch][carry_cap]: the unfinished segment of the previous / of this launch
+    uint32_t nsplit;             // waves per channel: each takes a contiguous share of the segments
+    double *part_psd, *part_level; float *part_peak;      // [nsplit][nch][nfft], [nsplit][nch], [nsplit][nch]: this launch's partial sums
+    double *psd, *level; float *peak;                     // [nch][nfft], [nch], [nch]: the running sums they are folded into, in split order
+};
+hipError_t monitor_launch(const MonArgs &a, hipStream_t st);        // the monitor kernel of a.nfft and the fold behind it
+
 }  // namespace mcrx

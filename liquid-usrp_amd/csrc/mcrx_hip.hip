@@ -269,6 +269,19 @@ struct mcrx_hip_s {
         ev_used[which] -= n;
         return MCRX_OK;
     }
+    // channel monitor (csrc/monitor.hip; mcrx_hip_monitor_*): off in a new handle, nothing below exists until the first enable
+    struct Monitor {
+        bool on = false, allocated = false, clear_pending = false, used = false;
+        uint32_t nfft = 0, window = 0, max_split = 1;
+        double wss = 1.0;                   // sum of the window's squares
+        float2 *d_carry[2] = { nullptr, nullptr }; int carry_cur = 0; uint32_t carry_len = 0;
+        double *d_sums = nullptr;           // [nch][256] psd | [nch] level, then (float) [nch] peak: one block, cleared with one fill
+        size_t sums_bytes = 0;
+        double *d_part = nullptr;           // the launches' partial sums, laid out like d_sums per split
+        int64_t next = 0, origin = 0;       // channel-rate sample the next launch begins at; the sample segment 0 began at
+        uint64_t nseg = 0, nsamp = 0;
+        hipStream_t s_mon = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_last = nullptr;
+    } mon;
     // harvested frames (host)
     std::vector<FrameRec> recs; HostArena arena_host, sarena_host; size_t next_frame = 0;
     uint64_t dropped = 0;
@@ -465,6 +478,56 @@ static int fork_from(mcrx_hip_t q, hipStream_t st)
     return MCRX_OK;
 }
 
+// ---------------------------------------------------------------- channel monitor
+// carry and sums dropped: the sums are cleared in stream order by the next monitor launch (or by the next read)
+static void monitor_restart(mcrx_hip_t q)
+{
+    auto &m = q->mon;
+    if (!m.allocated) return;
+    m.carry_len = 0; m.nseg = 0; m.nsamp = 0; m.clear_pending = true;
+    m.next = m.origin = q->chan_samples;
+}
+static int monitor_clear_sums(mcrx_hip_t q, hipStream_t st)
+{
+    HIPCHK(hipMemsetAsync(q->mon.d_sums, 0, q->mon.sums_bytes, st));
+    q->mon.clear_pending = false;
+    return MCRX_OK;
+}
+// One monitor pass over the tiles of a launch_sync buffer that nobody has counted yet: [max(buf_first, next), end).  Pipelined handles
+// run it on the monitor's own stream behind `st` (the stream the tiles were written on); `behind` is then made to wait for it, so that
+// whoever waits for the launch's synchronizers before reusing the buffer waits for the monitor as well.
+static int launch_monitor(mcrx_hip_t q, const float2 *chan, unsigned stride, unsigned off, int64_t buf_first, int64_t end, hipStream_t st)
+{
+    auto &m = q->mon;
+    int64_t first = std::max(buf_first, m.next);
+    first = buf_first + (first - buf_first + MCRX_TILE - 1) / MCRX_TILE * MCRX_TILE;       // whole tiles of the buffer
+    if (first != m.next) { m.carry_len = 0; m.origin = first; }                            // a gap in a stage-level caller's stream: segments start over
+    const int64_t ntiles = (end - first) / MCRX_TILE;
+    if (ntiles <= 0) return MCRX_OK;
+    if (ntiles > (int64_t)(0x7fffffff / MCRX_TILE)) return fail(MCRX_EINVAL, "monitor: push too long");
+    hipStream_t sm = q->pipelined ? m.s_mon : st;
+    if (sm != st) { HIPCHK(hipEventRecord(m.ev_in, st)); HIPCHK(hipStreamWaitEvent(sm, m.ev_in, 0)); }
+    if (m.clear_pending) RC(monitor_clear_sums(q, sm));
+    const uint64_t total = (uint64_t)m.carry_len + (uint64_t)ntiles * MCRX_TILE, S = total / m.nfft;
+    MonArgs a;
+    a.chan = chan; a.stride = stride; a.off = off; a.t0 = (uint32_t)((first - buf_first) / MCRX_TILE); a.ntiles = (uint32_t)ntiles;
+    a.nch = q->nch; a.nfft = m.nfft; a.window = m.window;
+    a.carry_len = m.carry_len; a.carry_cap = 256;
+    a.carry_in = m.d_carry[m.carry_cur]; a.carry_out = m.d_carry[m.carry_cur ^ 1];
+    // waves per channel: about eight to a SIMD over the whole chip for a handle of few channels, never less than four segments each
+    a.nsplit = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(m.max_split, S / 4));
+    const size_t nb = (size_t)q->nch * m.nfft;
+    a.part_psd = m.d_part; a.part_level = m.d_part + (size_t)m.max_split * nb;
+    a.part_peak = reinterpret_cast<float *>(a.part_level + (size_t)m.max_split * q->nch);
+    a.psd = m.d_sums; a.level = m.d_sums + (size_t)q->nch * 256; a.peak = reinterpret_cast<float *>(a.level + q->nch);
+    HIPCHK(monitor_launch(a, sm));
+    HIPCHK(hipEventRecord(m.ev_last, sm));
+    m.carry_cur ^= 1; m.carry_len = (uint32_t)(total - S * m.nfft);
+    m.nseg += S; m.nsamp += (uint64_t)ntiles * MCRX_TILE; m.next = first + ntiles * MCRX_TILE;
+    m.used = sm != st;
+    return MCRX_OK;
+}
+
 // synchronizers back to SEEK, channelizer history cleared, undelivered device frames dropped
 static int restart_async(mcrx_hip_t q, hipStream_t st, bool from_zero)
 {
@@ -473,6 +536,7 @@ static int restart_async(mcrx_hip_t q, hipStream_t st, bool from_zero)
     q->hist_cur = 0;
     q->last_slot = -1; q->last_ntiles = 0;
     q->pf_in_valid = 0; q->pf_steps = 0; q->pf_have_last = false;
+    monitor_restart(q);
     RC(join_into(q, st));
     // (both result generations: counters zeroed; the prediction lists only survive a Reset(), not a restart from zero)
     for (int g = 0; g < MCRX_GENS; g++) {
@@ -746,6 +810,11 @@ extern "C" int mcrx_hip_destroy(mcrx_hip_t q)
         if (q->ev_dcopy[i]) (void)hipEventDestroy(q->ev_dcopy[i]);
         if (q->ev_ddone[i]) (void)hipEventDestroy(q->ev_ddone[i]);
     }
+    if (q->mon.allocated) {
+        for (void *p : { (void *)q->mon.d_carry[0], (void *)q->mon.d_carry[1], (void *)q->mon.d_sums, (void *)q->mon.d_part }) if (p) (void)hipFree(p);
+        for (hipEvent_t e : { q->mon.ev_in, q->mon.ev_out, q->mon.ev_last }) if (e) (void)hipEventDestroy(e);
+        if (q->mon.s_mon) (void)hipStreamDestroy(q->mon.s_mon);
+    }
     if (q->copy_stream) (void)hipStreamDestroy(q->copy_stream);
     if (q->h_hint) (void)hipHostFree(q->h_hint);
     for (int w = 0; w < MCRX_NKERNELS; w++) for (auto e : q->evring[w]) if (e) (void)hipEventDestroy(e);
@@ -790,6 +859,8 @@ static int launch_sync(mcrx_hip_t q, const float2 *chan, unsigned stride, unsign
 {
     const unsigned slot = (unsigned)(q->seq % q->nslots), next = (unsigned)((q->seq + 1) % q->nslots);
     const int g = q->gen;
+    q->mon.used = false;
+    if (q->mon.on) RC(launch_monitor(q, chan, stride, off, buf_first, end, st));
     if (!q->il_tried) {                    // first synchronizer launch of this handle: the device's shared de-interleaver tables
         q->il_tried = true;
         // (a table that cannot be built -- 40-120 MB plus twice that in scratch -- is no table, not an error: the decoder's in-place passes
@@ -1019,6 +1090,10 @@ static int launch_sync(mcrx_hip_t q, const float2 *chan, unsigned stride, unsign
         if (split || gen_side) HIPCHK(hipEventRecord(q->ev_side_last, sd));
         q->side_last = split || gen_side;
         sw = sd;
+    }
+    if (q->mon.used) {                      // the slot is free again when the monitor has read its tiles, too
+        HIPCHK(hipEventRecord(q->mon.ev_out, q->mon.s_mon));
+        HIPCHK(hipStreamWaitEvent(sw, q->mon.ev_out, 0));
     }
     HIPCHK(hipEventRecord(q->ev_done[slot], sw));
     HIPCHK(hipEventRecord(q->ev_gen[g], sw));
@@ -1596,6 +1671,77 @@ extern "C" int mcrx_hip_reset_at(mcrx_hip_t q, uint64_t chan_position)
     q->chan_samples = (int64_t)chan_position;
     RC(restart_async(q, q->stream, false));
     HIPCHK(hipDeviceSynchronize());
+    return MCRX_OK;
+}
+
+// ---------------------------------------------------------------- channel monitor: C-ABI
+extern "C" int mcrx_hip_monitor_enable(mcrx_hip_t q, const mcrx_hip_monitor_config *cfg)
+{
+    uint32_t nfft = 64, window = 0;
+    if (cfg) {
+        if (cfg->struct_size >= offsetof(mcrx_hip_monitor_config, nfft) + sizeof(uint32_t) && cfg->nfft) nfft = cfg->nfft;
+        if (cfg->struct_size >= offsetof(mcrx_hip_monitor_config, window) + sizeof(uint32_t)) window = cfg->window;
+    }
+    if (nfft != 16 && nfft != 32 && nfft != 64 && nfft != 128 && nfft != 256) return fail(MCRX_EINVAL, "monitor: nfft must be 16, 32, 64, 128 or 256");
+    if (window > 2) return fail(MCRX_EINVAL, "monitor: window must be 0 (rectangular), 1 (Hann) or 2 (Hamming)");
+    if (!q) return fail(MCRX_EINVAL, "null handle");
+    DevScope dev_scope_(q->device);
+    auto &m = q->mon;
+    if (!m.allocated) {
+        // sized for every nfft: carries of 256 samples per channel, sums of 256 bins; partial sums for up to 8192 / nch waves per channel
+        m.max_split = std::max<uint32_t>(1, std::min<uint32_t>(64, (8192 + q->nch - 1) / q->nch));
+        m.sums_bytes = ((size_t)q->nch * 256 + q->nch) * sizeof(double) + (size_t)q->nch * sizeof(float);
+        HIPCHK(hipMalloc((void **)&m.d_carry[0], (size_t)q->nch * 256 * sizeof(float2)));
+        m.allocated = true;                 // (from here on mcrx_hip_destroy frees whatever exists)
+        HIPCHK(hipMalloc((void **)&m.d_carry[1], (size_t)q->nch * 256 * sizeof(float2)));
+        HIPCHK(hipMalloc((void **)&m.d_sums, m.sums_bytes));
+        HIPCHK(hipMalloc((void **)&m.d_part, m.sums_bytes * m.max_split));
+        HIPCHK(hipStreamCreateWithFlags(&m.s_mon, hipStreamNonBlocking));
+        for (hipEvent_t *e : { &m.ev_in, &m.ev_out, &m.ev_last }) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    } else if (m.ev_last) HIPCHK(hipEventSynchronize(m.ev_last));      // a monitor that was on: its launches are over before the sums go
+    m.nfft = nfft; m.window = window;
+    m.wss = 0.0;
+    for (uint32_t n = 0; n < nfft; n++) {
+        const double c = cos(2.0 * M_PI * (double)n / (double)nfft), w = window == 0 ? 1.0 : window == 1 ? 0.5 - 0.5 * c : 0.54 - 0.46 * c;
+        m.wss += w * w;
+    }
+    monitor_restart(q);
+    m.on = true;
+    return MCRX_OK;
+}
+extern "C" int mcrx_hip_monitor_disable(mcrx_hip_t q)
+{
+    if (!q) return fail(MCRX_EINVAL, "null handle");
+    q->mon.on = false;                      // (launches already enqueued finish; buffers stay with the handle)
+    return MCRX_OK;
+}
+extern "C" unsigned mcrx_hip_monitor_nfft(mcrx_hip_t q) { return (q && q->mon.on) ? q->mon.nfft : 0; }
+extern "C" int mcrx_hip_monitor_read(mcrx_hip_t q, double *level, float *peak, double *psd, uint64_t *nseg, uint64_t *nsamp, int reset)
+{
+    if (!q) return fail(MCRX_EINVAL, "null handle");
+    if (!q->mon.on) return fail(MCRX_EINVAL, "the monitor is off (mcrx_hip_monitor_enable)");
+    DevScope dev_scope_(q->device);
+    auto &m = q->mon;
+    HIPCHK(hipEventSynchronize(m.ev_last));              // the monitor's launches only: the synchronizers keep running
+    if (m.clear_pending) { RC(monitor_clear_sums(q, m.s_mon)); HIPCHK(hipStreamSynchronize(m.s_mon)); }
+    const size_t nch = q->nch;
+    std::vector<double> h((m.sums_bytes + sizeof(double) - 1) / sizeof(double));
+    HIPCHK(hipMemcpyAsync(h.data(), m.d_sums, m.sums_bytes, hipMemcpyDeviceToHost, m.s_mon));
+    HIPCHK(hipStreamSynchronize(m.s_mon));
+    const double *hl = h.data() + nch * 256; const float *hp = reinterpret_cast<const float *>(hl + nch);
+    const double kp = m.nseg ? 1.0 / ((double)m.nseg * m.wss) : 0.0, kl = m.nsamp ? 1.0 / (double)m.nsamp : 0.0;
+    for (size_t c = 0; c < nch; c++) {
+        if (level) level[c] = hl[c] * kl;
+        if (peak) peak[c] = hp[c];
+        if (psd) for (uint32_t k = 0; k < m.nfft; k++) psd[c * m.nfft + k] = h[c * m.nfft + k] * kp;
+    }
+    if (nseg) *nseg = m.nseg;
+    if (nsamp) *nsamp = m.nsamp;
+    if (reset) {                            // a new averaging interval; the unfinished segment stays, so that intervals tile the stream
+        RC(monitor_clear_sums(q, m.s_mon));
+        HIPCHK(hipStreamSynchronize(m.s_mon));
+        m.nseg = 0; m.nsamp = 0;
+    }
     return MCRX_OK;
 }
 

@@ -1,6 +1,7 @@
 // multichannelrx.cc -- host class over the C-ABI of libmcrx_hip.so (include/mcrx_hip.h).
 // Mirrors liquid-usrp's lib/multichannelrx.cc: ctor :45-104, dtor :107-132, Reset :135-153,
 // Execute :155-182; the DSP itself runs in the gfx950 kernels.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -49,6 +50,13 @@ struct multichannelrx::impl {
     // destructor synchronizes nothing further) and is not delivered here either.  chan_pos: channel-rate samples
     // (= blocks) pushed since the object was made -- what mcrx_frame::end_sample counts; drop_from: the first padded one.
     uint64_t chan_pos = 0, drop_from = ~0ull;
+    // Channel monitor (include/mcrx_hip.h), switched on from outside the unchanged applications like the front end:
+    //   MCRX_MONITOR=<nfft>        16, 32, 64, 128 or 256: the monitor runs from construction (rectangular window)
+    //   MCRX_MONITOR_FILE=<path>   every Reset() and the destructor append one line per channel of this object's shard, after the last
+    //                              callbacks: channel, level [dB], peak [dB], the spectrum [dB] in signed-bin order -nfft/2+1 .. nfft/2
+    unsigned mon_nfft = 0, ch_first = 0, ch_count = 0;
+    const char *mon_file = NULL;
+    void monitor_report();
     void take(const std::complex<float> *x, size_t n);              // sharded Execute: n samples at position `fill` of the round
     void push_round(multichannelrx *self);
     size_t finish_round(multichannelrx *self);                      // zero the trailing partial block, pad the round with zeros, push it
@@ -152,6 +160,21 @@ multichannelrx::multichannelrx(unsigned int _num_channels, unsigned int _M, unsi
         }
         pimpl->tail.assign(13 * pimpl->K, std::complex<float>(0.f, 0.f));
     }
+    pimpl->ch_first = cfg.channel_first; pimpl->ch_count = cfg.channel_count ? cfg.channel_count : _num_channels;
+    if (getenv("MCRX_MONITOR")) {
+        const int nfft = atoi(getenv("MCRX_MONITOR"));
+        mcrx_hip_monitor_config mc;
+        mc.struct_size = sizeof(mc); mc.nfft = (uint32_t)nfft; mc.window = 0;
+        if (nfft <= 0 || mcrx_hip_monitor_enable(pimpl->h, &mc) != MCRX_OK) {
+            fprintf(stderr, "error: multichannelrx, MCRX_MONITOR = '%s' must be 16, 32, 64, 128 or 256\n", getenv("MCRX_MONITOR"));
+            if (pimpl->pipe) mcrx_hip_pipeline_destroy(pimpl->pipe);
+            mcrx_hip_destroy(pimpl->h);
+            delete pimpl;
+            throw 0;
+        }
+        pimpl->mon_nfft = (unsigned)nfft;
+        pimpl->mon_file = getenv("MCRX_MONITOR_FILE");
+    }
     for (unsigned int i = 0; i < _num_channels; i++) {
         pimpl->userdata.push_back(_userdata ? _userdata[i] : NULL);
         pimpl->callback.push_back(_callback ? _callback[i] : NULL);
@@ -173,6 +196,7 @@ multichannelrx::~multichannelrx()
         mcrx_hip_flush(pimpl->h);
         Deliver();
         pimpl->drop_from = ~0ull;
+        pimpl->monitor_report();
         if (pimpl->pipe) mcrx_hip_pipeline_destroy(pimpl->pipe);
         mcrx_hip_destroy(pimpl->h);
     }
@@ -194,6 +218,25 @@ multichannelrx::~multichannelrx()
         }
     }
     delete pimpl;
+}
+
+// one line per channel of what the monitor has seen since the last report's Reset (MCRX_MONITOR_FILE)
+void multichannelrx::impl::monitor_report()
+{
+    if (!mon_nfft || !mon_file) return;
+    std::vector<double> level(ch_count), psd((size_t)ch_count * mon_nfft);
+    std::vector<float> peak(ch_count);
+    if (mcrx_hip_monitor_read(h, level.data(), peak.data(), psd.data(), NULL, NULL, 0) != MCRX_OK) return;
+    FILE *f = fopen(mon_file, "a");
+    if (!f) { fprintf(stderr, "warning: multichannelrx, cannot append to MCRX_MONITOR_FILE '%s'\n", mon_file); return; }
+    auto db = [](double v) { return 10.0 * log10(v > 1e-30 ? v : 1e-30); };
+    for (unsigned c = 0; c < ch_count; c++) {
+        fprintf(f, "%u %.4f %.4f", ch_first + c, db(level[c]), db((double)peak[c]));
+        for (int kp = -(int)mon_nfft / 2 + 1; kp <= (int)mon_nfft / 2; kp++)
+            fprintf(f, " %.2f", db(psd[(size_t)c * mon_nfft + (size_t)((kp + (int)mon_nfft) % (int)mon_nfft)]));
+        fprintf(f, "\n");
+    }
+    fclose(f);
 }
 
 void multichannelrx::Deliver()
@@ -231,6 +274,7 @@ void multichannelrx::Reset()
         // dropped partial block still count for it).  Every rank gets the same call at the same point of the stream.
         pimpl->drop_from = pimpl->chan_pos + pimpl->fill / pimpl->K;                 // (frames that end in the padding are not delivered)
         const size_t real = pimpl->fill, pushed = pimpl->finish_round(this);         // pushed: 0 (nothing but a partial block) or a whole round
+        if (pimpl->mon_file) { mcrx_hip_pipeline_wait(pimpl->pipe); pimpl->monitor_report(); }      // (the Reset below clears the monitor)
         if (mcrx_hip_pipeline_reset(pimpl->pipe, (long long)real - (long long)pushed) != MCRX_OK) {
             fprintf(stderr, "error: multichannelrx::Reset(), %s\n", mcrx_hip_pipeline_last_error());
             throw 0;
@@ -241,6 +285,11 @@ void multichannelrx::Reset()
         Deliver();
         pimpl->drop_from = ~0ull;
         return;
+    }
+    if (pimpl->mon_file) {                  // the report comes behind the callbacks of everything pushed, and before the Reset clears the monitor
+        mcrx_hip_flush(pimpl->h);
+        Deliver();
+        pimpl->monitor_report();
     }
     mcrx_hip_reset(pimpl->h);
     Deliver();
