@@ -132,8 +132,14 @@ int  mcrx_hip_create(mcrx_hip_t *out, unsigned num_channels, unsigned M, unsigne
                      unsigned taper_len, const unsigned char *p, const mcrx_hip_config *cfg);
 int  mcrx_hip_destroy(mcrx_hip_t q);
 int  mcrx_hip_reset(mcrx_hip_t q);
+/* Channel-rate sample positions (mcrx_hip_reset_at, mcrx_hip_sync, mcrx_frame.end_sample) are 64-bit, but the synchronizers key
+ * their speculation slots by a position packed into 48 bits (spec_key, csrc/ofdmsync.hip): every position a launch handles, the one
+ * behind its last sample included, must stay below MCRX_POSITION_MAX.  A call that would pass it is refused with MCRX_EINVAL --
+ * mcrx_hip_execute_* too, once the stream has run that far (an 8-channel receiver at 25 Msample/s: 5.7 years). */
+#define MCRX_POSITION_MAX (1ll << 48)
 /* the same for a handle driven through the stage-level calls (mcrx_hip_sync: it never learns the stream position by itself):
- * the synchronizers restart in SEEK at channel-rate sample `chan_position`.  What mcrx_hip_pipeline_reset calls. */
+ * the synchronizers restart in SEEK at channel-rate sample `chan_position` (< MCRX_POSITION_MAX, else MCRX_EINVAL).  What
+ * mcrx_hip_pipeline_reset calls. */
 int  mcrx_hip_reset_at(mcrx_hip_t q, uint64_t chan_position);
 unsigned mcrx_hip_num_channels(mcrx_hip_t q);
 
@@ -216,7 +222,8 @@ int  mcrx_hip_channelize(mcrx_hip_t q, const void *d_iq, size_t nblocks, uint64_
                          const void *d_halo, void *d_out, unsigned groups, void *stream);
 /* run the synchronizer bank of this handle's channel shard over d_chan[tile][c][MCRX_TILE],
  * holding channel-rate samples [first_sample, first_sample + nsamples).  The buffer must
- * still contain the M+cp samples preceding the first unconsumed one. */
+ * still contain the M+cp samples preceding the first unconsumed one.  MCRX_EINVAL unless first_sample + nsamples <
+ * MCRX_POSITION_MAX. */
 int  mcrx_hip_sync(mcrx_hip_t q, const void *d_chan, uint64_t first_sample, size_t nsamples, void *stream);
 
 /* benchmark replay: discard undelivered frames and return the object to its
@@ -257,6 +264,11 @@ typedef struct msresamp_hip_s *msresamp_hip_t;
 int    msresamp_hip_create(msresamp_hip_t *out, float rate, float As);
 int    msresamp_hip_destroy(msresamp_hip_t q);
 int    msresamp_hip_reset(msresamp_hip_t q);
+/* msresamp_hip_reset, but the stream continues from input sample `input_position` with zero history: as if that many zeros had
+ * been consumed and their outputs discarded.  Any 64-bit position; MCRX_EINVAL unless it is a multiple of 2^num_stages (the
+ * half-band stages in front of or behind the arbitrary one: one per halving of the rate below 1/2, per doubling above 2).
+ * A running stream needs no such call: the phase arithmetic is periodic and never overflows, however long the stream. */
+int    msresamp_hip_reset_at(msresamp_hip_t q, uint64_t input_position);
 float  msresamp_hip_get_delay(msresamp_hip_t q);
 size_t msresamp_hip_max_output(msresamp_hip_t q, size_t nin);
 int    msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out,

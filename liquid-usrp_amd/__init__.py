@@ -20,6 +20,7 @@ _LIBPATH = os.environ.get("MCRX_LIB") or os.path.join(_HERE, "lib", "libmcrx_hip
 
 MCRX_OK, MCRX_EINVAL, MCRX_ENOMEM, MCRX_EHIP, MCRX_EUNSUPP, MCRX_EOVERFLOW, MCRX_EBUSY = 0, -1, -2, -3, -4, -5, -6
 TILE = 16         # MCRX_TILE (include/mcrx_hip.h)
+POSITION_MAX = 1 << 48      # MCRX_POSITION_MAX: channel-rate positions stay below it (mcrx_hip_reset_at, mcrx_hip_sync)
 TX_TILE = 8       # granules of the transmit side (mctx_hip_traffic_tiles)
 
 LIQUID_CRC_NONE, LIQUID_CRC_32 = 1, 6
@@ -96,6 +97,7 @@ _EXPORTS = {
     "msresamp_hip_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_float, C.c_float]),
     "msresamp_hip_destroy": (C.c_int, [C.c_void_p]),
     "msresamp_hip_reset": (C.c_int, [C.c_void_p]),
+    "msresamp_hip_reset_at": (C.c_int, [C.c_void_p, C.c_uint64]),
     "msresamp_hip_get_delay": (C.c_float, [C.c_void_p]),
     "msresamp_hip_max_output": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "msresamp_hip_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
@@ -302,6 +304,15 @@ class multichannelrx(object):
         _check(lib().mcrx_hip_reset(self._h))
         self._deliver(flush=False)
 
+    def reset_at(self, pos):
+        """Reset() that also moves the stream to channel-rate sample `pos` (mcrx_hip_reset_at): frames then carry end_sample from
+        there.  ValueError beyond MCRX_POSITION_MAX."""
+        rc = lib().mcrx_hip_reset_at(self._h, int(pos))
+        if rc == MCRX_EINVAL:
+            raise ValueError(lib().mcrx_hip_last_error().decode())
+        _check(rc)
+        self._deliver(flush=False)
+
     # ---- additions -----------------------------------------------------------------------
     def Flush(self):
         """Process everything pushed so far and deliver the callbacks."""
@@ -487,8 +498,13 @@ class msresamp(object):
     def get_delay(self):
         return float(lib().msresamp_hip_get_delay(self._h))
 
-    def reset(self):
-        lib().msresamp_hip_reset(self._h)
+    def reset(self, at=0):
+        """Start over with zero history, at input sample `at` of the stream (msresamp_hip_reset_at: a multiple of 2^num_stages)."""
+        rc = lib().msresamp_hip_reset_at(self._h, int(at))
+        if rc == MCRX_EINVAL:
+            raise ValueError(lib().msresamp_hip_last_error().decode())
+        if rc != MCRX_OK:
+            raise McrxError("msresamp_hip_reset_at failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
 
     def execute(self, x, stream=None):
         import torch

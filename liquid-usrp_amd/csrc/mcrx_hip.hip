@@ -1117,6 +1117,8 @@ extern "C" int mcrx_hip_sync(mcrx_hip_t q, const void *d_chan, uint64_t first_sa
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q || !d_chan) return fail(MCRX_EINVAL, "null argument");
+    // (first_sample may be negative: history in front of sample 0)
+    if ((int64_t)first_sample + (int64_t)nsamples >= MCRX_POSITION_MAX) return fail(MCRX_EINVAL, "channel-rate positions must stay below MCRX_POSITION_MAX = 2^48");
     hipStream_t st = stream ? (hipStream_t)stream : q->stream;
     return launch_sync(q, (const float2 *)d_chan, q->nch, 0, (int64_t)first_sample, (int64_t)(first_sample + nsamples), st);
 }
@@ -1233,6 +1235,7 @@ static int run_oversampled(mcrx_hip_t q, const float2 *x, size_t nblocks, uint64
 static int run_blocks(mcrx_hip_t q, const float2 *x, size_t nblocks, uint64_t first_abs, hipStream_t st)
 {
     if (nblocks == 0) return MCRX_OK;
+    if (q->chan_samples + (int64_t)nblocks >= MCRX_POSITION_MAX) return fail(MCRX_EINVAL, "channel-rate positions must stay below MCRX_POSITION_MAX = 2^48");
     const size_t ntiles = nblocks / MCRX_TILE;
     RC(ensure_chan(q, q->hist_tiles + ntiles));
     const int slot = (int)(q->seq % q->nslots);
@@ -1665,6 +1668,7 @@ extern "C" int mcrx_hip_reset_at(mcrx_hip_t q, uint64_t chan_position)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) return fail(MCRX_EINVAL, "null handle");
+    if (chan_position >= (uint64_t)MCRX_POSITION_MAX) return fail(MCRX_EINVAL, "channel-rate positions must stay below MCRX_POSITION_MAX = 2^48");
     HIPCHK(hipDeviceSynchronize());                      // stage-level launches run on the caller's and the handle's streams
     int rc = harvest(q);
     if (rc != MCRX_OK && rc != MCRX_EOVERFLOW) return rc;

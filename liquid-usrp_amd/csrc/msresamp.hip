@@ -14,7 +14,11 @@
 //       v[2k] = u[k-7],   v[2k+1] = sum_{i<14} h1[i] * u[k-13+i]
 // Every output is a closed form of its index, so each stage is one embarrassingly parallel
 // kernel (64-bit integer phase, exact); overlapping 14/27-sample windows are served by L1/L2.
-// Streaming state = absolute sample counters on the host + retained tails of each stage buffer.
+// Streaming state = sample counters on the host + retained tails of each stage buffer.  The counters are NOT absolute for ever:
+// the phase j * step is a 64-bit product with 24 fractional bits, so it wraps once the arbitrary stage's input index reaches 2^40
+// (three hours of a 100 Msample/s stream).  The phase repeats exactly every step / g inputs = 2^24 / g outputs of that stage
+// (g = gcd(step, 2^24)); before every call the host takes whole periods off every counter (rs_rebase), which changes no bit of
+// any output and keeps the kernels' indices below a period plus the samples the stage buffers still hold.
 #include "../../include/mcrx_hip.h"
 #include "design.hpp"
 #include "devscope.hpp"
@@ -296,7 +300,8 @@ struct msresamp_hip_s {
     float *d_h1 = nullptr, *d_hpfb = nullptr;
     std::vector<StageBuf> in;       // decimating: in[0] = resampler input, in[s] = input of half-band s / arbitrary stage;
                                     // interpolating: in[0] = input of the arbitrary stage, in[1 + s] = input of half-band interpolator s
-    long long out_count = 0;        // outputs produced so far (absolute j)
+    long long out_count = 0;        // outputs of the arbitrary stage produced so far (j), less the whole periods taken off by rs_rebase
+    long long per_in = 1, per_out = 1;      // one period of the phase: step / g inputs, 2^24 / g outputs of the arbitrary stage
     hipStream_t stream = nullptr;
 };
 
@@ -324,6 +329,33 @@ static int stage_reserve(msresamp_hip_t q, StageBuf &b, size_t extra, hipStream_
     b.d = nd; b.cap = ncap; b.base = b.end - (long long)keep;
     (void)q;
     return MCRX_OK;
+}
+
+// Sample positions of stage buffer i per input sample of the arbitrary stage (decimating: in[i] runs 2^(num_stages - i) times as
+// fast), or per output of it (interpolating, i >= 1: in[i] is the input of half-band interpolator i - 1); whole periods of those.
+static inline long long rs_period(const msresamp_hip_s *q, unsigned i)
+{
+    if (q->interp) return i ? q->per_out << (i - 1) : q->per_in;
+    return q->per_in << (q->num_stages - i);
+}
+// Take as many whole periods of the phase off every counter as all of them allow (a buffer's base must stay >= 0: samples
+// before 0 read as zeros).  Output j - m * per_out reads input n_j - m * per_in with the fraction of output j: nothing changes.
+static void rs_rebase(msresamp_hip_s *q)
+{
+    const unsigned ns = q->num_stages;
+    long long m = q->out_count / q->per_out;
+    for (unsigned i = 0; i <= ns && m > 0; i++) {
+        const bool counted = !q->interp && ns && i == ns;       // the folded half-band stage's output: counted, never stored
+        m = std::min(m, (counted ? q->in[i].end : q->in[i].base) / rs_period(q, i));
+    }
+    if (m <= 0) return;
+    for (unsigned i = 0; i <= ns; i++) {
+        const bool counted = !q->interp && ns && i == ns;
+        const long long d = m * rs_period(q, i);
+        q->in[i].end -= d;
+        q->in[i].base = counted ? q->in[i].end : q->in[i].base - d;
+    }
+    q->out_count -= m * q->per_out;
 }
 
 // in[0] only ever holds the retained tail of the caller's input: the stages read the new samples where they lie
@@ -354,6 +386,8 @@ extern "C" int msresamp_hip_create(msresamp_hip_t *out, float rate, float As)
         for (unsigned k = 0; k < RS_TAPS; k++)
             hp[(size_t)b * RS_HROW + (RS_TAPS - 1 - k)] = (float)((double)hf[b + k * RS_NPFB] * gain);
     q->step = (unsigned long long)std::llrint((double)(1u << RS_PHASE_BITS) / q->rate_arb);
+    const long long g = (long long)std::min<unsigned long long>(q->step & (~q->step + 1), 1ull << RS_PHASE_BITS);     // gcd(step, 2^24): step's lowest set bit
+    q->per_in = (long long)q->step / g; q->per_out = (1ll << RS_PHASE_BITS) / g;
     if (hipMalloc((void **)&q->d_h1, h1.size() * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&q->d_hpfb, hp.size() * sizeof(float)) != hipSuccess ||
         hipMemcpy(q->d_h1, h1.data(), h1.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
@@ -376,12 +410,24 @@ extern "C" int msresamp_hip_destroy(msresamp_hip_t q)
     return MCRX_OK;
 }
 
-extern "C" int msresamp_hip_reset(msresamp_hip_t q)
+extern "C" int msresamp_hip_reset(msresamp_hip_t q) { return msresamp_hip_reset_at(q, 0); }
+
+// msresamp_hip_reset, but the stream goes on from input sample `input_position` with zero history: as if that many zeros had been
+// consumed and their outputs discarded.  Only the position within a period of the phase matters (rs_rebase).
+extern "C" int msresamp_hip_reset_at(msresamp_hip_t q, uint64_t input_position)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) return MCRX_EINVAL;
-    for (auto &b : q->in) { b.base = 0; b.end = 0; }
-    q->out_count = 0;
+    const unsigned ns = q->num_stages;
+    if (input_position & ((1ull << ns) - 1)) { g_rs_err = "msresamp: a position must be a multiple of 2^num_stages"; return MCRX_EINVAL; }
+    // the arbitrary stage's input index within its period, and the first output that reads a sample from there on
+    const long long r = (long long)((q->interp ? input_position : input_position >> ns) % (uint64_t)q->per_in);
+    const long long j = (long long)((((unsigned long long)r << RS_PHASE_BITS) + q->step - 1) / q->step);
+    for (unsigned i = 0; i <= ns; i++) {
+        StageBuf &b = q->in[i];
+        b.base = b.end = q->interp ? (i ? j << (i - 1) : r) : r << (ns - i);
+    }
+    q->out_count = j;
     return MCRX_OK;
 }
 
@@ -407,6 +453,7 @@ extern "C" int msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, s
     // msresamp -> multichannelrx chains on the default stream unordered: the bank could read samples not yet written.)
     hipStream_t st = (hipStream_t)stream;
     *nout = 0;
+    rs_rebase(q);
     // the first stage reads [retained tail | the caller's new samples]; nothing is copied
     StageBuf &b0 = q->in[0];
     int rc;

@@ -368,7 +368,12 @@ def test_class_switches_on_the_unchanged_receiver_application(oracle, tmp_path):
     out = subprocess.run(args, env=dict(base, MCRX_MONITOR="64", MCRX_MONITOR_FILE=str(mon)), capture_output=True, text=True, timeout=120)
     assert plain.returncode == 0 and out.returncode == 0, out.stderr[-2000:]
     pk = r"channel: (\d+) rx packet id:\s+(\d+)\n"
-    assert re.findall(pk, out.stdout) == re.findall(pk, plain.stdout) and len(re.findall(pk, out.stdout)) >= 3 * N
+    # (the application stops after 0.5 s of WALL time and the stand-in radio replays the file unpaced: how many passes a run
+    #  gets through depends on the machine's load, so the two runs print the same sequence to different lengths -- on a busy
+    #  machine they differed by four passes either way.  What the monitor must not change is the sequence.)
+    got_mon, got_plain = re.findall(pk, out.stdout), re.findall(pk, plain.stdout)
+    both = min(len(got_mon), len(got_plain))
+    assert got_mon[:both] == got_plain[:both] and both >= 3 * N
     rows = _monitor_lines(mon)
     assert len(rows) % N == 0 and len(rows) >= N and [r[0] for r in rows[:N]] == list(range(N))
     assert all(len(r[3]) == 64 for r in rows)
