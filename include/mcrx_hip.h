@@ -109,6 +109,15 @@ typedef struct {
                                     through the block decoder of rounds 3-4: the same bytes on every frame that decodes, a fixed 192-step overlap
                                     instead of an exact one on frames that do not); 1 = with the handle (callers that know they will receive the code);
                                     2 = never.  An allocation that fails is not an error: the block decoder stays */
+    uint32_t input_format;       /* wideband samples the handle takes: 0 = cf32 (interleaved float re, im; default), 1 = sc16 (interleaved int16 re, im,
+                                    what radios deliver): half the bytes over the host link and into the channelizer, converted where its oscillator
+                                    multiplies.  An sc16 sample (re, im) MEANS (re * 2^-15, im * 2^-15) -- exact in fp32 for every int16, -32768
+                                    included, so an sc16 handle gives bit for bit what a cf32 handle gives on those floats.  (UHD's own sc16 -> fc32
+                                    converter scales by 1 / 32767: the 3e-5 difference in gain is the caller's business.)  The format belongs to the
+                                    handle: pushes go through mcrx_hip_execute_host_sc16 / _device_sc16, the plain calls return MCRX_EINVAL (and the
+                                    _sc16 calls on a cf32 handle); mcrx_hip_channelize reads d_iq / d_halo in it.  Any other value: MCRX_EINVAL.
+                                    Out of scope, refused with MCRX_EUNSUPP: sc16 with single_channel (no channelizer to convert in), with
+                                    front_end = 2, and mcrx_hip_pipeline_create on an sc16 handle.  The C++ classes take std::complex<float> only */
 } mcrx_hip_config;
 
 /* One decoded frame = the arguments of the reference's framesync_callback
@@ -151,6 +160,14 @@ int  mcrx_hip_execute_host(mcrx_hip_t q, const float *iq, size_t nsamples);
  * enqueued, but waits first (once per turn of the handle's buffer sets) for the launch one turn back, so the host stays
  * within 2 * MCRX_SLOTS launches of the device and the acquisition's feedback words reach the next launches. */
 int  mcrx_hip_execute_device(mcrx_hip_t q, const void *d_iq, size_t nsamples, void *stream);
+/* the same two calls for a handle made with input_format = 1: nsamples sc16 samples = 2 * nsamples int16 (re, im interleaved).
+ * Staging, the host-to-device copy and the channelizer's reads are half the cf32 calls'.  A call of the other format's kind
+ * returns MCRX_EINVAL and processes nothing.
+ * Alignment of device buffers: the channelizer fetches two samples per lane as one vector, so d_iq (and mcrx_hip_channelize's d_halo)
+ * must be 16-byte aligned on a cf32 handle and 8-byte aligned on an sc16 handle (4 when num_channels = 1). */
+int  mcrx_hip_execute_host_sc16(mcrx_hip_t q, const int16_t *iq, size_t nsamples);
+int  mcrx_hip_execute_device_sc16(mcrx_hip_t q, const void *d_iq, size_t nsamples, void *stream);
+unsigned mcrx_hip_input_format(mcrx_hip_t q);          /* the handle's mcrx_hip_config::input_format (0 for a null handle) */
 
 /* wait for all pushed samples, gather decoded frames (ordered by end time, then channel). */
 int  mcrx_hip_flush(mcrx_hip_t q);
@@ -215,7 +232,7 @@ unsigned mcrx_hip_monitor_nfft(mcrx_hip_t q);          /* segment length of the 
 /* ---- stage level (multi-GPU split, parity tests, benchmarks) ------------------------- */
 /* NCO + analysis bank on `nblocks` blocks of 2N samples.  `first_sample` is the absolute
  * index of d_iq[0] (NCO phase); d_halo holds the mcrx_hip_history_blocks() blocks preceding d_iq -- 13 = 2m - 1 for the
- * reference's bank, 27 for front_end = 1 -- (NULL = zeros).
+ * reference's bank, 27 for front_end = 1 -- (NULL = zeros).  Both are read in the handle's input format (cf32, or sc16 words).
  * Output layout: out[g][tile][c][MCRX_TILE] cf32 with channel = g*(N/groups)+c,
  * tile = block / MCRX_TILE; nblocks must be a multiple of MCRX_TILE. */
 int  mcrx_hip_channelize(mcrx_hip_t q, const void *d_iq, size_t nblocks, uint64_t first_sample,

@@ -45,7 +45,11 @@ class Config(C.Structure):
                 ("payload_soft", C.c_uint32), ("slab_blocks", C.c_uint32), ("channel_first", C.c_uint32),
                 ("channel_count", C.c_uint32), ("batch_samples", C.c_uint32), ("single_channel", C.c_uint32),
                 ("serial", C.c_uint32), ("chunk_blocks", C.c_uint32), ("defer_samples", C.c_uint32), ("front_end", C.c_uint32), ("skip_framesyms", C.c_uint32),
-                ("worker_build", C.c_uint32), ("acquisition", C.c_uint32), ("scout_build", C.c_uint32), ("conv_scratch", C.c_uint32)]
+                ("worker_build", C.c_uint32), ("acquisition", C.c_uint32), ("scout_build", C.c_uint32), ("conv_scratch", C.c_uint32),
+                ("input_format", C.c_uint32)]
+
+
+INPUT_FORMATS = {"cf32": 0, "sc16": 1}      # mcrx_hip_config::input_format
 
 
 class FrameC(C.Structure):
@@ -65,6 +69,9 @@ _EXPORTS = {
     "mcrx_hip_num_channels": (C.c_uint, [C.c_void_p]),
     "mcrx_hip_execute_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mcrx_hip_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mcrx_hip_execute_host_sc16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mcrx_hip_execute_device_sc16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mcrx_hip_input_format": (C.c_uint, [C.c_void_p]),
     "mcrx_hip_flush": (C.c_int, [C.c_void_p]),
     "mcrx_hip_poll": (C.c_int, [C.c_void_p]),
     "mcrx_hip_discard": (C.c_int, [C.c_void_p]),
@@ -260,6 +267,9 @@ class multichannelrx(object):
                 (stats is the :class:`Frame`: evm, rssi, cfo, framesyms, ...)
     Callbacks run on the calling thread at flush points (buffer full, Flush(), Reset(), close()),
     in the reference's order (frame end time, then channel).
+
+    Keyword arguments are the fields of mcrx_hip_config.  input_format="sc16" (or 1) makes a receiver of 16-bit integer IQ:
+    Execute then takes int16 arrays of interleaved (re, im) pairs, a sample meaning (re, im) * 2^-15.
     """
 
     def __init__(self, num_channels, M, cp_len, taper_len, p=None, userdata=None, callback=None, **cfg):
@@ -270,6 +280,10 @@ class multichannelrx(object):
         c.struct_size = C.sizeof(Config)
         c.payload_soft = 1
         for k, v in cfg.items():
+            if k == "input_format" and isinstance(v, str):
+                if v not in INPUT_FORMATS:
+                    raise ValueError("input_format must be one of %s" % sorted(INPUT_FORMATS))
+                v = INPUT_FORMATS[v]
             setattr(c, k, v)
         rc = lib().mcrx_hip_create(C.byref(self._h), num_channels, M, cp_len, taper_len,
                                    None if parr is None else parr.ctypes.data, C.addressof(c))
@@ -284,17 +298,46 @@ class multichannelrx(object):
         self.frames = []            # every frame delivered so far (also handed to the callbacks)
         self.channel_first = int(c.channel_first)
         self.nch = int(c.channel_count) if c.channel_count else num_channels - self.channel_first
+        self.input_format = int(c.input_format)
 
     # ---- reference API -----------------------------------------------------------------
     def GetNumChannels(self):
         return self.N
 
     def Execute(self, x, num_samples=None, stream=None):
-        """Push samples: a complex64 numpy array (host) or a torch complex64 CUDA tensor (HBM)."""
+        """Push samples: a complex64 numpy array (host) or a torch complex64 CUDA tensor (HBM).  An sc16 receiver
+        (input_format="sc16") takes an int16 numpy array or a torch int16 CUDA tensor of interleaved (re, im) pairs instead;
+        num_samples counts samples (pairs).  TypeError on the wrong dtype for an sc16 receiver, and on int16 for a cf32 one (whose other
+        inputs are taken as before)."""
+        sc16 = self.input_format == INPUT_FORMATS["sc16"]
         if hasattr(x, "is_cuda") and x.is_cuda:
+            import torch
+            if sc16:
+                if x.dtype != torch.int16:
+                    raise TypeError("this receiver takes int16 device tensors (interleaved re, im), not %s" % x.dtype)
+                if not x.is_contiguous():
+                    raise ValueError("device samples must be contiguous")
+                n = int(x.numel()) // 2 if num_samples is None else int(num_samples)
+                _check(lib().mcrx_hip_execute_device_sc16(self._h, _dptr(x), n, _stream_ptr(stream)))
+                return
+            if x.dtype == torch.int16:
+                raise TypeError("int16 samples need a receiver made with input_format=\"sc16\"")
             n = int(x.numel()) if num_samples is None else int(num_samples)
             _check(lib().mcrx_hip_execute_device(self._h, _dptr(x), n, _stream_ptr(stream)))
             return
+        if sc16:
+            a = np.asarray(x)
+            if a.dtype != np.int16:
+                raise TypeError("this receiver takes int16 samples (interleaved re, im), not %s" % a.dtype)
+            a = np.ascontiguousarray(a)
+            if a.size % 2:
+                raise ValueError("an sc16 buffer holds (re, im) pairs: odd number of int16")
+            n = a.size // 2 if num_samples is None else int(num_samples)
+            _check(lib().mcrx_hip_execute_host_sc16(self._h, a.ctypes.data, n), allow=(MCRX_EOVERFLOW,))
+            self._deliver(flush=False)
+            return
+        if getattr(x, "dtype", None) == np.int16:
+            raise TypeError("int16 samples need a receiver made with input_format=\"sc16\"")
         a = np.ascontiguousarray(x, np.complex64)
         n = a.size if num_samples is None else int(num_samples)
         _check(lib().mcrx_hip_execute_host(self._h, a.ctypes.data, n), allow=(MCRX_EOVERFLOW,))   # drops are counted
@@ -397,6 +440,7 @@ class multichannelrx(object):
         return int(lib().mcrx_hip_history_blocks(self._h))
 
     def channelize(self, d_iq, nblocks, first_sample, d_out, groups=1, d_halo=None, stream=None):
+        """mcrx_hip_channelize: d_iq and d_halo in the receiver's input format (complex64, or int16 pairs), d_out complex64 tiles."""
         _check(lib().mcrx_hip_channelize(self._h, _dptr(d_iq), nblocks, first_sample, _dptr(d_halo),
                                          _dptr(d_out), groups, _stream_ptr(stream)))
 

@@ -26,7 +26,7 @@
 // fetched 1.85 x their algorithmic bytes: profiles/r3_v4_traffic.json) -- and the per-destination chunking an
 // xGMI all-to-all needs.  A round of 8 blocks fills one half of every granule; the next round of the same
 // workgroup fills the other (slabs are whole tiles), so the halves meet in that XCD's L2.
-// HBM-bound by design: 8 B read + 4 B written per wideband sample.
+// HBM-bound by design: 8 B read + 4 B written per wideband sample (4 + 4 from 16-bit integer input, below).
 //
 // Round 6: the kernel is a template of the taps per column P, and the oversampled front end (cfg.front_end = 1: liquid's
 // firpfbch2 analysis bank, 2N channels at twice the channel rate, + a half-band decimator per kept channel) runs through it
@@ -38,6 +38,13 @@
 // 8 + 8 (oscillator pass) + 8 + 16 (bank at rate 2) + 8 + 4 (adapter) = 52 over three kernels.  The rotation by s is where a
 // column's FIR output lands in the LDS tile; the taps of 1024 columns x 28 do not fit LDS beside the tile (112 + 68 KB), so
 // the newest TL = 22 of every column live in LDS and the oldest six come from a table in L2 at the start of every round.
+//
+// Input formats (template parameter IN; kernels.h: CH_IN_CF32 / CH_IN_SC16).  An sc16 sample is one 32-bit word, int16 re in the low half
+// and int16 im in the high half, and means (re, im) * 2^-15.  The word stays packed from the load to the mixer, which converts the halves
+// and scales them (both exact for every int16) where the sample is first used: from there on the arithmetic is the cf32 launch's on the
+// dequantised floats, word for word.  (Folding the 2^-15 into the oscillator value is just as exact and four multiplies per block
+// cheaper, but that build of K = 1024 spilled 32 bytes where this one and its cf32 twin spill none.)  8 B read + 4 B written per
+// wideband sample become 4 + 4.
 #include "devel.h"
 #include "devmath.h"
 #include "kernels.h"
@@ -66,6 +73,10 @@ __device__ __forceinline__ void lds_barrier()
 {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
+
+// what a thread holds of one sample between the load and the mixer
+template <int IN> struct RawOf { typedef float2 type; };
+template <> struct RawOf<CH_IN_SC16> { typedef uint32_t type; };
 
 template <int K> struct Log2 { enum { v = 1 + Log2<K / 2>::v }; };
 template <> struct Log2<1> { enum { v = 0 }; };
@@ -142,9 +153,11 @@ template <int K, int C, int T, int P> struct Geo {
 // granule stores' LDS sources and HBM destinations) are computed once per launch, not once per use.
 // P = taps per column: a.taps is the column tap table tap[j][n], j = 0 the newest block's tap, P * K floats.
 // SHIFT: column n's FIR output goes to tile column (n + a.col_shift) mod K (the oversampled front end's rotation).
-template <int K, int C, int T, int P, bool SHIFT, bool EDGE>
+template <int K, int C, int T, int P, bool SHIFT, int IN, bool EDGE>
 __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *tile)
 {
+    typedef typename RawOf<IN>::type Raw;
+    constexpr bool SC16 = IN == CH_IN_SC16;
     constexpr int TPS = K / C;              // threads per slab
     constexpr int NS = T / TPS;             // slabs per workgroup
     constexpr int N = K / 2;
@@ -196,16 +209,29 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
     // raw samples of block b (relative to a.x), columns n0..n0+C-1; zeros outside the stream
     // Branch free on purpose: a load inside a divergent `if` gets an s_waitcnt vmcnt(0) at the
     // join, which would serialise the round's loads into one HBM round trip each.
-    auto load_raw = [&](long long b, float2 (&dst)[C]) {
-        const float2 *src = a.x + n0;                                   // always mapped
+    const Raw *const xin = static_cast<const Raw *>(a.x), *const hin = static_cast<const Raw *>(a.halo);
+    auto load_raw = [&](long long b, Raw (&dst)[C]) {
+        const Raw *src = xin + n0;                                      // always mapped
         if constexpr (EDGE) {
             const bool inx = b >= 0 && b < (long long)a.nblocks;
-            const bool inh = b < 0 && a.halo != nullptr;
-            if (inx) src = a.x + (size_t)b * K + n0;
-            if (inh) src = a.halo + (size_t)(b + H) * K + n0;
-        } else src = a.x + (size_t)b * K + n0;
+            const bool inh = b < 0 && hin != nullptr;
+            if (inx) src = xin + (size_t)b * K + n0;
+            if (inh) src = hin + (size_t)(b + H) * K + n0;
+        } else if constexpr (SC16) src = xin + (uint32_t)((uint32_t)b * (uint32_t)K + (uint32_t)n0);      // (a 32-bit sample offset from the uniform base: no 64-bit
+                                                                                                         //  address pair per block in flight; launch_one checks the range)
+        else src = xin + (size_t)b * K + n0;
         // the value is not touched here (that would wait for it): the mixer zeroes blocks outside the stream
-        if constexpr (C == 2) {
+        if constexpr (SC16) {           // one 8-byte vector per lane (two samples): a wave reads 512 contiguous bytes of a block row
+            if constexpr (C == 2) {
+#if CH_NT_LOAD
+                typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+                const v2u v = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(src));
+#else
+                const uint2 v = *reinterpret_cast<const uint2 *>(src);
+#endif
+                dst[0] = v.x; dst[1] = v.y;
+            } else dst[0] = src[0];
+        } else if constexpr (C == 2) {
 #if CH_NT_LOAD
             typedef float v4f __attribute__((ext_vector_type(4)));
             const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(src));
@@ -227,7 +253,8 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
     auto osc_next_block = [&](float &sn, float &cs) {
         const float s2 = fmaf(sn, ck8, cs * sk8), c2 = fmaf(cs, ck8, -(sn * sk8)); sn = s2; cs = c2;
     };
-    auto mix_with = [&](long long b, float sn, float cs, float2 (&dst)[C]) {
+    // src -> dst; cf32 mixes in place (src and dst are the same window entry), sc16 unpacks the word here, where it is first used
+    auto mix_with = [&](long long b, float sn, float cs, const Raw (&src)[C], float2 (&dst)[C]) {
         // blocks outside the stream become zeros: a zeroed oscillator (by value; the caller's copy keeps turning)
         // zeroes both columns, two selects per block instead of four.  (Clamped loads return finite samples.)
         if constexpr (EDGE) {
@@ -237,7 +264,10 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
 #pragma unroll
         for (int c = 0; c < C; c++) {
             if (c > 0) { const float s2 = fmaf(sn, cd1, cs * sd1), c2 = fmaf(cs, cd1, -(sn * sd1)); sn = s2; cs = c2; }
-            dst[c] = make_float2(fmaf(dst[c].x, cs, dst[c].y * sn), fmaf(dst[c].y, cs, -(dst[c].x * sn)));
+            float x, y;
+            if constexpr (SC16) { x = (float)(int16_t)(src[c] & 0xffffu) * 0x1p-15f; y = (float)((int32_t)src[c] >> 16) * 0x1p-15f; }
+            else { x = src[c].x; y = src[c].y; }
+            dst[c] = make_float2(fmaf(x, cs, y * sn), fmaf(y, cs, -(x * sn)));
         }
     };
 
@@ -245,10 +275,14 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
     // round r+1 are requested into s[H..H+7] right after round r's FIR has consumed them, so
     // the HBM latency hides under the FFT stages; they are mixed in place when the round starts.
     float2 s[H + CH_R][C];
+    // sc16: the packed words wait in w[] -- all H + 8 at the start, then only the round's new blocks in w[H ..]: half the registers of
+    // the cf32 build's in-flight blocks across the FFT stages
+    Raw w[SC16 ? H + CH_R : 1][C];
+    auto raw = [&](int i) -> Raw (&)[C] { if constexpr (SC16) return w[i]; else return s[i]; };
     // (slabs past the end of the stream run on clamped addresses and zeros; their stores are masked.
     //  Keeping this straight-line matters: a load under a branch is waited for at the join.)
 #pragma unroll
-    for (int i = 0; i < H + CH_R; i++) load_raw(bs - H + i, s[i]);
+    for (int i = 0; i < H + CH_R; i++) load_raw(bs - H + i, raw(i));
     {   // the history blocks bs-H .. bs-1 sit in the groups of 8 starting at bs - 8 HG, ..., bs - 8 (the first one from position HSKIP on)
         constexpr int HG = (H + CH_R - 1) / CH_R, HSKIP = HG * CH_R - H;
         static_assert(CH_R == 8, "groups of 8");
@@ -259,7 +293,7 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
             osc_start(bs - (long long)CH_R * (HG - g), sn, cs);
 #pragma unroll
             for (int k = 0; k < CH_R; k++) {
-                if (g > 0 || k >= HSKIP) { mix_with(bs - H + i, sn, cs, s[i]); i++; }
+                if (g > 0 || k >= HSKIP) { mix_with(bs - H + i, sn, cs, raw(i), s[i]); i++; }
                 osc_next_block(sn, cs);
             }
         }
@@ -326,7 +360,7 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
                 float sn, cs;
                 osc_start(b0, sn, cs);
 #pragma unroll
-                for (int r = 0; r < CH_R; r++) { mix_with(b0 + r, sn, cs, s[H + r]); osc_next_block(sn, cs); }
+                for (int r = 0; r < CH_R; r++) { mix_with(b0 + r, sn, cs, raw(H + r), s[H + r]); osc_next_block(sn, cs); }
             }
 #pragma unroll
             for (int r = 0; r < CH_R; r++) {
@@ -358,7 +392,7 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
                 float sn, cs;
                 osc_start(b0, sn, cs);
 #pragma unroll
-                for (int r = 0; r < CH_R; r++) { mix_with(b0 + r, sn, cs, s[H + r]); osc_next_block(sn, cs); }
+                for (int r = 0; r < CH_R; r++) { mix_with(b0 + r, sn, cs, raw(H + r), s[H + r]); osc_next_block(sn, cs); }
             }
             // (CH_RH outputs per pass: the accumulators of all eight at once cost 16 more registers than the kernel has)
 #pragma unroll
@@ -401,7 +435,7 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
             for (int c = 0; c < C; c++) s[i][c] = s[i + CH_R][c];
         // next round's blocks (past the slab's last round: clamped, never used)
 #pragma unroll
-        for (int r = 0; r < CH_R; r++) load_raw(b0 + CH_R + r, s[H + r]);
+        for (int r = 0; r < CH_R; r++) load_raw(b0 + CH_R + r, raw(H + r));
         lds_barrier();
 
         // ---- NS*CH_R independent K-point FFTs, in place
@@ -469,18 +503,18 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
     }
 }
 
-template <int K, int C, int T, int P, bool SHIFT>
+template <int K, int C, int T, int P, bool SHIFT, int IN>
 __global__ __launch_bounds__(T) void channelizer_kernel(ChanArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float2 tile[];     // [NS][CH_R][ROWP], then the taps in LDS
     constexpr int NS = T / (K / C), H = P - 1;
     const long long s0 = (long long)blockIdx.x * NS;
     const long long first = s0 * (long long)a.slab_blocks - H, last = (s0 + NS) * (long long)a.slab_blocks + CH_R;
-    if (first >= 0 && last <= (long long)a.nblocks) channelizer_rounds<K, C, T, P, SHIFT, false>(a, tile);
-    else channelizer_rounds<K, C, T, P, SHIFT, true>(a, tile);
+    if (first >= 0 && last <= (long long)a.nblocks) channelizer_rounds<K, C, T, P, SHIFT, IN, false>(a, tile);
+    else channelizer_rounds<K, C, T, P, SHIFT, IN, true>(a, tile);
 }
 
-template <int K, int C, int T, int P, bool SHIFT>
+template <int K, int C, int T, int P, bool SHIFT, int IN>
 static hipError_t launch_one(const ChanArgs &a, hipStream_t st)
 {
     constexpr int NS = T / (K / C);
@@ -491,10 +525,12 @@ static hipError_t launch_one(const ChanArgs &a, hipStream_t st)
     // granule stores are addressed by 32-bit offsets in 16-byte units: 64 GB of output per launch
     if ((unsigned long long)(K / 2) * ((unsigned long long)a.ntiles + (unsigned long long)NS * a.slab_blocks / MCRX_TILE_S + 1ull) * (MCRX_TILE_S / 2) >= (1ull << 32))
         return hipErrorInvalidValue;
+    // sc16 interior loads are addressed by 32-bit sample offsets from a.x: 4 Gi samples (16 GB of input) per launch
+    if (IN == CH_IN_SC16 && (unsigned long long)a.nblocks * K >= (1ull << 32)) return hipErrorInvalidValue;
     static PerDeviceOnce attr_done;          // (per instantiation; devscope.hpp)
-    hipError_t e = raise_lds_limit((const void *)channelizer_kernel<K, C, T, P, SHIFT>, lds, attr_done);
+    hipError_t e = raise_lds_limit((const void *)channelizer_kernel<K, C, T, P, SHIFT, IN>, lds, attr_done);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((channelizer_kernel<K, C, T, P, SHIFT>), dim3(grid), dim3(T), lds, st, a);
+    hipLaunchKernelGGL((channelizer_kernel<K, C, T, P, SHIFT, IN>), dim3(grid), dim3(T), lds, st, a);
     return hipGetLastError();
 }
 
@@ -507,6 +543,15 @@ static hipError_t launch_one(const ChanArgs &a, hipStream_t st)
 #define CG_T 256
 #define CH_P CH_P_REF
 #define CH_H (CH_P_REF - 1)
+// one wideband sample as cf32: an sc16 word converted and scaled (both exact), so that the two formats share every later rounding
+template <int IN> __device__ __forceinline__ float2 sample_cf32(const void *p, size_t i)
+{
+    if constexpr (IN == CH_IN_SC16) {
+        const uint32_t v = static_cast<const uint32_t *>(p)[i];
+        return make_float2((float)(int16_t)(v & 0xffffu) * 0x1p-15f, (float)((int32_t)v >> 16) * 0x1p-15f);
+    } else return static_cast<const float2 *>(p)[i];
+}
+template <int IN>
 __global__ __launch_bounds__(CG_T) void channelizer_generic_kernel(ChanArgs a, uint32_t K)
 {
     extern __shared__ __attribute__((aligned(16))) float2 gl[];        // V[CH_R][K], then W[K]
@@ -528,8 +573,8 @@ __global__ __launch_bounds__(CG_T) void channelizer_generic_kernel(ChanArgs a, u
             const long long b = b0 - CH_H + i;
             float2 x = make_float2(0.f, 0.f);
             bool valid = false;
-            if (b >= 0 && b < (long long)a.nblocks) { x = a.x[(size_t)b * K + n]; valid = true; }
-            else if (b < 0 && a.halo != nullptr && b + CH_H >= 0) { x = a.halo[(size_t)(b + CH_H) * K + n]; valid = true; }
+            if (b >= 0 && b < (long long)a.nblocks) { x = sample_cf32<IN>(a.x, (size_t)b * K + n); valid = true; }
+            else if (b < 0 && a.halo != nullptr && b + CH_H >= 0) { x = sample_cf32<IN>(a.halo, (size_t)(b + CH_H) * K + n); valid = true; }
             float2 u = make_float2(0.f, 0.f);
             if (valid) u = mix_down_hw(x, (t0 + (uint32_t)(b * (long long)K + n)) * dth);
 #pragma unroll
@@ -587,20 +632,21 @@ uint32_t channelizer_auto_slab(unsigned K, size_t nblocks, unsigned ncu)
     return (uint32_t)slab;
 }
 
-hipError_t channelizer_launch(unsigned K, unsigned P, const ChanArgs &a, hipStream_t st)
+template <int IN>
+static hipError_t launch_format(unsigned K, unsigned P, const ChanArgs &a, hipStream_t st)
 {
     if (P == CH_P_OVS) {                    // the composite bank of the oversampled front end: power-of-two channel counts only
         switch (K) {
-        case 2:    return launch_one<2, 1, 256, CH_P_OVS, true>(a, st);
-        case 4:    return launch_one<4, 2, 256, CH_P_OVS, true>(a, st);
-        case 8:    return launch_one<8, 2, 256, CH_P_OVS, true>(a, st);
-        case 16:   return launch_one<16, 2, 256, CH_P_OVS, true>(a, st);
-        case 32:   return launch_one<32, 2, 256, CH_P_OVS, true>(a, st);
-        case 64:   return launch_one<64, 2, 256, CH_P_OVS, true>(a, st);
-        case 128:  return launch_one<128, 2, 256, CH_P_OVS, true>(a, st);
-        case 256:  return launch_one<256, 2, 256, CH_P_OVS, true>(a, st);
-        case 512:  return launch_one<512, 2, 512, CH_P_OVS, true>(a, st);     // (two slabs per workgroup: with 256 threads the taps + tile would leave one wave per SIMD)
-        case 1024: return launch_one<1024, 2, 512, CH_P_OVS, true>(a, st);
+        case 2:    return launch_one<2, 1, 256, CH_P_OVS, true, IN>(a, st);
+        case 4:    return launch_one<4, 2, 256, CH_P_OVS, true, IN>(a, st);
+        case 8:    return launch_one<8, 2, 256, CH_P_OVS, true, IN>(a, st);
+        case 16:   return launch_one<16, 2, 256, CH_P_OVS, true, IN>(a, st);
+        case 32:   return launch_one<32, 2, 256, CH_P_OVS, true, IN>(a, st);
+        case 64:   return launch_one<64, 2, 256, CH_P_OVS, true, IN>(a, st);
+        case 128:  return launch_one<128, 2, 256, CH_P_OVS, true, IN>(a, st);
+        case 256:  return launch_one<256, 2, 256, CH_P_OVS, true, IN>(a, st);
+        case 512:  return launch_one<512, 2, 512, CH_P_OVS, true, IN>(a, st);     // (two slabs per workgroup: with 256 threads the taps + tile would leave one wave per SIMD)
+        case 1024: return launch_one<1024, 2, 512, CH_P_OVS, true, IN>(a, st);
         default:   return hipErrorInvalidValue;
         }
     }
@@ -609,25 +655,32 @@ hipError_t channelizer_launch(unsigned K, unsigned P, const ChanArgs &a, hipStre
         if (a.nblocks == 0) return hipSuccess;
         const size_t lds = (size_t)(CH_R + 1) * K * sizeof(float2);
         static PerDeviceOnce gen_done;
-        hipError_t e = raise_lds_limit((const void *)channelizer_generic_kernel, 160 * 1024, gen_done);
+        hipError_t e = raise_lds_limit((const void *)channelizer_generic_kernel<IN>, 160 * 1024, gen_done);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(channelizer_generic_kernel, dim3(a.nblocks / CH_R), dim3(CG_T), lds, st, a, (uint32_t)K);
+        hipLaunchKernelGGL(channelizer_generic_kernel<IN>, dim3(a.nblocks / CH_R), dim3(CG_T), lds, st, a, (uint32_t)K);
         return hipGetLastError();
     }
     switch (K) {
-    case 2:    return launch_one<2, 1, 256, CH_P_REF, false>(a, st);
-    case 4:    return launch_one<4, 2, 256, CH_P_REF, false>(a, st);
-    case 8:    return launch_one<8, 2, 256, CH_P_REF, false>(a, st);
-    case 16:   return launch_one<16, 2, 256, CH_P_REF, false>(a, st);
-    case 32:   return launch_one<32, 2, 256, CH_P_REF, false>(a, st);
-    case 64:   return launch_one<64, 2, 256, CH_P_REF, false>(a, st);
-    case 128:  return launch_one<128, 2, 256, CH_P_REF, false>(a, st);
-    case 256:  return launch_one<256, 2, 256, CH_P_REF, false>(a, st);
-    case 512:  return launch_one<512, 2, 256, CH_P_REF, false>(a, st);
+    case 2:    return launch_one<2, 1, 256, CH_P_REF, false, IN>(a, st);
+    case 4:    return launch_one<4, 2, 256, CH_P_REF, false, IN>(a, st);
+    case 8:    return launch_one<8, 2, 256, CH_P_REF, false, IN>(a, st);
+    case 16:   return launch_one<16, 2, 256, CH_P_REF, false, IN>(a, st);
+    case 32:   return launch_one<32, 2, 256, CH_P_REF, false, IN>(a, st);
+    case 64:   return launch_one<64, 2, 256, CH_P_REF, false, IN>(a, st);
+    case 128:  return launch_one<128, 2, 256, CH_P_REF, false, IN>(a, st);
+    case 256:  return launch_one<256, 2, 256, CH_P_REF, false, IN>(a, st);
+    case 512:  return launch_one<512, 2, 256, CH_P_REF, false, IN>(a, st);
     case 1024: { static const int c1 = devel_env("MCRX_CHAN_C1") ? atoi(devel_env("MCRX_CHAN_C1")) : 0;
-                 return c1 ? launch_one<1024, 1, 1024, CH_P_REF, false>(a, st) : launch_one<1024, 2, 512, CH_P_REF, false>(a, st); }
+                 return c1 ? launch_one<1024, 1, 1024, CH_P_REF, false, IN>(a, st) : launch_one<1024, 2, 512, CH_P_REF, false, IN>(a, st); }
     default:   return hipErrorInvalidValue;
     }
+}
+
+hipError_t channelizer_launch(unsigned K, unsigned P, unsigned in_fmt, const ChanArgs &a, hipStream_t st)
+{
+    if (in_fmt == CH_IN_CF32) return launch_format<CH_IN_CF32>(K, P, a, st);
+    if (in_fmt == CH_IN_SC16) return launch_format<CH_IN_SC16>(K, P, a, st);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace mcrx

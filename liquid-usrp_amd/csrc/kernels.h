@@ -12,9 +12,12 @@ namespace mcrx {
 #define MCRX_HDR_DEC 14
 
 // ---------------------------------------------------------------- channelizer.hip
+// wideband input formats (== mcrx_hip_config::input_format): cf32 = interleaved float re, im; sc16 = interleaved int16 re, im,
+// a sample meaning (re, im) * 2^-15 -- both the conversion and the scaling are exact in fp32 for every int16
+enum { CH_IN_CF32 = 0, CH_IN_SC16 = 1 };
 struct ChanArgs {
-    const float2 *x;            // new wideband samples, nblocks * K
-    const float2 *halo;         // the P - 1 blocks preceding x (NULL = zeros: cold start)
+    const void *x;              // new wideband samples, nblocks * K, in the launch's input format (8 or 4 bytes each)
+    const void *halo;           // the P - 1 blocks preceding x, same format (NULL = zeros: cold start)
     const float *taps;          // column tap table tap[j][n]: column n's tap on the block j back (j = 0: the newest), P * K floats
     float2 *out;                // out[g][tile][c][16]
     uint32_t nblocks;           // blocks in x (multiple of 16)
@@ -28,8 +31,9 @@ struct ChanArgs {
 int channelizer_supported(unsigned K);
 // blocks per workgroup slab such that the grid is a whole number of waves over `ncu` compute units
 uint32_t channelizer_auto_slab(unsigned K, size_t nblocks, unsigned ncu);
-// P = taps per column: 14 = the reference's bank (any even K <= 2048), 28 = the oversampled front end's composite bank (power-of-two K <= 1024)
-hipError_t channelizer_launch(unsigned K, unsigned P, const ChanArgs &a, hipStream_t st);
+// P = taps per column: 14 = the reference's bank (any even K <= 2048), 28 = the oversampled front end's composite bank (power-of-two K <= 1024);
+// in_fmt = CH_IN_CF32 / CH_IN_SC16: what a.x and a.halo hold
+hipError_t channelizer_launch(unsigned K, unsigned P, unsigned in_fmt, const ChanArgs &a, hipStream_t st);
 
 // ---------------------------------------------------------------- ofdmsync.hip
 // The two named deviations from liquid-dsp's ofdmframesync in the S1 stage -- the same

@@ -67,7 +67,9 @@ static int coding_tables(CodingDev *out)
 }
 
 // ---------------------------------------------------------------- small kernels
-__global__ void hist_update_kernel(const float2 *old_hist, const float2 *x, uint64_t nx, float2 *new_hist, uint64_t nh)
+// (T = one wideband sample in the handle's input format: float2, or the packed 32-bit word of an sc16 pair)
+template <class T>
+__global__ void hist_update_kernel(const T *old_hist, const T *x, uint64_t nx, T *new_hist, uint64_t nh)
 {
     // new_hist = last nh samples of concat(old_hist[nh], x[nx])
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -205,9 +207,12 @@ struct mcrx_hip_s {
     uint64_t total_samples = 0;             // wideband samples accepted since creation (NCO phase)
     uint64_t stage_first = 0;               // absolute index of h_stage[0]
     int64_t chan_samples = 0;               // channel-rate samples produced since creation
-    float2 *d_hist[2] = { nullptr, nullptr }; int hist_cur = 0;
-    float2 *d_in = nullptr;                 // device staging (stage_cap samples)
-    float2 *h_stage = nullptr; size_t stage_cap = 0, stage_fill = 0;   // pinned host staging (samples)
+    // the handle's wideband input format (mcrx_hip_config::input_format == kernels.h: CH_IN_*) and its bytes per sample.  The raw-sample
+    // history, both stagings and the bulk path's device buffers hold samples in that format: bytes, indexed in samples * ss
+    uint32_t in_fmt = CH_IN_CF32; size_t ss = sizeof(float2);
+    char *d_hist[2] = { nullptr, nullptr }; int hist_cur = 0;
+    char *d_in = nullptr;                   // device staging (stage_cap samples)
+    char *h_stage = nullptr; size_t stage_cap = 0, stage_fill = 0;     // pinned host staging (samples)
     float2 *d_chan[MCRX_SLOTS] = {}; size_t chan_cap_tiles = 0;
     unsigned hist_tiles = 0; uint64_t defer = 0;
     // taps per column of the bank channelizer_kernel runs and the blocks of FIR history it needs in front of every push: 14 / 13 = the
@@ -220,7 +225,7 @@ struct mcrx_hip_s {
     uint64_t pf_in_valid = 0, pf_steps = 0; size_t pf_last_blocks = 0; bool pf_have_last = false;
     hipStream_t stream = nullptr;
     // large host buffers skip the staging copy: chunks go from the caller's memory to one of two device buffers
-    float2 *d_direct[2] = { nullptr, nullptr }; size_t direct_cap = 0; int direct_idx = 0; bool direct_used[2] = { false, false };
+    char *d_direct[2] = { nullptr, nullptr }; size_t direct_cap = 0; int direct_idx = 0; bool direct_used[2] = { false, false };
     hipStream_t copy_stream = nullptr; hipEvent_t ev_dcopy[2] = { nullptr, nullptr }, ev_ddone[2] = { nullptr, nullptr };
     uint64_t min_frame = 1;                 // channel-rate samples of the shortest possible frame
     uint64_t pending_bound = 0;             // upper bound of frame records produced since the last harvest
@@ -528,6 +533,9 @@ static int launch_monitor(mcrx_hip_t q, const float2 *chan, unsigned stride, uns
     return MCRX_OK;
 }
 
+// the raw-sample history of one buffer, rounded up to whole 16-byte units (what sync_reset_launch clears: an even number of cf32)
+static size_t hist_bytes(mcrx_hip_t q) { return ((size_t)q->hist_blocks * q->K * q->ss + 15) & ~(size_t)15; }
+
 // synchronizers back to SEEK, channelizer history cleared, undelivered device frames dropped
 static int restart_async(mcrx_hip_t q, hipStream_t st, bool from_zero)
 {
@@ -540,8 +548,9 @@ static int restart_async(mcrx_hip_t q, hipStream_t st, bool from_zero)
     RC(join_into(q, st));
     // (both result generations: counters zeroed; the prediction lists only survive a Reset(), not a restart from zero)
     for (int g = 0; g < MCRX_GENS; g++) {
-        HIPCHK(sync_reset_launch(q->d_st, q->nch, q->chan_samples, g == 0 ? q->d_hist[0] : nullptr, g == 0 ? q->d_hist[1] : nullptr,
-                                 (size_t)q->hist_blocks * q->K, q->d_nrec[g], q->d_arena_used[g],
+        HIPCHK(sync_reset_launch(q->d_st, q->nch, q->chan_samples, g == 0 ? reinterpret_cast<float2 *>(q->d_hist[0]) : nullptr,
+                                 g == 0 ? reinterpret_cast<float2 *>(q->d_hist[1]) : nullptr,
+                                 hist_bytes(q) / sizeof(float2), q->d_nrec[g], q->d_arena_used[g],
                                  (from_zero && g == 0) ? q->d_pred_n : nullptr, st));
         q->gen_used[g] = false; q->gen_closed[g] = false; q->gen_abandoned[g] = false;
     }
@@ -563,6 +572,12 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
     if (taper > cp) return fail(MCRX_EINVAL, "error: multichannelrx, taper length cannot exceed cyclic prefix length");
     const bool bypass = cfg && cfg->struct_size >= offsetof(mcrx_hip_config, single_channel) + sizeof(uint32_t) && cfg->single_channel;
     if (bypass && N != 1) return fail(MCRX_EINVAL, "single_channel needs num_channels == 1");
+    const uint32_t in_fmt = (cfg && cfg->struct_size >= offsetof(mcrx_hip_config, input_format) + sizeof(uint32_t)) ? cfg->input_format : 0u;
+    if (in_fmt != CH_IN_CF32 && in_fmt != CH_IN_SC16) return fail(MCRX_EINVAL, "input_format must be 0 (cf32) or 1 (sc16)");
+    // sc16 ends where the channelizer's oscillator multiplies: configurations without channelizer_kernel in front take cf32 only
+    if (in_fmt == CH_IN_SC16 && bypass) return fail(MCRX_EUNSUPP, "input_format = 1 (sc16) needs the channelizer: not with single_channel");
+    if (in_fmt == CH_IN_SC16 && cfg->struct_size >= offsetof(mcrx_hip_config, front_end) + sizeof(uint32_t) && cfg->front_end == 2)
+        return fail(MCRX_EUNSUPP, "input_format = 1 (sc16) is not built for front_end = 2 (the oversampled front end stage by stage)");
     if (!bypass && !channelizer_supported(2 * N)) return fail(MCRX_EUNSUPP, "at most 1024 channels");
     if (M > 1024) return fail(MCRX_EUNSUPP, "at most 1024 subcarriers");
     int ndev = 0;
@@ -572,6 +587,7 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
     mcrx_hip_t q = new mcrx_hip_s();
     q->device = current_device();
     q->N = N; q->K = bypass ? 1 : 2 * N; q->M = M; q->cp = cp; q->taper = taper; q->bypass = bypass;
+    q->in_fmt = in_fmt; q->ss = in_fmt == CH_IN_SC16 ? 2 * sizeof(int16_t) : sizeof(float2);
     if (q->od.init(M, cp, taper, p) != 0) { delete q; return fail(MCRX_EINVAL, "invalid subcarrier allocation"); }
     if (cfg) memcpy(&q->cfg, cfg, std::min<size_t>(cfg->struct_size ? cfg->struct_size : sizeof(*cfg), sizeof(q->cfg)));
     else q->cfg.payload_soft = 1;
@@ -729,15 +745,15 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
             if ((rc = q->alloc(&q->d_anchor, q->nch))) return bail(rc);
         }
     }
-    if ((rc = q->alloc(&q->d_hist[0], (size_t)q->hist_blocks * q->K))) return bail(rc);
-    if ((rc = q->alloc(&q->d_hist[1], (size_t)q->hist_blocks * q->K))) return bail(rc);
+    if ((rc = q->alloc(&q->d_hist[0], hist_bytes(q)))) return bail(rc);
+    if ((rc = q->alloc(&q->d_hist[1], hist_bytes(q)))) return bail(rc);
     // host staging for Execute(): whole tiles of MCRX_TILE blocks
     size_t tile_samples = (size_t)MCRX_TILE * q->K;
     size_t want = q->cfg.batch_samples ? q->cfg.batch_samples : ((size_t)1 << 20);
     q->stage_cap = std::max<size_t>(1, (want + tile_samples - 1) / tile_samples) * tile_samples;
-    if (hipHostMalloc((void **)&q->h_stage, q->stage_cap * sizeof(float2), hipHostMallocDefault) != hipSuccess)
+    if (hipHostMalloc((void **)&q->h_stage, q->stage_cap * q->ss, hipHostMallocDefault) != hipSuccess)
         return bail(fail(MCRX_ENOMEM, "pinned staging allocation failed"));
-    if ((rc = q->alloc(&q->d_in, q->stage_cap))) return bail(rc);
+    if ((rc = q->alloc(&q->d_in, q->stage_cap * q->ss))) return bail(rc);
     // (blocking streams: work a caller puts on the legacy default stream -- e.g. a torch copy of a result buffer --
     //  still orders against them, as it did when everything ran on one stream)
     if (hipStreamCreate(&q->stream) != hipSuccess) return bail(fail(MCRX_EHIP, "hipStreamCreate failed"));
@@ -824,6 +840,7 @@ extern "C" int mcrx_hip_destroy(mcrx_hip_t q)
 }
 
 extern "C" unsigned mcrx_hip_num_channels(mcrx_hip_t q) { return q ? q->N : 0; }
+extern "C" unsigned mcrx_hip_input_format(mcrx_hip_t q) { return q ? q->in_fmt : 0; }
 extern "C" uint32_t mcrx_hip_nco_step(mcrx_hip_t q) { return q ? q->dtheta : 0; }
 extern "C" unsigned mcrx_hip_history_blocks(mcrx_hip_t q) { return q ? q->hist_blocks : 0; }
 extern "C" int mcrx_hip_get_taps(mcrx_hip_t q, float *h, size_t n)
@@ -834,8 +851,8 @@ extern "C" int mcrx_hip_get_taps(mcrx_hip_t q, float *h, size_t n)
 }
 
 // ---------------------------------------------------------------- stage level
-static int launch_channelizer(mcrx_hip_t q, const float2 *x, size_t nblocks, uint64_t first_sample,
-                              const float2 *halo, float2 *out, unsigned groups, size_t ntiles_stride, hipStream_t st)
+static int launch_channelizer(mcrx_hip_t q, const void *x, size_t nblocks, uint64_t first_sample,
+                              const void *halo, float2 *out, unsigned groups, size_t ntiles_stride, hipStream_t st)
 {
     if (nblocks == 0) return MCRX_OK;
     if (nblocks % MCRX_TILE) return fail(MCRX_EINVAL, "nblocks must be a multiple of MCRX_TILE (16)");
@@ -847,7 +864,7 @@ static int launch_channelizer(mcrx_hip_t q, const float2 *x, size_t nblocks, uin
     a.first_sample_lo = (uint32_t)first_sample; a.dtheta = q->dtheta;
     a.ntiles = (uint32_t)ntiles_stride; a.cg = q->N / groups; a.col_shift = q->col_shift;
     RC(q->ev_begin(0, st));
-    HIPCHK(channelizer_launch(q->K, q->chan_P, a, st));
+    HIPCHK(channelizer_launch(q->K, q->chan_P, q->in_fmt, a, st));
     RC(q->ev_end(0, st));
     return MCRX_OK;
 }
@@ -1110,7 +1127,7 @@ extern "C" int mcrx_hip_channelize(mcrx_hip_t q, const void *d_iq, size_t nblock
     if (q && q->oversampled) return fail(MCRX_EUNSUPP, "front_end = 2 (the oversampled front end stage by stage) runs inside execute_host / execute_device only");
     if (!q || !d_iq || !d_out) return fail(MCRX_EINVAL, "null argument");
     hipStream_t st = stream ? (hipStream_t)stream : q->stream;
-    return launch_channelizer(q, (const float2 *)d_iq, nblocks, first_sample, (const float2 *)d_halo,
+    return launch_channelizer(q, d_iq, nblocks, first_sample, d_halo,      // (both in the handle's input format)
                               (float2 *)d_out, groups, nblocks / MCRX_TILE, st);
 }
 extern "C" int mcrx_hip_sync(mcrx_hip_t q, const void *d_chan, uint64_t first_sample, size_t nsamples, void *stream)
@@ -1232,7 +1249,8 @@ static int run_oversampled(mcrx_hip_t q, const float2 *x, size_t nblocks, uint64
 
 // channelize + synchronize `nblocks` (multiple of MCRX_TILE) blocks sitting in device memory, readable in `st`'s order.
 // Launch k writes the channel tiles of slot k % 3: [history: the last hist_tiles tiles of launch k-1][ntiles new].
-static int run_blocks(mcrx_hip_t q, const float2 *x, size_t nblocks, uint64_t first_abs, hipStream_t st)
+// x: wideband samples in the handle's input format.
+static int run_blocks(mcrx_hip_t q, const void *x, size_t nblocks, uint64_t first_abs, hipStream_t st)
 {
     if (nblocks == 0) return MCRX_OK;
     if (q->chan_samples + (int64_t)nblocks >= MCRX_POSITION_MAX) return fail(MCRX_EINVAL, "channel-rate positions must stay below MCRX_POSITION_MAX = 2^48");
@@ -1255,14 +1273,19 @@ static int run_blocks(mcrx_hip_t q, const float2 *x, size_t nblocks, uint64_t fi
     if (q->bypass)      // the input already is the channel's sample stream (one channel: its tiles are contiguous)
         HIPCHK(hipMemcpyAsync(buf + q->hist_tiles * tile_elems, x, nblocks * sizeof(float2), hipMemcpyDeviceToDevice, sc));
     else if (q->oversampled)
-        RC(run_oversampled(q, x, nblocks, first_abs, buf + q->hist_tiles * tile_elems, sc));
+        RC(run_oversampled(q, static_cast<const float2 *>(x), nblocks, first_abs, buf + q->hist_tiles * tile_elems, sc));      // (cf32 handles only: create)
     else
         RC(launch_channelizer(q, x, nblocks, first_abs, q->d_hist[q->hist_cur], buf + q->hist_tiles * tile_elems, 1, ntiles, sc));
     // FIR history: the last 13 (27) blocks of (history, x)
     if (!q->bypass && !q->oversampled) {
         const uint64_t nh = (uint64_t)q->hist_blocks * q->K;
-        hipLaunchKernelGGL(hist_update_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, sc,
-                           q->d_hist[q->hist_cur], x, (uint64_t)nblocks * q->K, q->d_hist[1 - q->hist_cur], nh);
+        const dim3 hg((unsigned)((nh + 255) / 256));
+        if (q->in_fmt == CH_IN_SC16)
+            hipLaunchKernelGGL(hist_update_kernel<uint32_t>, hg, dim3(256), 0, sc, reinterpret_cast<const uint32_t *>(q->d_hist[q->hist_cur]),
+                               static_cast<const uint32_t *>(x), (uint64_t)nblocks * q->K, reinterpret_cast<uint32_t *>(q->d_hist[1 - q->hist_cur]), nh);
+        else
+            hipLaunchKernelGGL(hist_update_kernel<float2>, hg, dim3(256), 0, sc, reinterpret_cast<const float2 *>(q->d_hist[q->hist_cur]),
+                               static_cast<const float2 *>(x), (uint64_t)nblocks * q->K, reinterpret_cast<float2 *>(q->d_hist[1 - q->hist_cur]), nh);
         HIPCHK(hipGetLastError());
         q->hist_cur ^= 1;
     }
@@ -1282,11 +1305,11 @@ static int process_staged(mcrx_hip_t q)
     const size_t tile_samples = (size_t)MCRX_TILE * q->K;
     const size_t n = (q->stage_fill / tile_samples) * tile_samples;
     if (n == 0) return MCRX_OK;
-    HIPCHK(hipMemcpyAsync(q->d_in, q->h_stage, n * sizeof(float2), hipMemcpyHostToDevice, q->stream));
+    HIPCHK(hipMemcpyAsync(q->d_in, q->h_stage, n * q->ss, hipMemcpyHostToDevice, q->stream));
     RC(run_blocks(q, q->d_in, n / q->K, q->stage_first, q->stream));
     HIPCHK(hipStreamSynchronize(q->stream));        // staging buffers are reused (the channelizer has read them; decoding goes on)
     const size_t rest = q->stage_fill - n;
-    if (rest) memmove(q->h_stage, q->h_stage + n, rest * sizeof(float2));
+    if (rest) memmove(q->h_stage, q->h_stage + n * q->ss, rest * q->ss);
     q->stage_fill = rest; q->stage_first += n;
     return MCRX_OK;
 }
@@ -1300,7 +1323,7 @@ static uint64_t record_bound(mcrx_hip_t q, uint64_t blocks) { return ((blocks + 
 // Bulk Execute(buf, n): whole tiles go straight from the caller's (pageable) memory into one of two device
 // buffers on a copy stream while the previous chunk is still being processed; frames are harvested only when
 // the record pool could otherwise fill up.  What does not fill a tile is left for the staging path.
-static int execute_direct(mcrx_hip_t q, const float2 *&src, size_t &nsamples, bool &overflow)
+static int execute_direct(mcrx_hip_t q, const char *&src, size_t &nsamples, bool &overflow)
 {
     const size_t tile_samples = (size_t)MCRX_TILE * q->K;
     if (q->stage_fill || nsamples < 64 * tile_samples) return MCRX_OK;
@@ -1322,7 +1345,7 @@ static int execute_direct(mcrx_hip_t q, const float2 *&src, size_t &nsamples, bo
             for (int i = 0; i < 2; i++) {
                 if (q->d_direct[i]) (void)hipFree(q->d_direct[i]);
                 q->d_direct[i] = nullptr; q->direct_used[i] = false;
-                HIPCHK(hipMalloc((void **)&q->d_direct[i], take * sizeof(float2)));
+                HIPCHK(hipMalloc((void **)&q->d_direct[i], take * q->ss));
             }
             q->direct_cap = take;
         }
@@ -1336,7 +1359,7 @@ static int execute_direct(mcrx_hip_t q, const float2 *&src, size_t &nsamples, bo
         double t0 = now_s();
         if (q->direct_used[b]) HIPCHK(hipEventSynchronize(q->ev_ddone[b]));
         q->t_wait += now_s() - t0; t0 = now_s();
-        HIPCHK(hipMemcpyAsync(q->d_direct[b], src, take * sizeof(float2), hipMemcpyHostToDevice, q->copy_stream));
+        HIPCHK(hipMemcpyAsync(q->d_direct[b], src, take * q->ss, hipMemcpyHostToDevice, q->copy_stream));
         HIPCHK(hipEventRecord(q->ev_dcopy[b], q->copy_stream));
         HIPCHK(hipStreamWaitEvent(q->stream, q->ev_dcopy[b], 0));
         q->t_copy += now_s() - t0; t0 = now_s();
@@ -1348,31 +1371,31 @@ static int execute_direct(mcrx_hip_t q, const float2 *&src, size_t &nsamples, bo
         q->t_copy += now_s() - t0;
         q->pending_bound += bound;
         q->total_samples += take; q->stage_first = q->total_samples;
-        src += take; nsamples -= take;
+        src += take * q->ss; nsamples -= take;
     }
     return MCRX_OK;
 }
 
-extern "C" int mcrx_hip_execute_host(mcrx_hip_t q, const float *iq, size_t nsamples)
+static const char *const k_fmt_mismatch = "input format mismatch: the _sc16 calls serve handles made with input_format = 1, the plain ones cf32 handles";
+
+// the host push of both formats: `src` holds nsamples samples of q->ss bytes
+static int execute_host_any(mcrx_hip_t q, const char *src, size_t nsamples)
 {
-    DevScope dev_scope_(q ? q->device : -1);
-    if (!q || (!iq && nsamples)) return fail(MCRX_EINVAL, "null argument");
-    const float2 *src = reinterpret_cast<const float2 *>(iq);
     bool overflow = false;
     const size_t tile_samples = (size_t)MCRX_TILE * q->K;
     if (q->stage_fill && nsamples >= 64 * tile_samples) {
         // a partial tile is waiting: complete it from this buffer so that the bulk path can take over
         const size_t need = std::min(nsamples, (tile_samples - q->stage_fill % tile_samples) % tile_samples);
-        memcpy(q->h_stage + q->stage_fill, src, need * sizeof(float2));
-        q->stage_fill += need; q->total_samples += need; src += need; nsamples -= need;
+        memcpy(q->h_stage + q->stage_fill * q->ss, src, need * q->ss);
+        q->stage_fill += need; q->total_samples += need; src += need * q->ss; nsamples -= need;
         RC(process_staged(q));
         q->pending_bound += record_bound(q, q->stage_cap / q->K);
     }
     RC(execute_direct(q, src, nsamples, overflow));
     while (nsamples) {
         const size_t take = std::min(nsamples, q->stage_cap - q->stage_fill);
-        memcpy(q->h_stage + q->stage_fill, src, take * sizeof(float2));
-        q->stage_fill += take; q->total_samples += take; src += take; nsamples -= take;
+        memcpy(q->h_stage + q->stage_fill * q->ss, src, take * q->ss);
+        q->stage_fill += take; q->total_samples += take; src += take * q->ss; nsamples -= take;
         if (q->stage_fill == q->stage_cap) {
             RC(process_staged(q));
             int rc = harvest(q);                // frames become deliverable as soon as a batch is done
@@ -1382,11 +1405,23 @@ extern "C" int mcrx_hip_execute_host(mcrx_hip_t q, const float *iq, size_t nsamp
     }
     return overflow ? fail(MCRX_EOVERFLOW, "frame pool exhausted: frames were dropped (raise max_frames)") : MCRX_OK;
 }
-
-extern "C" int mcrx_hip_execute_device(mcrx_hip_t q, const void *d_iq, size_t nsamples, void *stream)
+extern "C" int mcrx_hip_execute_host(mcrx_hip_t q, const float *iq, size_t nsamples)
 {
     DevScope dev_scope_(q ? q->device : -1);
-    if (!q || (!d_iq && nsamples)) return fail(MCRX_EINVAL, "null argument");
+    if (!q || (!iq && nsamples)) return fail(MCRX_EINVAL, "null argument");
+    if (q->in_fmt != CH_IN_CF32) return fail(MCRX_EINVAL, k_fmt_mismatch);
+    return execute_host_any(q, reinterpret_cast<const char *>(iq), nsamples);
+}
+extern "C" int mcrx_hip_execute_host_sc16(mcrx_hip_t q, const int16_t *iq, size_t nsamples)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q || (!iq && nsamples)) return fail(MCRX_EINVAL, "null argument");
+    if (q->in_fmt != CH_IN_SC16) return fail(MCRX_EINVAL, k_fmt_mismatch);
+    return execute_host_any(q, reinterpret_cast<const char *>(iq), nsamples);
+}
+
+static int execute_device_any(mcrx_hip_t q, const void *d_iq, size_t nsamples, void *stream)
+{
     if (q->stage_fill) return fail(MCRX_EINVAL, "host samples are still staged: flush before pushing device buffers");
     if (nsamples % ((size_t)MCRX_TILE * q->K)) return fail(MCRX_EINVAL, "device pushes must be whole tiles of MCRX_TILE = 16 blocks (32*N samples)");
     hipStream_t st = stream ? (hipStream_t)stream : q->stream;
@@ -1395,15 +1430,29 @@ extern "C" int mcrx_hip_execute_device(mcrx_hip_t q, const void *d_iq, size_t ns
     const size_t nblocks = nsamples / q->K;
     size_t chunk = q->cfg.struct_size >= offsetof(mcrx_hip_config, chunk_blocks) + sizeof(uint32_t) && q->cfg.chunk_blocks
                        ? ((size_t)q->cfg.chunk_blocks + MCRX_TILE - 1) / MCRX_TILE * MCRX_TILE : nblocks;
-    const float2 *x = (const float2 *)d_iq;
+    const char *x = static_cast<const char *>(d_iq);
     for (size_t b = 0; b < nblocks; b += chunk) {
         const size_t nb = std::min(chunk, nblocks - b);
-        RC(run_blocks(q, x + b * q->K, nb, q->total_samples, st));
+        RC(run_blocks(q, x + b * q->K * q->ss, nb, q->total_samples, st));
         q->total_samples += nb * q->K;
     }
     q->stage_first = q->total_samples;
     q->pending_bound += record_bound(q, nblocks);
     return MCRX_OK;
+}
+extern "C" int mcrx_hip_execute_device(mcrx_hip_t q, const void *d_iq, size_t nsamples, void *stream)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q || (!d_iq && nsamples)) return fail(MCRX_EINVAL, "null argument");
+    if (q->in_fmt != CH_IN_CF32) return fail(MCRX_EINVAL, k_fmt_mismatch);
+    return execute_device_any(q, d_iq, nsamples, stream);
+}
+extern "C" int mcrx_hip_execute_device_sc16(mcrx_hip_t q, const void *d_iq, size_t nsamples, void *stream)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q || (!d_iq && nsamples)) return fail(MCRX_EINVAL, "null argument");
+    if (q->in_fmt != CH_IN_SC16) return fail(MCRX_EINVAL, k_fmt_mismatch);
+    return execute_device_any(q, d_iq, nsamples, stream);
 }
 
 extern "C" int mcrx_hip_stream_wait(mcrx_hip_t q, void *stream)

@@ -144,6 +144,7 @@ extern "C" int mcrx_hip_pipeline_create(mcrx_hip_pipeline_t *out, mcrx_hip_t rx,
 {
     if (!out || !rx) return pfail(MCRX_EINVAL, "null argument");
     *out = nullptr;
+    if (mcrx_hip_input_format(rx) != 0) return pfail(MCRX_EUNSUPP, "the pipeline moves cf32 sub-slabs: not built for a handle with input_format = 1 (sc16)");
     const unsigned N = mcrx_hip_num_channels(rx);
     if (world < 1 || rank < 0 || rank >= world || N % (unsigned)world) return pfail(MCRX_EINVAL, "ranks must divide the channel count");
     if (sub_blocks == 0 || sub_blocks % MCRX_TILE) return pfail(MCRX_EINVAL, "sub-slabs are whole tiles of MCRX_TILE = 16 blocks");
