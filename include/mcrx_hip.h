@@ -356,15 +356,33 @@ const char *mcrx_hip_pipeline_last_error(void);
  * Replaces multichanneltx (lib/multichanneltx.cc:41-242: N x ofdmflexframegen -> 2N-channel
  * synthesis bank, m = 13 -> NCO mix-up) driven by the traffic loop of src/multichannel_tx.cc:
  * 163-213: frames back to back on every channel, header = [pid_hi, pid_lo, channel, 5 seeded
- * bytes], seeded payloads, soft gain.  The stream is written to device memory. */
+ * bytes], seeded payloads, soft gain.  The stream is written to device memory, as cf32 or as sc16
+ * (mctx_hip_set_output_format). */
 typedef struct mctx_hip_s *mctx_hip_t;
 int    mctx_hip_create(mctx_hip_t *out, unsigned num_channels, unsigned M, unsigned cp_len,
                        unsigned taper_len, const unsigned char *p);
 int    mctx_hip_destroy(mctx_hip_t q);
+/* Output format of the wideband stream: 0 = cf32 (the default), 1 = sc16 -- 16-bit integer IQ, interleaved int16 re, im, 4 bytes a
+ * sample in the same block order, which is the receiver's input_format = 1 as it stands (a sample means (re, im) * 2^-15; no scale
+ * factor between the two).  Let v be the fp32 value a cf32 handle stores for one component, behind the oscillator and `gain`: an sc16
+ * handle stores Q(v) = clamp(r, -32768, 32767), r = rint(v * 32768.0f) -- round half to even, in fp32, the multiply exact -- so the
+ * integers are a function of the cf32 output alone.  NaN stores 0, infinities saturate.  `gain` therefore sets the level against the
+ * full scale 1.0; a SAMPLE is clipped when r lies outside the range for its re or its im (NaN does not count).
+ * On an sc16 handle mctx_hip_generate, _generate_ragged and _synthesize_tiles write nblocks * 2N samples of 4 bytes to d_iq (8-byte
+ * aligned, else MCRX_EINVAL); everything else about them is unchanged.  The host paths that produce a block or a frame at a time --
+ * mctx_hip_stream_begin / _update / _generate and mctx_hip_frame -- have no gain to put the full scale against and return
+ * MCRX_EUNSUPP there.  Any other format value: MCRX_EINVAL, as is a null handle; MCRX_EBUSY once mctx_hip_stream_begin has run. */
+int      mctx_hip_set_output_format(mctx_hip_t q, unsigned format);
+unsigned mctx_hip_output_format(mctx_hip_t q);                                      /* 0 for a null handle */
+/* Clipped samples of every sample-producing call on this handle since the last reset (reset = 1 starts a new count).  Waits for
+ * those calls first (an event recorded on the caller's stream behind each).  Always 0 on a cf32 handle; samples may be NULL. */
+int      mctx_hip_clipped(mctx_hip_t q, uint64_t *samples, int reset);
+/* the quantiser Q of the kernels on n host floats (one component each): tests reach rounding ties and the saturation edges with it */
+int      mctx_hip_selftest_quantise(const float *in, int16_t *out, size_t n);
 /* blocks of 2N samples needed for `frames_per_channel` frames plus the filter tail (multiple of MCRX_TILE) */
 size_t mctx_hip_blocks_for(mctx_hip_t q, unsigned frames_per_channel, unsigned payload_len,
                            int mod, int fec0, int fec1);
-/* writes nblocks*2N cf32 samples to d_iq; the headers / payloads that were sent are returned in
+/* writes nblocks*2N samples to d_iq in the handle's output format (cf32: 8 bytes each, sc16: 4); the headers / payloads that were sent are returned in
  * hdr[ch][frame][8] and pay[ch][frame][payload_len] (host buffers, may be NULL) */
 int    mctx_hip_generate(mctx_hip_t q, void *d_iq, size_t nblocks, unsigned frames_per_channel,
                          unsigned payload_len, int mod, int fec0, int fec1, float gain, uint32_t seed,

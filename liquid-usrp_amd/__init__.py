@@ -50,6 +50,7 @@ class Config(C.Structure):
 
 
 INPUT_FORMATS = {"cf32": 0, "sc16": 1}      # mcrx_hip_config::input_format
+OUTPUT_FORMATS = {"cf32": 0, "sc16": 1}     # mctx_hip_set_output_format
 
 
 class FrameC(C.Structure):
@@ -130,6 +131,10 @@ _EXPORTS = {
     "mcrx_hip_pipeline_last_error": (C.c_char_p, []),
     "mctx_hip_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]),
     "mctx_hip_destroy": (C.c_int, [C.c_void_p]),
+    "mctx_hip_set_output_format": (C.c_int, [C.c_void_p, C.c_uint]),
+    "mctx_hip_output_format": (C.c_uint, [C.c_void_p]),
+    "mctx_hip_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
+    "mctx_hip_selftest_quantise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mctx_hip_blocks_for": (C.c_size_t, [C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_int]),
     "mctx_hip_generate_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                                            C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -696,10 +701,22 @@ class multichanneltx(object):
     (reference: lib/multichanneltx.cc + the traffic loop of src/multichannel_tx.cc:163-213).
 
     generate(frames_per_channel, payload_len, ...) -> (iq, sent): iq is a torch complex64 CUDA
-    tensor with the wideband stream, sent[ch] = [(header, payload), ...]."""
+    tensor with the wideband stream, sent[ch] = [(header, payload), ...].
 
-    def __init__(self, num_channels, M, cp_len, taper_len, p=None, max_payload_len=2048):
+    output_format="sc16" (or 1) makes a transmitter of 16-bit integer IQ: generate, generate_ragged and synthesize then return (or
+    take as `out`) a contiguous torch int16 CUDA tensor of shape (samples, 2) -- re, im of clamp(rint(v * 32768)), v the cf32
+    transmitter's value, so `gain` sets the level against the full scale 1.0 -- which multichannelrx(..., input_format="sc16").Execute
+    takes as it stands.  clipped() counts the samples that hit the range.  The host paths (GenerateSamples, UpdateData, frame) are
+    cf32 only and raise McrxError there."""
+
+    def __init__(self, num_channels, M, cp_len, taper_len, p=None, max_payload_len=2048, output_format="cf32"):
         self._h = C.c_void_p()
+        if isinstance(output_format, str):
+            if output_format not in OUTPUT_FORMATS:
+                raise ValueError("output_format must be one of %s" % sorted(OUTPUT_FORMATS))
+            output_format = OUTPUT_FORMATS[output_format]
+        elif output_format not in OUTPUT_FORMATS.values():
+            raise ValueError("output_format must be one of %s or %s" % (sorted(OUTPUT_FORMATS), sorted(OUTPUT_FORMATS.values())))
         self.N, self.K, self.M, self.cp = num_channels, 2 * num_channels, M, cp_len
         self.max_payload_len, self._stream_max = max_payload_len, -1
         parr = None if p is None else np.ascontiguousarray(np.frombuffer(bytes(bytearray(p)), np.uint8))
@@ -711,9 +728,30 @@ class multichanneltx(object):
             if rc == MCRX_EINVAL:
                 raise ValueError(msg)
             raise McrxError("mctx_hip_create failed (%d): %s" % (rc, msg))
+        if output_format:
+            self._chk(lib().mctx_hip_set_output_format(self._h, int(output_format)), "mctx_hip_set_output_format")
 
     def GetNumChannels(self):
         return self.N
+
+    @property
+    def output_format(self):
+        """0 (cf32) or 1 (sc16): OUTPUT_FORMATS"""
+        return int(lib().mctx_hip_output_format(self._h))
+
+    def clipped(self, reset=False):
+        """Samples whose re or im hit the int16 range, over every generate / generate_ragged / synthesize since the last reset (waits
+        for them); always 0 on a cf32 transmitter."""
+        n = C.c_uint64(0)
+        self._chk(lib().mctx_hip_clipped(self._h, C.byref(n), 1 if reset else 0), "mctx_hip_clipped")
+        return int(n.value)
+
+    def _slab(self, nsamples, device):
+        """an output buffer of nsamples wideband samples in the transmitter's format"""
+        import torch
+        if self.output_format == OUTPUT_FORMATS["sc16"]:
+            return torch.empty((nsamples, 2), dtype=torch.int16, device=device)
+        return torch.empty(nsamples, dtype=torch.complex64, device=device)
 
     def generate(self, frames_per_channel, payload_len, mod=LIQUID_MODEM_QPSK, fec0=LIQUID_FEC_NONE,
                  fec1=LIQUID_FEC_HAMMING128, gain=None, seed=0xC0FFEE, nblocks=None, device=None):
@@ -721,7 +759,7 @@ class multichanneltx(object):
         nb = int(lib().mctx_hip_blocks_for(self._h, frames_per_channel, payload_len, mod, fec0, fec1))
         if nblocks is not None:
             nb = max(nb, (int(nblocks) + TILE - 1) // TILE * TILE)
-        iq = torch.empty(nb * self.K, dtype=torch.complex64, device=device or "cuda")
+        iq = self._slab(nb * self.K, device or "cuda")
         hdr = np.zeros((self.N, frames_per_channel, 8), np.uint8)
         pay = np.zeros((self.N, frames_per_channel, max(payload_len, 1)), np.uint8)
         g = (1.0 / self.N) if gain is None else gain
@@ -744,7 +782,7 @@ class multichanneltx(object):
         L = self.M + self.cp
         shortest = int(lib().mctx_hip_blocks_for(self._h, 1, len_lo, mod, fec0, fec1)) - 64
         maxf = nb // max(shortest, L) + 2
-        iq = torch.empty(nb * self.K, dtype=torch.complex64, device=device or "cuda")
+        iq = self._slab(nb * self.K, device or "cuda")
         cnt = np.zeros(self.N, np.uint32); hdr = np.zeros((self.N, maxf, 8), np.uint8); ln = np.zeros((self.N, maxf), np.uint32)
         pay = np.zeros((self.N, maxf, max(len_hi, 1)), np.uint8); start = np.zeros((self.N, maxf), np.uint64)
         g = (1.0 / self.N) if gain is None else gain
@@ -766,11 +804,17 @@ class multichanneltx(object):
 
     def synthesize(self, tiles, groups, first_block, nblocks, lead_blocks, keep_blocks=0, gain=None, out=None, stream=None):
         """Wideband samples of blocks [first_block-keep, first_block+nblocks) from exchanged channel-rate granules
-        tiles[groups][(lead+nblocks)/8][N/groups][8] (mctx_hip_synthesize_tiles)."""
+        tiles[groups][(lead+nblocks)/8][N/groups][8] (mctx_hip_synthesize_tiles).  `out`: complex64, or on an sc16 transmitter
+        a contiguous int16 tensor of (re, im) pairs; TypeError on the wrong dtype for the format."""
         import torch
+        sc16 = self.output_format == OUTPUT_FORMATS["sc16"]
         if out is None:
-            out = torch.empty((keep_blocks + nblocks) * self.K, dtype=torch.complex64, device=tiles.device)
-        assert tiles.numel() >= (lead_blocks + nblocks) * self.N and out.numel() >= (keep_blocks + nblocks) * self.K
+            out = self._slab((keep_blocks + nblocks) * self.K, tiles.device)
+        elif out.dtype != (torch.int16 if sc16 else torch.complex64):
+            raise TypeError("this transmitter writes %s, not %s" % ("int16 (re, im) pairs" if sc16 else "complex64", out.dtype))
+        elif sc16 and not out.is_contiguous():
+            raise ValueError("device samples must be contiguous")
+        assert tiles.numel() >= (lead_blocks + nblocks) * self.N and out.numel() >= (keep_blocks + nblocks) * self.K * (2 if sc16 else 1)
         g = (1.0 / self.N) if gain is None else gain
         st = stream if stream is not None else torch.cuda.current_stream(tiles.device)
         self._chk(lib().mctx_hip_synthesize_tiles(self._h, _dptr(tiles), groups, first_block, nblocks, lead_blocks, keep_blocks,

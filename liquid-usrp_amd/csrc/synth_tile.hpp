@@ -7,7 +7,7 @@
 //   X_b[k]  = channel k's sample of block b (k < N; bins N..K-1 are zero)        4 B read per wideband sample
 //   v_b     = K-point inverse FFT of X_b, unnormalised                           LDS tile, radix-4 + 16-point register stage
 //   y_b[n]  = sum_{j<26} h[n + jK] v_{b-j}[n]                                    register window down the time axis
-//   out     = gain * y_b[n] * exp(+j t dtheta), t = absolute sample index        8 B written per wideband sample
+//   out     = gain * y_b[n] * exp(+j t dtheta), t = absolute sample index        8 B written per wideband sample (sc16: 4 B)
 // Round 2 ran this as two kernels with the inverse-FFT outputs in HBM between them (one workgroup per block, radix-2 Stockham
 // with a sincos per butterfly; 28 B per sample, 7.5 + 5.0 GB of measured traffic per 207 M samples): 2.68 ms.  Here a workgroup owns
 // a time slab; a thread owns two adjacent columns and keeps their last 25 inverse-FFT outputs in registers (the analysis bank's
@@ -120,7 +120,9 @@ __host__ __device__ inline bool syn_aligned(const TxSynthArgs &a)
 {
     return !a.tiles && !a.ft0 && (a.L % 8) == 0 && (a.cp % 8) == 0 && (a.M % 8) == 0 && a.taper >= 0 && a.taper <= 4;
 }
-template <int K, int R, int IN>
+// FMT: what is stored -- TX_CF32 one float4 of two samples per lane and block, TX_SC16 the same two samples through sc16_sample
+// (sc16_out.hpp) as one 8-byte store, the clipped ones counted in a register and committed once per wave behind the last round
+template <int K, int R, int IN, int FMT = TX_CF32>
 __global__ __launch_bounds__(K / 2) void synth_kernel(TxSynthArgs a, uint32_t slab_blocks)
 {
     constexpr int T = K / 2, N = K / 2, C = 2;
@@ -179,7 +181,9 @@ __global__ __launch_bounds__(K / 2) void synth_kernel(TxSynthArgs a, uint32_t sl
 #pragma unroll
         for (int c = 0; c < C; c++) s[i][c] = make_float2(0.f, 0.f);
     char *outb = reinterpret_cast<char *>(a.out);
-    const uint32_t ooff = (uint32_t)n0 * (uint32_t)sizeof(float2);
+    constexpr size_t OSZ = FMT == TX_SC16 ? sizeof(uint32_t) : sizeof(float2);      // bytes of a stored sample
+    const uint32_t ooff = (uint32_t)n0 * (uint32_t)OSZ;
+    uint32_t nclip = 0;                                             // (sc16) clipped samples of this lane
     // Oscillator e^{+j t dtheta}: exact 32-bit phase through v_sin / v_cos at the first column of every group of 8 blocks
     // (groups start on multiples of 8 of the launch's block axis, which callers keep aligned with the absolute one), then
     // turned by the per-block step K dtheta and, for the second column, by dtheta -- explicit fma shapes, so a block's
@@ -526,6 +530,10 @@ __global__ __launch_bounds__(K / 2) void synth_kernel(TxSynthArgs a, uint32_t sl
                     const float s1 = fmaf(osn, cd1, ocs * sd1), c1 = fmaf(ocs, cd1, -(osn * sd1));            // the second column
                     const float2 y0 = make_float2(fmaf(acc[r][0].x, ocs, -(acc[r][0].y * osn)), fmaf(acc[r][0].y, ocs, acc[r][0].x * osn));
                     const float2 y1 = make_float2(fmaf(acc[r][1].x, c1, -(acc[r][1].y * s1)), fmaf(acc[r][1].y, c1, acc[r][1].x * s1));
+                    if constexpr (FMT == TX_SC16) {
+                        *reinterpret_cast<uint2 *>(uniform_ptr(outb + (size_t)(b - (long long)a.out_first) * K * OSZ) + ooff) =
+                            make_uint2(sc16_sample(y0.x * a.gain, y0.y * a.gain, nclip), sc16_sample(y1.x * a.gain, y1.y * a.gain, nclip));
+                    } else {
 #if SYN_NT_STORE
                     { typedef float v4f __attribute__((ext_vector_type(4)));
                       const v4f nv = { y0.x * a.gain, y0.y * a.gain, y1.x * a.gain, y1.y * a.gain };
@@ -534,6 +542,7 @@ __global__ __launch_bounds__(K / 2) void synth_kernel(TxSynthArgs a, uint32_t sl
                     *reinterpret_cast<float4 *>(uniform_ptr(outb + (size_t)(b - (long long)a.out_first) * K * sizeof(float2)) + ooff) =
                         make_float4(y0.x * a.gain, y0.y * a.gain, y1.x * a.gain, y1.y * a.gain);
 #endif
+                    }
                 }
                 { const float s2 = fmaf(osn, ck8, ocs * sk8), c2 = fmaf(ocs, ck8, -(osn * sk8)); osn = s2; ocs = c2; }      // next block
             }
@@ -557,6 +566,7 @@ __global__ __launch_bounds__(K / 2) void synth_kernel(TxSynthArgs a, uint32_t sl
         }
         lds_barrier();
     }
+    if constexpr (FMT == TX_SC16) sc16_clip_commit(a.clip, nclip);
 }
 
 }  // namespace syn

@@ -19,6 +19,7 @@
 #include "devmath.h"
 #include "txcode.hpp"
 #include "devscope.hpp"
+#include "sc16_out.hpp"
 #include <random>
 #include <string>
 #include <vector>
@@ -360,6 +361,8 @@ struct TxSynthArgs {
     uint32_t out_first = 0;       // blocks in front of this one only feed the filter: out holds blocks >= out_first
     // ragged traffic: symkind[ch][S] (TXK_*), frames = 1, S = symbols of the whole axis
     const uint8_t *symkind = nullptr;
+    // sc16 output (sc16_out.hpp): `out` then holds 4-byte samples, and the clipped ones are added to *clip
+    unsigned long long *clip = nullptr;
 };
 
 __device__ __forceinline__ float2 frame_sample_sym(const TxSynthArgs &a, uint32_t ch, const float2 *xb, int S, uint32_t nsym, uint32_t gs, uint32_t i);
@@ -475,10 +478,13 @@ __global__ void txframe_kernel(TxSynthArgs a, uint32_t nsamples)
 }
 
 // synthesis FIR down the time axis + NCO mix-up + gain; a thread owns one column for 8 blocks
-__global__ void txfir_kernel(TxSynthArgs a, uint32_t K)
+// The output format is a run-time choice here (a.clip != NULL: sc16), not a build of its own: the compiler contracts the FIR sums and
+// the oscillator product differently from one instantiation to the next (a build that ended in the 4-byte store fused every
+// multiply-add of the window, the cf32 build less than a fifth of them: 24 of 59904 samples one step apart at N = 8), and Q is a function
+// of the cf32 value only if that value is the same one.  One body computes it; the formats part at the store.  The lanes past column
+// K - 1 idle to the end, where the whole wave commits its clip count.
+__device__ __forceinline__ void txfir_column(const TxSynthArgs &a, const uint32_t K, const uint32_t i, uint32_t &nclip)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= K) return;
     const long long b0 = (long long)blockIdx.y * 8;
     float h[TX_P];
 #pragma unroll
@@ -502,8 +508,17 @@ __global__ void txfir_kernel(TxSynthArgs a, uint32_t K)
         }
         const uint32_t t = a.first_sample_lo + (uint32_t)((unsigned long long)b * K + i);
         float2 y = mix_up(acc, t * a.dtheta);
-        a.out[(size_t)(b - (long long)a.out_first) * K + i] = make_float2(y.x * a.gain, y.y * a.gain);
+        const float2 o = make_float2(y.x * a.gain, y.y * a.gain);
+        if (a.clip) reinterpret_cast<uint32_t *>(a.out)[(size_t)(b - (long long)a.out_first) * K + i] = sc16_sample(o.x, o.y, nclip);
+        else a.out[(size_t)(b - (long long)a.out_first) * K + i] = o;
     }
+}
+__global__ void txfir_kernel(TxSynthArgs a, uint32_t K)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t nclip = 0;
+    if (i < K) txfir_column(a, K, i, nclip);
+    if (a.clip) sc16_clip_commit(a.clip, nclip);
 }
 
 // channel-rate samples of a channel shard for blocks [first_block, first_block + 8 ntiles) as granules
@@ -567,6 +582,8 @@ __global__ void txtiles_kernel(TxSynthArgs a, long long first_block, uint32_t nt
 using namespace mcrx;
 
 static thread_local std::string g_tx_err;
+// the host paths that produce a block or a frame at a time have no gain to put the full scale against: they stay cf32
+#define TX_SC16_UNSUPP "sc16 output covers mctx_hip_generate, _generate_ragged and _synthesize_tiles; the streaming interface and mctx_hip_frame are cf32 only"
 #define TXCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_tx_err = std::string(#x) + ": " + hipGetErrorString(e_); return MCRX_EHIP; } } while (0)
 
 struct mctx_hip_s {
@@ -592,6 +609,11 @@ struct mctx_hip_s {
     long long period = 0, blocks_out = 0; unsigned out_pos = 0;
     hipStream_t sst = nullptr;
     float2 *d_synv = nullptr; size_t syn_cap = 0;       // sharded synthesis: inverse-FFT outputs of one slab (+ lead)
+    // ---- output format (mctx_hip_set_output_format): TX_CF32, or TX_SC16 with its count of clipped samples
+    unsigned out_fmt = TX_CF32;
+    unsigned long long *d_clip = nullptr;               // clipped samples since the handle was made (device, 64 bits)
+    unsigned long long clip_base = 0;                   // ... of them, already reported and reset (mctx_hip_clipped)
+    hipEvent_t clip_ev = nullptr; bool clip_pending = false;    // recorded behind the last sample-producing launch
     template <class T> int up(const T **dst, const T *src, size_t n)
     {
         T *p = nullptr;
@@ -654,6 +676,8 @@ extern "C" int mctx_hip_destroy(mctx_hip_t q)
     for (void *p : { (void *)q->d_shdr, (void *)q->d_spay, (void *)q->d_sxsym, (void *)q->d_ft0, (void *)q->d_fS,
                      (void *)q->d_sv[0], (void *)q->d_sv[1], (void *)q->d_sout, (void *)q->d_synv }) if (p) (void)hipFree(p);
     if (q->h_sout) (void)hipHostFree(q->h_sout);
+    if (q->d_clip) (void)hipFree(q->d_clip);
+    if (q->clip_ev) (void)hipEventDestroy(q->clip_ev);
     if (q->sst) (void)hipStreamDestroy(q->sst);
     delete q;
     return MCRX_OK;
@@ -1016,12 +1040,12 @@ static bool tx_fused_ok(mctx_hip_t q, const TxSynthArgs &ya)
     return env != 0 && q->taps_symmetric && !ya.ft0 && ya.hist == 0 && (q->K == 128 || q->K == 256 || q->K == 512 || q->K == 1024) &&
            (ya.out_first % 8) == 0;
 }
-template <int KK, int R, int IN>
-static int tx_launch_fused_in(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t st)
+template <int KK, int R, int IN, int FMT>
+static int tx_launch_fused_fmt(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t st)
 {
     const size_t lds = syn::Lds<KK, R>::bytes();
     static PerDeviceOnce attr;               // (per instantiation and device: devscope.hpp)
-    TXCHK(raise_lds_limit((const void *)syn::synth_kernel<KK, R, IN>, lds, attr));
+    TXCHK(raise_lds_limit((const void *)syn::synth_kernel<KK, R, IN, FMT>, lds, attr));
     const size_t nout = ya.nblocks - ya.out_first;
     // slab per workgroup: a whole number of workgroup waves over the CUs, at most 512 blocks (28 blocks of lead-in each)
     const size_t cap = (size_t)q->ncu * (KK >= 1024 ? 1 : 2);
@@ -1029,9 +1053,18 @@ static int tx_launch_fused_in(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t s
     size_t slab = ((nout + cap * k - 1) / (cap * k) + 7) & ~(size_t)7;
     if (slab < 256) slab = 256;                     // (28 blocks of lead-in per slab)
     const unsigned grid = (unsigned)((nout + slab - 1) / slab);
-    hipLaunchKernelGGL((syn::synth_kernel<KK, R, IN>), dim3(grid), dim3(KK / 2), lds, st, ya, (uint32_t)slab);
+    hipLaunchKernelGGL((syn::synth_kernel<KK, R, IN, FMT>), dim3(grid), dim3(KK / 2), lds, st, ya, (uint32_t)slab);
     TXCHK(hipGetLastError());
     return MCRX_OK;
+}
+// the output format is a compile-time choice of the store phase, like the input side
+template <int KK, int R, int IN>
+static int tx_launch_fused_in(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t st)
+{
+    if constexpr (KK < 512 || R == 8) {     // (sc16 has no rounds of 4 at K >= 512 -- a development switch of the cf32 kernels: tx_synthesize_fmt)
+        if (ya.clip) return tx_launch_fused_fmt<KK, R, IN, TX_SC16>(q, ya, st);
+    }
+    return tx_launch_fused_fmt<KK, R, IN, TX_CF32>(q, ya, st);
 }
 // the input side of the kernel is a compile-time choice (three loaders in one body spilled the window): exchanged granules,
 // the aligned symbol loader (rounds of 8 blocks only), or the block-by-block walk
@@ -1045,22 +1078,94 @@ static int tx_launch_fused(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t st)
     }
     return tx_launch_fused_in<KK, R, syn::SYN_WALK>(q, ya, st);
 }
-static int tx_synthesize(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t st)
+static int tx_synthesize_fmt(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t st)
 {
     if (tx_fused_ok(q, ya)) {
         switch (q->K) {
         case 128: return tx_launch_fused<128, 4>(q, ya, st);
         case 256: return tx_launch_fused<256, 4>(q, ya, st);
-        case 512: { static const int r8 = devel_env("MCTX_R8") ? atoi(devel_env("MCTX_R8")) : 1; return r8 ? tx_launch_fused<512, 8>(q, ya, st) : tx_launch_fused<512, 4>(q, ya, st); }
-        default:  { static const int r8 = devel_env("MCTX_R8") ? atoi(devel_env("MCTX_R8")) : 1; return r8 ? tx_launch_fused<1024, 8>(q, ya, st) : tx_launch_fused<1024, 4>(q, ya, st); }
+        case 512: { static const int r8 = devel_env("MCTX_R8") ? atoi(devel_env("MCTX_R8")) : 1; return (r8 || ya.clip) ? tx_launch_fused<512, 8>(q, ya, st) : tx_launch_fused<512, 4>(q, ya, st); }
+        default:  { static const int r8 = devel_env("MCTX_R8") ? atoi(devel_env("MCTX_R8")) : 1; return (r8 || ya.clip) ? tx_launch_fused<1024, 8>(q, ya, st) : tx_launch_fused<1024, 4>(q, ya, st); }
         }
     }
     if (!ya.v) { g_tx_err = "two-kernel synthesis needs its inverse-FFT buffer"; return MCRX_EINVAL; }
     { int rc = tx_launch_ifft(q, ya, ya.nblocks, st); if (rc) return rc; }
     const unsigned K = q->K, tb = K < 256 ? 64 : 256;
-    hipLaunchKernelGGL(txfir_kernel, dim3((K + tb - 1) / tb, (unsigned)((ya.nblocks + 7) / 8)), dim3(tb), 0, st, ya, K);
+    const dim3 grid((K + tb - 1) / tb, (unsigned)((ya.nblocks + 7) / 8));
+    hipLaunchKernelGGL(txfir_kernel, grid, dim3(tb), 0, st, ya, K);
     TXCHK(hipGetLastError());
     return MCRX_OK;
+}
+// ... in the handle's output format.  An sc16 handle's kernels add to its clip counter, and an event behind them on the caller's
+// stream is what mctx_hip_clipped waits for.
+static int tx_synthesize(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t st)
+{
+    if (q->out_fmt != TX_SC16) return tx_synthesize_fmt(q, ya, st);
+    if (reinterpret_cast<uintptr_t>(ya.out) & 7u) { g_tx_err = "sc16 output must be 8-byte aligned"; return MCRX_EINVAL; }
+    TxSynthArgs yi = ya;
+    yi.clip = q->d_clip;
+    { int rc = tx_synthesize_fmt(q, yi, st); if (rc) return rc; }
+    TXCHK(hipEventRecord(q->clip_ev, st));
+    q->clip_pending = true;
+    return MCRX_OK;
+}
+
+extern "C" int mctx_hip_set_output_format(mctx_hip_t q, unsigned format)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_tx_err = "null handle"; return MCRX_EINVAL; }
+    if (format != TX_CF32 && format != TX_SC16) { g_tx_err = "output format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
+    if (q->st_on) { g_tx_err = "the output format cannot change once the streaming interface has started"; return MCRX_EBUSY; }
+    if (format == TX_SC16 && !q->d_clip) {
+        TXCHK(hipMalloc((void **)&q->d_clip, sizeof(unsigned long long)));
+        TXCHK(hipMemset(q->d_clip, 0, sizeof(unsigned long long)));
+        TXCHK(hipDeviceSynchronize());
+        TXCHK(hipEventCreateWithFlags(&q->clip_ev, hipEventDisableTiming));
+    }
+    q->out_fmt = format;
+    return MCRX_OK;
+}
+
+extern "C" unsigned mctx_hip_output_format(mctx_hip_t q) { return q ? q->out_fmt : 0u; }
+
+extern "C" int mctx_hip_clipped(mctx_hip_t q, uint64_t *samples, int reset)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_tx_err = "null handle"; return MCRX_EINVAL; }
+    uint64_t n = 0;
+    if (q->out_fmt == TX_SC16) {
+        if (q->clip_pending) { TXCHK(hipEventSynchronize(q->clip_ev)); q->clip_pending = false; }
+        unsigned long long seen = 0;
+        TXCHK(hipMemcpy(&seen, q->d_clip, sizeof(seen), hipMemcpyDeviceToHost));
+        n = seen - q->clip_base;
+        if (reset) q->clip_base = seen;
+    }
+    if (samples) *samples = n;
+    return MCRX_OK;
+}
+
+// the shared quantiser on n host floats (tests reach rounding ties and the saturation edges through it)
+__global__ void sc16_selftest_kernel(const float *in, int16_t *out, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t nclip = 0;
+    out[i] = (int16_t)(mcrx::sc16_sample(in[i], 0.0f, nclip) & 0xffffu);
+}
+extern "C" int mctx_hip_selftest_quantise(const float *in, int16_t *out, size_t n)
+{
+    if ((!in || !out) && n) { g_tx_err = "bad argument"; return MCRX_EINVAL; }
+    if (!n) return MCRX_OK;
+    float *d_in = nullptr; int16_t *d_out = nullptr;
+    auto done = [&](int rc) { (void)hipFree(d_in); (void)hipFree(d_out); return rc; };
+#define TXQ(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_tx_err = std::string(#x) + ": " + hipGetErrorString(e_); return done(MCRX_EHIP); } } while (0)
+    TXQ(hipMalloc((void **)&d_in, n * sizeof(float))); TXQ(hipMalloc((void **)&d_out, n * sizeof(int16_t)));
+    TXQ(hipMemcpy(d_in, in, n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(sc16_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d_in, d_out, n);
+    TXQ(hipGetLastError());
+    TXQ(hipMemcpy(out, d_out, n * sizeof(int16_t), hipMemcpyDeviceToHost));
+#undef TXQ
+    return done(MCRX_OK);
 }
 
 // (re)size the per-channel frame slots to hold Sp payload symbols; frames in flight are carried over
@@ -1085,6 +1190,7 @@ extern "C" int mctx_hip_stream_begin(mctx_hip_t q, unsigned max_payload_len)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_tx_err = "null handle"; return MCRX_EINVAL; }
+    if (q->out_fmt == TX_SC16) { g_tx_err = TX_SC16_UNSUPP; return MCRX_EUNSUPP; }
     const unsigned N = q->N, M = q->M, K = q->K, L = M + q->cp, Md = q->od.M_data;
     // slots for the longest frame a payload of this size can make: BPSK behind two rate-1/2 codes
     unsigned Sh, Sp, S; frame_geometry(q, max_payload_len, 39, 7, 7, Sh, Sp, S);
@@ -1134,6 +1240,7 @@ extern "C" int mctx_hip_stream_update(mctx_hip_t q, unsigned ch, const uint8_t *
                                       int mod, int fec0, int fec1)
 {
     DevScope dev_scope_(q ? q->device : -1);
+    if (q && q->out_fmt == TX_SC16) { g_tx_err = TX_SC16_UNSUPP; return MCRX_EUNSUPP; }
     if (!q || !q->st_on || !header8 || (!payload && payload_len)) { g_tx_err = "bad argument"; return MCRX_EINVAL; }
     if (ch >= q->N) { g_tx_err = "error: multichanneltx::UpdateData(), invalid channel id"; return MCRX_EINVAL; }
     if (!mod_bps(mod)) { g_tx_err = "unsupported modulation scheme"; return MCRX_EUNSUPP; }
@@ -1197,6 +1304,7 @@ static int tx_stream_period(mctx_hip_t q)
 extern "C" int mctx_hip_stream_generate(mctx_hip_t q, float *out)
 {
     DevScope dev_scope_(q ? q->device : -1);
+    if (q && q->out_fmt == TX_SC16) { g_tx_err = TX_SC16_UNSUPP; return MCRX_EUNSUPP; }
     if (!q || !q->st_on || !out) { g_tx_err = "bad argument"; return MCRX_EINVAL; }
     const unsigned L = q->M + q->cp;
     if (q->out_pos >= L) { int rc = tx_stream_period(q); if (rc) return rc; }
@@ -1221,6 +1329,7 @@ extern "C" int mctx_hip_frame(mctx_hip_t q, const uint8_t *header8, const uint8_
                               int mod, int fec0, int fec1, float gain, float *out, size_t out_cap)
 {
     DevScope dev_scope_(q ? q->device : -1);
+    if (q && q->out_fmt == TX_SC16) { g_tx_err = TX_SC16_UNSUPP; return MCRX_EUNSUPP; }
     if (!q || !header8 || (!payload && payload_len) || !out) { g_tx_err = "bad argument"; return MCRX_EINVAL; }
     if (!mod_bps(mod)) { g_tx_err = "unsupported modulation scheme"; return MCRX_EUNSUPP; }
     if (!fec_supported(fec0) || !fec_supported(fec1)) { g_tx_err = "unsupported fec scheme"; return MCRX_EUNSUPP; }

@@ -234,7 +234,12 @@ class TxPipeline(object):
         self.cuda = device is not None and torch.device(device).type == "cuda"
         self.out = [torch.zeros(world * self.per, dtype=torch.complex64, device=device) for _ in range(nbuf)]
         self.recv = [torch.zeros(world * self.per, dtype=torch.complex64, device=device) for _ in range(nbuf)]
-        self.iq = [torch.zeros((keep_blocks + sub_blocks) * self.K, dtype=torch.complex64, device=device) for _ in range(nbuf)]
+        # (the wideband slabs in the transmitter's output format; the exchange buffers above hold channel-rate granules: complex64)
+        nsamp = (keep_blocks + sub_blocks) * self.K
+        if getattr(tx, "output_format", 0) == 1:                # an sc16 transmitter: int16 (re, im) pairs
+            self.iq = [torch.zeros((nsamp, 2), dtype=torch.int16, device=device) for _ in range(nbuf)]
+        else:
+            self.iq = [torch.zeros(nsamp, dtype=torch.complex64, device=device) for _ in range(nbuf)]
         self.rounds = 0
         self.alias = world == 1 and self.cuda                   # one rank: the granules are made where the synthesis reads them
         if self.alias:
