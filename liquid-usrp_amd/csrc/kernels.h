@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "acq_shared.h"        // MCRX_SPEC_MAX, MCRX_SEG_MAX, the hint block's words (HintWord): shared with the host-only planner
 
 namespace mcrx {
 
@@ -139,7 +140,6 @@ struct PayloadJob {
 // then the segment wave has executed exactly the events the scout would have, so the result is the sequential one; where no
 // slot matches (a timing that locked differently, an invalid header, an idle stretch) the scout walks on by itself --
 // slower, never different.  Nothing depends on the traffic having a cadence.
-#define MCRX_SPEC_MAX 256
 // A segment wave writes its hand-offs straight into the launch's job list -- synchronizer state, equaliser, everything a payload
 // worker needs -- but with the owner field void (PayloadJob::ch = ~0: workers, placement and decoder skip such entries, as they skip
 // a reservation that came to nothing); the scout makes a frame real by storing the channel number there.  Nothing is copied.
@@ -201,13 +201,12 @@ struct SyncArgs {
     uint32_t *live, *live_next;
     uint32_t frames_hint;       // ~0: unknown
     uint32_t live_off;          // lean workers: the main launch's grid (payload_lean.hpp, REST)
-    uint32_t *list_hint;        // [0] QAM hand-offs, [1] unused, [2] frames on the general list, of the most recent launch
+    uint32_t *list_hint;        // [0] QAM hand-offs, [1] unused, [2] frames on the general list, of the most recent launch (the hint block from HINT_LIST_BASE on: acq_shared.h)
     uint32_t grid_hint[3];      // what the host last read there (~0: no hint, full grids)
     uint32_t payload_lds_pad;  // bytes of unused dynamic LDS per payload worker: caps the workers' occupancy (walk mode, launch_sync)
     int seek_burst;            // idle stretches: SEEK events four at a time, their windows requested together (Walker::seek_burst)
     // speculation (see SpecSlot)
     SpecSlot *spec; float2 *spec_R;      // [nch][spec_stride]; [nch][MCRX_SEG_MAX][M]: a segment wave's equaliser between the S1 fit and the hand-off
-#define MCRX_SEG_MAX 128
     int64_t *pred; uint32_t *pred_n;     // predicted fresh-state positions for the next launch: [nch][MCRX_SPEC_MAX], [nch]
     uint32_t spec_cap;                   // slots per channel the segment waves fill in this launch = nseg * (slots per wave) (0: off)
     uint32_t spec_stride;                // slots between two channels in `spec` (>= spec_cap; MCRX_SPEC_MAX unless a push holds more frames per
@@ -235,8 +234,8 @@ struct SyncArgs {
                                          // frame is re-acquired from if the next push defers it (a frame detected at the end of one push and deferred
                                          // in the next used to go back to position 0 -- pushes shorter than a frame re-delivered the whole history)
     uint32_t *spec_hint;                 // host-mapped word: largest prediction count, sizes the next launch's grid
-    uint32_t *walk_hint;                 // host-mapped word: frames the scouts had to acquire themselves so far (the host adds a full-width round while it moves)
-    uint32_t *hint;             // host-mapped word: longest coded frame (bytes) among this launch's jobs
+    uint32_t *walk_hint;                 // host-mapped words (the hint block from HINT_WALK_BASE on: acq_shared.h): frames the scouts had to acquire themselves so far (the host adds a full-width round while it moves)
+    uint32_t *hint;             // the hint block (HintWord, acq_shared.h), host-mapped; [0]: longest coded frame (bytes) among this launch's jobs
     uint32_t enc_hint;          // the value the host last saw there (0: none yet)
     int round_idx;              // which acquisition round of the launch this is (a scout that stops in round >= 1 reports it: stats[6], the host
                                 // sizes the number of rounds by the last one that was needed)

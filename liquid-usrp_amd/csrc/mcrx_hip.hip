@@ -2,6 +2,8 @@
 // buffers, streaming glue between the channelizer and the synchronizer bank, frame
 // harvesting.  Host code only; the kernels live in channelizer.hip / ofdmsync.hip.
 #include "../../include/mcrx_hip.h"
+#include "acq_plan.hpp"
+#include "config_read.hpp"
 #include "design.hpp"
 #include "devel.h"
 #include "devmath.h"
@@ -160,7 +162,6 @@ struct mcrx_hip_s {
     FrameRec *d_rec[MCRX_GENS] = {}; uint8_t *d_arena[MCRX_GENS] = {}, *d_sarena[MCRX_GENS] = {};
     uint32_t *d_nrec[MCRX_GENS] = {}; unsigned long long *d_arena_used[MCRX_GENS] = {};
     int gen = 0; bool gen_used[MCRX_GENS] = {}, gen_closed[MCRX_GENS] = {}, gen_abandoned[MCRX_GENS] = {};
-    uint32_t list_seen[3] = { 0, 0, 0 }, list_age[3] = { 64, 64, 64 };      // launch_sync: grids of the list-driven launches
     uint32_t round_lds_pad = 0;      // the same cap outside walk mode (MCRX_PAYLOAD_LDS_PAD)
     uint32_t walk_lds_pad = 13312;   // walk mode: unused LDS per payload worker = at most three of them per SIMD, the fourth slot is the walking scouts' (95 -> 110 Gsample/s on ragged traffic)
     int payload_fr = 1, payload_lean = 1, payload_xb = 63;      // MCRX_PAYLOAD_FR / _LEAN / _XB: which build of the M = 64 payload workers (tests)
@@ -189,14 +190,13 @@ struct mcrx_hip_s {
     hipEvent_t ev_ready[MCRX_SLOTS] = {}, ev_scout[MCRX_SLOTS] = {}, ev_done[MCRX_SLOTS] = {}, ev_in = nullptr, ev_consumed = nullptr, ev_tmp[4] = {};
     int last_slot = -1; size_t last_ntiles = 0;     // where the synchronizer history (tail of the previous launch) sits
     uint32_t spec_stride = MCRX_SPEC_MAX;           // slots per channel in d_spec (grows when a push holds more frames per channel: launch_sync)
-    SpecSlot *d_spec = nullptr; float2 *d_spec_R = nullptr; int64_t *d_pred = nullptr, *d_anchor = nullptr, *d_seekst = nullptr; uint32_t *d_pred_n = nullptr;
+    SpecSlot *d_spec = nullptr; float2 *d_spec_R = nullptr; int64_t *d_anchor = nullptr, *d_seekst = nullptr;
     bool spec = false;
-    uint32_t *h_hint = nullptr, *d_hint = nullptr;     // pinned, device-mapped: longest coded frame of the last launch
+    uint32_t *h_hint = nullptr, *d_hint = nullptr;     // pinned, device-mapped: the hint block (acq_shared.h: HintWord)
     uint8_t *d_jsoft[MCRX_SLOTS] = {}, *d_jtmp[MCRX_SLOTS] = {};
     bool scout = true, scout_tables = true, il_tried = false;
-    int anchor_kind = 0; uint32_t anchor_retry = 0, anc_filled = 0, anc_adopted = 0;      // cadenced traffic: 0 / 1 = the lattice carried over from the previous push (absolute / from the push's beginning), 2 = an anchor phase (launch_sync)
-    uint32_t nseg_fixed = 0, seg_frames = 4; float frames_per_push = 0.f; uint64_t last_nsamp = 0;      // segment-parallel acquisition: launch_sync
-    bool cadenced = true; uint32_t cad_same = 0, cad_frames = 0; int cad_count = 0;                       // ... its anchor phase
+    bool acq_prio = true;                   // the acquisition stream is created with the highest priority (MCRX_NO_PRIO: not)
+    AcqPolicy acq;                          // what the acquisition schedule remembers from launch to launch (acq_plan.hpp)
     // scouts of the acquisition rounds: 1 = the lean scout's unbudgeted build (sync_walk_kernel: 256 + 40 registers, no spills), 0 = the
     // 168-register build (293 spilled) that round 2 made to fit beside four 80-register payload workers.  With eight 56-register
     // workers per SIMD neither fits beside them any more, and a scout that adopts 100 frames of a channel pays for every spill:
@@ -546,18 +546,44 @@ static int restart_async(mcrx_hip_t q, hipStream_t st, bool from_zero)
     q->pf_in_valid = 0; q->pf_steps = 0; q->pf_have_last = false;
     monitor_restart(q);
     RC(join_into(q, st));
-    // (both result generations: counters zeroed; the prediction lists only survive a Reset(), not a restart from zero)
+    // (both result generations: counters zeroed)
     for (int g = 0; g < MCRX_GENS; g++) {
         HIPCHK(sync_reset_launch(q->d_st, q->nch, q->chan_samples, g == 0 ? reinterpret_cast<float2 *>(q->d_hist[0]) : nullptr,
                                  g == 0 ? reinterpret_cast<float2 *>(q->d_hist[1]) : nullptr,
                                  hist_bytes(q) / sizeof(float2), q->d_nrec[g], q->d_arena_used[g],
-                                 (from_zero && g == 0) ? q->d_pred_n : nullptr, st));
+                                 nullptr, st));
         q->gen_used[g] = false; q->gen_closed[g] = false; q->gen_abandoned[g] = false;
     }
     if (q->d_seekst) HIPCHK(hipMemsetAsync(q->d_seekst, 0, (size_t)q->nch * 2 * sizeof(int64_t), st));     // (the synchronizers restart in SEEK: it is set before it is used)
     q->gen = 0;
     RC(fork_from(q, st));
     return MCRX_OK;
+}
+
+// The experiment switches of development builds (devel.h: constant nullptr in a release build), read once, behind the configuration's
+// fields and over them.  MCRX_DEBUG is the one variable a release build reads.
+static void read_devel_env(mcrx_hip_t q)
+{
+    q->debug = getenv("MCRX_DEBUG") ? atoi(getenv("MCRX_DEBUG")) : 0;
+    if (devel_env("MCRX_SERIAL")) q->pipelined = false;
+    q->scout = devel_env("MCRX_NO_SCOUT") == nullptr;
+    if (!q->scout || devel_env("MCRX_NO_SPEC")) q->spec = false;        // (speculation hands off through the scouts' job list)
+    if (devel_env("MCRX_NO_PRIO")) q->acq_prio = false;
+    q->no_fast = devel_env_int("MCRX_NO_FAST", 0);
+    q->free_run = devel_env("MCRX_FREE_RUN") != nullptr;
+    q->payload_fr = devel_env_int("MCRX_PAYLOAD_FR", q->payload_fr);
+    q->payload_lean = devel_env_int("MCRX_PAYLOAD_LEAN", q->payload_lean) != 0;
+    q->payload_xb = devel_env_int("MCRX_PAYLOAD_XB", q->payload_xb);
+    q->seek_burst = devel_env_int("MCRX_SEEK_BURST", q->seek_burst);
+    q->acq_mode = devel_env_int("MCRX_ACQ_MODE", q->acq_mode);
+    q->lean_build = devel_env_int("MCRX_LEAN_BUILD", q->lean_build);
+    q->walk_lds_pad = (uint32_t)devel_env_int("MCRX_WALK_LDS_PAD", (int)q->walk_lds_pad);
+    q->round_lds_pad = (uint32_t)devel_env_int("MCRX_PAYLOAD_LDS_PAD", (int)q->round_lds_pad);
+    if (devel_env("MCRX_EVT")) q->ev_on = true;
+    if (devel_env("MCRX_EVT_DUMP")) { q->ev_on = true; q->ev_dump = true; }
+    if (devel_env("MCRX_SLOTS")) q->nslots = (unsigned)std::max(2, std::min(MCRX_SLOTS, atoi(devel_env("MCRX_SLOTS"))));
+    if (devel_env("MCRX_NSEG")) q->acq.nseg_fixed = (uint32_t)std::max(1, std::min(MCRX_SEG_MAX, atoi(devel_env("MCRX_NSEG"))));         // segments per channel, fixed
+    if (devel_env("MCRX_SEG_FRAMES")) q->acq.seg_frames = (uint32_t)std::max(1, std::min(64, atoi(devel_env("MCRX_SEG_FRAMES"))));         // ... or frames per segment aimed at
 }
 
 extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned cp, unsigned taper,
@@ -570,13 +596,14 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
     if (M < 8) return fail(MCRX_EINVAL, "error: multichannelrx, number of subcarriers must be at least 8");
     if (cp < 1) return fail(MCRX_EINVAL, "error: multichannelrx, cyclic prefix length must be at least 1");
     if (taper > cp) return fail(MCRX_EINVAL, "error: multichannelrx, taper length cannot exceed cyclic prefix length");
-    const bool bypass = cfg && cfg->struct_size >= offsetof(mcrx_hip_config, single_channel) + sizeof(uint32_t) && cfg->single_channel;
+    const mcrx_hip_config ec = effective_config(cfg);       // (fields behind the caller's struct_size read as 0 from here on)
+    const bool bypass = ec.single_channel != 0;
     if (bypass && N != 1) return fail(MCRX_EINVAL, "single_channel needs num_channels == 1");
-    const uint32_t in_fmt = (cfg && cfg->struct_size >= offsetof(mcrx_hip_config, input_format) + sizeof(uint32_t)) ? cfg->input_format : 0u;
+    const uint32_t in_fmt = ec.input_format;
     if (in_fmt != CH_IN_CF32 && in_fmt != CH_IN_SC16) return fail(MCRX_EINVAL, "input_format must be 0 (cf32) or 1 (sc16)");
     // sc16 ends where the channelizer's oscillator multiplies: configurations without channelizer_kernel in front take cf32 only
     if (in_fmt == CH_IN_SC16 && bypass) return fail(MCRX_EUNSUPP, "input_format = 1 (sc16) needs the channelizer: not with single_channel");
-    if (in_fmt == CH_IN_SC16 && cfg->struct_size >= offsetof(mcrx_hip_config, front_end) + sizeof(uint32_t) && cfg->front_end == 2)
+    if (in_fmt == CH_IN_SC16 && ec.front_end == 2)
         return fail(MCRX_EUNSUPP, "input_format = 1 (sc16) is not built for front_end = 2 (the oversampled front end stage by stage)");
     if (!bypass && !channelizer_supported(2 * N)) return fail(MCRX_EUNSUPP, "at most 1024 channels");
     if (M > 1024) return fail(MCRX_EUNSUPP, "at most 1024 subcarriers");
@@ -589,8 +616,7 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
     q->N = N; q->K = bypass ? 1 : 2 * N; q->M = M; q->cp = cp; q->taper = taper; q->bypass = bypass;
     q->in_fmt = in_fmt; q->ss = in_fmt == CH_IN_SC16 ? 2 * sizeof(int16_t) : sizeof(float2);
     if (q->od.init(M, cp, taper, p) != 0) { delete q; return fail(MCRX_EINVAL, "invalid subcarrier allocation"); }
-    if (cfg) memcpy(&q->cfg, cfg, std::min<size_t>(cfg->struct_size ? cfg->struct_size : sizeof(*cfg), sizeof(q->cfg)));
-    else q->cfg.payload_soft = 1;
+    q->cfg = ec;
     q->max_payload = q->cfg.max_payload_len ? q->cfg.max_payload_len : 2048;
     q->max_enc = 4 * (q->max_payload + 4) + 16;
     // floor: the per-frame scratch rows (max_enc + 16 bytes) also hold the soft Viterbi decoder's checkpoints, 128 bytes
@@ -623,12 +649,12 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
     q->arena_cap = (uint64_t)q->max_rec * (((uint64_t)q->max_payload + 15) & ~15ull);
     q->sarena_cap = (uint64_t)q->max_rec * (8ull * 8ull * (2ull * (q->max_payload + 4) + 8));
     if (q->sarena_cap > (8ull << 30)) q->sarena_cap = 8ull << 30;
-    q->pipelined = !(q->cfg.struct_size >= offsetof(mcrx_hip_config, serial) + sizeof(uint32_t) && q->cfg.serial) && devel_env("MCRX_SERIAL") == nullptr;
+    q->pipelined = !q->cfg.serial;
     q->slab_blocks = q->cfg.slab_blocks ? ((q->cfg.slab_blocks + MCRX_TILE - 1) & ~(uint32_t)(MCRX_TILE - 1)) : 0;      // 0: sized per launch; slabs are whole tiles
     { int dev = 0, n = 0;
       if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
           q->ncu = (uint32_t)n; }
-    const uint32_t front_end = (!bypass && q->cfg.struct_size >= offsetof(mcrx_hip_config, front_end) + sizeof(uint32_t)) ? q->cfg.front_end : 0;
+    const uint32_t front_end = bypass ? 0 : q->cfg.front_end;
     if (front_end > 2) { delete q; return fail(MCRX_EINVAL, "front_end must be 0, 1 or 2"); }
     q->oversampled = front_end == 2;
     if (front_end && ((q->K & (q->K - 1)) || q->K > 1024 || q->K < 2)) { delete q; return fail(MCRX_EUNSUPP, "the oversampled front end needs a power-of-two channel count <= 512"); }
@@ -637,11 +663,11 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
     q->dtheta = bypass ? 0u : channel_center_step(N);
     // channel-rate history in front of every push's tiles: a symbol window, plus -- if frames straddling two pushes are
     // to be deferred rather than walked serially -- the longest frame start-to-push-end distance to be covered
-    q->defer = (q->cfg.struct_size >= offsetof(mcrx_hip_config, defer_samples) + sizeof(uint32_t)) ? q->cfg.defer_samples : 0;
+    q->defer = q->cfg.defer_samples;
     q->hist_tiles = (unsigned)((q->defer + M + cp + 8 + MCRX_TILE - 1) / MCRX_TILE + 1);
 
     auto bail = [&](int rc) { mcrx_hip_destroy(q); return rc; };
-    int rc; bool no_spec_cfg = false;
+    int rc;
     {   // the channelizer's column tap table (kernels.h: ChanArgs::taps)
         std::vector<float> ct = q->chan_P == 28 ? pfb2_composite_taps(pfb2_prototype(q->K, 7, 60.0f), halfband_branch_taps(7, 60.0f), q->K)
                               : bypass ? q->taps : pfb_column_taps(q->taps, q->K);
@@ -672,41 +698,25 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
         if (hipEventCreateWithFlags(&q->ev_gen[g], hipEventDisableTiming) != hipSuccess) return bail(fail(MCRX_EHIP, "hipEventCreate failed"));
         if (hipEventCreateWithFlags(&q->ev_clean[g], hipEventDisableTiming) != hipSuccess) return bail(fail(MCRX_EHIP, "hipEventCreate failed"));
     }
-    q->scout = devel_env("MCRX_NO_SCOUT") == nullptr;
-    q->debug = getenv("MCRX_DEBUG") ? atoi(getenv("MCRX_DEBUG")) : 0;
-    q->no_fast = devel_env("MCRX_NO_FAST") ? atoi(devel_env("MCRX_NO_FAST")) : 0;
-    q->free_run = devel_env("MCRX_FREE_RUN") != nullptr;
-    {   // mcrx_hip_config::worker_build / acquisition / scout_build (fields past the caller's struct_size read as 0 = default)
-        auto field = [&](size_t off) { return q->cfg.struct_size >= off + sizeof(uint32_t) ? *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(&q->cfg) + off) : 0u; };
-        const uint32_t wb = field(offsetof(mcrx_hip_config, worker_build)), aq = field(offsetof(mcrx_hip_config, acquisition));
+    {   // mcrx_hip_config::worker_build / acquisition / scout_build
+        const uint32_t wb = q->cfg.worker_build, aq = q->cfg.acquisition, sb = q->cfg.scout_build;
         if (wb > 5 || aq > 5) return bail(fail(MCRX_EINVAL, "worker_build / acquisition out of range"));
         if (wb == 1) q->payload_xb = 0;
         if (wb >= 2) { q->payload_lean = 0; q->payload_fr = wb == 2 ? 1 : wb == 3 ? 2 : wb == 4 ? 4 : 0; }
         if ((aq >= 1 && aq <= 3) || aq == 5) q->acq_mode = (int)aq;
-        no_spec_cfg = aq == 4;
-        const uint32_t sb = field(offsetof(mcrx_hip_config, scout_build));
+        q->spec = aq != 4;                      // (wanted; whether the design and the device allow it: below)
         if (sb > 2) return bail(fail(MCRX_EINVAL, "scout_build out of range"));
         if (sb == 1) q->lean_build = 0;
         if (sb == 2) q->seg_walker = 0;
     }
-    if (devel_env("MCRX_PAYLOAD_FR")) q->payload_fr = atoi(devel_env("MCRX_PAYLOAD_FR"));
-    if (devel_env("MCRX_PAYLOAD_LEAN")) q->payload_lean = atoi(devel_env("MCRX_PAYLOAD_LEAN")) != 0;
-    if (devel_env("MCRX_PAYLOAD_XB")) q->payload_xb = atoi(devel_env("MCRX_PAYLOAD_XB"));
-    if (devel_env("MCRX_SEEK_BURST")) q->seek_burst = atoi(devel_env("MCRX_SEEK_BURST"));
-    if (devel_env("MCRX_ACQ_MODE")) q->acq_mode = atoi(devel_env("MCRX_ACQ_MODE"));
-    if (devel_env("MCRX_WALK_LDS_PAD")) q->walk_lds_pad = (uint32_t)atoi(devel_env("MCRX_WALK_LDS_PAD"));
-    if (devel_env("MCRX_PAYLOAD_LDS_PAD")) q->round_lds_pad = (uint32_t)atoi(devel_env("MCRX_PAYLOAD_LDS_PAD"));
-    if (devel_env("MCRX_EVT")) q->ev_on = true;
-    if (devel_env("MCRX_EVT_DUMP")) { q->ev_on = true; q->ev_dump = true; }
-    if (devel_env("MCRX_SLOTS")) q->nslots = (unsigned)std::max(2, std::min(MCRX_SLOTS, atoi(devel_env("MCRX_SLOTS"))));
+    read_devel_env(q);
     if (!q->pipelined) q->nslots = 2;
     if ((rc = q->alloc(&q->d_njobs, MCRX_SLOTS))) return bail(rc);      // one counter per slot: a launch's placement kernel zeroes the next slot's
     if ((rc = q->alloc(&q->d_stats, 8))) return bail(rc);
     // (coherent: with hipHostMallocMapped alone the allocation is non-coherent and a free-running host -- one that never
     //  synchronizes with the device -- does not see the kernels' updates at all)
-    if (hipHostMalloc((void **)&q->h_hint, 12 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
-        for (int i = 0; i < 12; i++) q->h_hint[i] = 0;    // [0] longest coded frame, [1] widest prediction list, [2] walked, [3] adopted, [4] frames on a cadence, [5] frames seen, [11] a frame with the K = 7 code was decoded,
-                                                          // [8] QAM hand-offs, [9] trellis blocks, [10] general-list frames of the most recent launch (kernels.h: list_hint)
+    if (hipHostMalloc((void **)&q->h_hint, HINT_WORDS * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
+        for (int i = 0; i < HINT_WORDS; i++) q->h_hint[i] = 0;          // (the words: acq_shared.h, HintWord)
         if (hipHostGetDevicePointer((void **)&q->d_hint, q->h_hint, 0) != hipSuccess) q->d_hint = nullptr;
     }
     if (q->scout) {
@@ -727,18 +737,15 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
             // payloads = 0.4 GB: allocated when the first frame with the code has been seen (cfg.conv_scratch), launch_sync.
             q->vit_rows = vf::rows_for(4u * q->max_enc + 6u);
             q->vit_waves = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(q->max_rec, 2048));
-            q->vit_mode = q->cfg.struct_size >= offsetof(mcrx_hip_config, conv_scratch) + sizeof(uint32_t) ? q->cfg.conv_scratch : 0u;
+            q->vit_mode = q->cfg.conv_scratch;
             if (q->vit_mode > 2) return bail(fail(MCRX_EINVAL, "conv_scratch must be 0, 1 or 2"));
             if ((rc = q->alloc(&q->d_vit_passes, 8))) return bail(rc);
             if (q->vit_mode == 1 && (rc = q->alloc_raw(&q->d_vit_scratch, (size_t)q->vit_waves * q->vit_rows * 64))) return bail(rc);
         }
-        // speculative acquisition (lean path only): slots, their equalisers, the prediction lists
+        // speculative acquisition (lean path only): slots, their equalisers, the anchors
         const bool lean = (q->sc.log2M >= 6 && q->sc.M == 64 * q->sc.E && q->sc.M_pilot <= 64) ||
                           (q->sc.M == 48 && q->sc.E == 1 && q->sc.M_pilot <= 64);        // (48 = 3 x 16: the reference applications' default, round 5)
-        q->spec = lean && q->d_hint && !no_spec_cfg && devel_env("MCRX_NO_SPEC") == nullptr;
-        if (devel_env("MCRX_NSEG")) q->nseg_fixed = (uint32_t)std::max(1, std::min(MCRX_SEG_MAX, atoi(devel_env("MCRX_NSEG"))));           // experiments: segments per channel, fixed
-        if (devel_env("MCRX_SEG_FRAMES")) q->seg_frames = (uint32_t)std::max(1, std::min(64, atoi(devel_env("MCRX_SEG_FRAMES"))));            // ... or frames per segment aimed at
-        if (devel_env("MCRX_LEAN_BUILD")) q->lean_build = atoi(devel_env("MCRX_LEAN_BUILD"));
+        q->spec = q->spec && lean && q->d_hint;
         if (q->spec) {
             if ((rc = q->alloc(&q->d_spec, (size_t)q->nch * MCRX_SPEC_MAX))) return bail(rc);
             if ((rc = q->alloc(&q->d_spec_R, (size_t)q->nch * MCRX_SEG_MAX * M))) return bail(rc);
@@ -759,7 +766,7 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
     if (hipStreamCreate(&q->stream) != hipSuccess) return bail(fail(MCRX_EHIP, "hipStreamCreate failed"));
     {   // the acquisition stream carries the serial per-channel chains every payload launch waits for: highest priority
         int least = 0, greatest = 0;
-        const bool prio = devel_env("MCRX_NO_PRIO") == nullptr && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least;
+        const bool prio = q->acq_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least;
         if ((prio ? hipStreamCreateWithPriority(&q->s_scout, hipStreamDefault, greatest) : hipStreamCreate(&q->s_scout)) != hipSuccess)
             return bail(fail(MCRX_EHIP, "hipStreamCreate failed"));
     }
@@ -868,17 +875,12 @@ static int launch_channelizer(mcrx_hip_t q, const void *x, size_t nblocks, uint6
     RC(q->ev_end(0, st));
     return MCRX_OK;
 }
-// One pass of the synchronizer bank over a channel-tile buffer that is ready in `st`'s order.
-// Pipelined: the acquisition kernels go to s_scout, the payload workers and the decoder to s_work; `st` itself
-// does not wait for them (mcrx_hip_stream_wait / flush / poll do).  Slot reuse: launch k waits for launch k-2's
-// decode, which frees the job counter its placement kernel zeroes and (in order on s_work) its own slot.
-static int launch_sync(mcrx_hip_t q, const float2 *chan, unsigned stride, unsigned off, int64_t buf_first, int64_t end, hipStream_t st)
+// ---- launch_sync in parts: what is allocated late, the kernels' argument block, the acquisition launches, the workers' and decoders'
+// What a handle allocates when it first needs it: the device's shared de-interleaver tables (first synchronizer launch), the K = 7
+// decoder's scratch (the launch after the device reports a frame with the code), more slots for the segment waves.
+static int sync_lazy_allocs(mcrx_hip_t q, const AcqPlan &plan)
 {
-    const unsigned slot = (unsigned)(q->seq % q->nslots), next = (unsigned)((q->seq + 1) % q->nslots);
-    const int g = q->gen;
-    q->mon.used = false;
-    if (q->mon.on) RC(launch_monitor(q, chan, stride, off, buf_first, end, st));
-    if (!q->il_tried) {                    // first synchronizer launch of this handle: the device's shared de-interleaver tables
+    if (!q->il_tried) {
         q->il_tried = true;
         // (a table that cannot be built -- 40-120 MB plus twice that in scratch -- is no table, not an error: the decoder's in-place passes
         //  serve every length)
@@ -889,7 +891,32 @@ static int launch_sync(mcrx_hip_t q, const float2 *chan, unsigned stride, unsign
             if (q->debug) fprintf(stderr, "[mcrx] de-interleaver gather tables not built (%s): decoding without them\n", mcrx_hip_last_error());
         }
     }
-    SyncArgs a;
+    if (!q->d_vit_scratch && q->vit_mode == 0 && q->vit_rows && plan.want_k7) {
+        // a frame with the K = 7 code has been decoded: its decoder's scratch from here on (a failure is not an error: the block decoder stays)
+        const size_t vit_bytes = (size_t)q->vit_waves * q->vit_rows * 64 * sizeof(uint2);       // [waves][rows][64 lanes] of 8 bytes
+        if (hipMalloc((void **)&q->d_vit_scratch, vit_bytes) != hipSuccess) {
+            (void)hipGetLastError(); q->d_vit_scratch = nullptr; q->vit_mode = 2;
+            if (q->debug) fprintf(stderr, "[mcrx] the K = 7 decoder's scratch (%zu MB) could not be allocated: the block decoder stays\n", vit_bytes >> 20);
+        } else q->owned.push_back(q->d_vit_scratch);
+    }
+    if (plan.spec_stride > q->spec_stride) {
+        // (rare: the first long push of a few-channel stream.  Launches in flight use the old slots: wait for them.)
+        uint32_t ns = q->spec_stride; while (ns < plan.spec_stride) ns *= 2;
+        SpecSlot *nb = nullptr;
+        HIPCHK(hipDeviceSynchronize());
+        RC(q->alloc(&nb, (size_t)q->nch * ns));
+        q->d_spec = nb; q->spec_stride = ns;            // (the old array stays with the handle until it is destroyed)
+    }
+    return MCRX_OK;
+}
+
+// The argument block of the launch's kernels, as the workers and decoders get it; the acquisition launches vary seg_phase / seg_jobs
+// and the tail kernel's copy on theirs.  Every field not named here is zero / null.
+static SyncArgs sync_args(mcrx_hip_t q, const float2 *chan, unsigned stride, unsigned off, int64_t buf_first, int64_t end, const AcqPlan &plan)
+{
+    const unsigned slot = (unsigned)(q->seq % q->nslots), next = (unsigned)((q->seq + 1) % q->nslots);
+    const int g = q->gen;
+    SyncArgs a{};
     a.c = q->sc; a.chan = chan; a.chan_stride = stride; a.chan_off = off;
     a.buf_first = buf_first; a.end = end; a.nch = q->nch; a.ch_first = q->ch_first;
     a.st = q->d_st; a.hbits = q->d_hbits; a.R = q->d_R; a.soft = q->d_soft; a.tmpa = q->d_tmpa; a.tmpb = q->d_tmpb;
@@ -899,49 +926,34 @@ static int launch_sync(mcrx_hip_t q, const float2 *chan, unsigned stride, unsign
     a.debug = q->debug; a.no_fast = q->no_fast; a.seek_burst = q->seek_burst;
     a.payload_fr = q->payload_fr; a.payload_lean = q->payload_lean; a.payload_xb = q->payload_xb;
     a.payload_lds_pad = q->acq_mode == 2 ? q->walk_lds_pad : q->round_lds_pad;
-    a.vit_off = 0;
     a.scout = q->scout ? 1 : 0;
     a.jobs = q->d_jobs[slot]; a.njobs = q->d_njobs + slot; a.njobs_next = q->d_njobs + next; a.max_jobs = q->max_jobs;
-    a.gen_list = q->d_gen[slot]; a.dec_lds_soft = 0;
-    if (!q->d_vit_scratch && q->vit_mode == 0 && q->vit_rows && q->h_hint && ((volatile uint32_t *)q->h_hint)[11]) {
-        // a frame with the K = 7 code has been decoded: its decoder's scratch from here on (a failure is not an error: the block decoder stays)
-        const size_t vit_bytes = (size_t)q->vit_waves * q->vit_rows * 64 * sizeof(uint2);       // [waves][rows][64 lanes] of 8 bytes
-        if (hipMalloc((void **)&q->d_vit_scratch, vit_bytes) != hipSuccess) {
-            (void)hipGetLastError(); q->d_vit_scratch = nullptr; q->vit_mode = 2;
-            if (q->debug) fprintf(stderr, "[mcrx] the K = 7 decoder's scratch (%zu MB) could not be allocated: the block decoder stays\n", vit_bytes >> 20);
-        } else q->owned.push_back(q->d_vit_scratch);
-    }
+    a.gen_list = q->d_gen[slot];
     a.vit_scratch = q->d_vit_scratch; a.vit_rows = q->vit_rows; a.vit_waves = q->vit_waves; a.vit_passes = q->d_vit_passes;
-    a.qam_list = q->d_qam[slot]; a.qam_next = q->d_qam[next]; a.list_hint = nullptr;
+    a.qam_list = q->d_qam[slot]; a.qam_next = q->d_qam[next];
     a.live = q->d_live[slot]; a.live_next = q->d_live[next];
-    a.live_off = 0; a.split_rest = 0; a.dec_phase = 0;
-    a.frames_hint = (q->h_hint && q->d_hint) ? ((volatile uint32_t *)q->h_hint)[7] : ~0u;
-    if (a.frames_hint == 0) a.frames_hint = ~0u;                 // (a launch without frames says nothing about the next)
-    for (int i = 0; i < 3; i++) a.grid_hint[i] = ~0u;
-    if (q->h_hint && q->d_hint) {                        // (sticky for a while: a list that was non-empty within the last 64 launches keeps its full grid)
-        a.list_hint = q->d_hint + 8;
-        for (int i = 0; i < 3; i++) {
-            const uint32_t v = ((volatile uint32_t *)q->h_hint)[8 + i];
-            if (v) { q->list_seen[i] = v; q->list_age[i] = 0; } else if (q->list_age[i] < 64) q->list_age[i]++; else q->list_seen[i] = 0;
-            a.grid_hint[i] = q->list_seen[i];
-        }
-    }
     a.jR = q->d_jR[slot]; a.jsoft = q->d_jsoft[slot]; a.jtmp = q->d_jtmp[slot];
     a.stats = q->d_stats;
-    a.hint = q->d_hint; a.enc_hint = (q->h_hint && q->d_hint) ? *(volatile uint32_t *)q->h_hint : 0u;
-    a.spec = q->d_spec; a.spec_stride = q->spec_stride; a.spec_R = q->d_spec_R; a.pred = nullptr; a.pred_n = nullptr; a.spec_cap = 0; a.spec_hint = nullptr; a.walk_hint = nullptr;
-    a.nseg = 0; a.seg_phase = 0; a.anchor = nullptr; a.seg_jobs = 1; a.seekst = q->d_seekst; a.seg_walker = q->seg_walker;
-    a.no_syms = (q->cfg.struct_size >= offsetof(mcrx_hip_config, skip_framesyms) + sizeof(uint32_t) && q->cfg.skip_framesyms == 2) ? 1 : 0;
-    hipStream_t sa = st, sw = st;
-    // The host never waits for the device on this path (slots are handed over by stream waits), so a free-running caller
-    // can be any number of launches ahead -- and the hints the kernels leave for the next launch (widest prediction list,
-    // scouts that had to walk) would arrive after everything is enqueued.  Bound the lead to the slots: wait here for the
-    // launch that last used this one (the device still has nslots - 1 launches queued behind it) -- once per turn of the
-    // slots, i.e. a lead of nslots .. 2 nslots - 1 launches: a wait per launch costs a short-slab stream (8 channels,
-    // 0.36 ms per push) 4 %.
-    if (q->pipelined && q->scout && q->spec && q->seq >= q->nslots && slot == 0 && !q->free_run) HIPCHK(hipEventSynchronize(q->ev_done[slot]));
+    // the hint block (acq_shared.h): where the kernels leave their words, and what the host last read there
+    a.hint = q->d_hint;
+    if (q->h_hint && q->d_hint) a.list_hint = q->d_hint + HINT_LIST_BASE;
+    a.frames_hint = plan.frames_hint; a.enc_hint = plan.enc_hint;
+    for (int i = 0; i < 3; i++) a.grid_hint[i] = plan.grid_hint[i];
+    a.spec = q->d_spec; a.spec_stride = q->spec_stride; a.spec_R = q->d_spec_R;
+    a.seg_jobs = plan.seg_jobs; a.seekst = q->d_seekst; a.seg_walker = q->seg_walker;
+    if (q->spec) { a.nseg = plan.nseg; a.spec_cap = plan.spec_cap; a.walk_hint = q->d_hint + HINT_WALK_BASE; a.anchor = q->d_anchor; }
+    a.no_syms = q->cfg.skip_framesyms == 2 ? 1 : 0;
+    a.defer_limit = (int64_t)q->defer;
+    return a;
+}
+
+// The launch's acquisition on `sa`, behind the buffer's readiness in `st`: the segment waves the plan asks for, strung together by the
+// per-channel scouts (lean configurations), or one wave per channel that walks everything.
+static int launch_acquisition(mcrx_hip_t q, SyncArgs &a, const AcqPlan &plan, hipStream_t st, hipStream_t sa)
+{
+    const unsigned slot = (unsigned)(q->seq % q->nslots), next = (unsigned)((q->seq + 1) % q->nslots);
+    const int g = q->gen;
     if (q->pipelined && q->scout) {
-        sa = q->s_scout; sw = q->s_work;
         HIPCHK(hipEventRecord(q->ev_ready[slot], st));
         HIPCHK(hipStreamWaitEvent(sa, q->ev_ready[slot], 0));
         if (q->seq + 1 >= q->nslots) HIPCHK(hipStreamWaitEvent(sa, q->ev_done[next], 0));     // launch seq + 1 - nslots
@@ -950,106 +962,22 @@ static int launch_sync(mcrx_hip_t q, const float2 *chan, unsigned stride, unsign
     q->acq_stream = sa;
     if (q->clean_pending[g]) { HIPCHK(hipStreamWaitEvent(sa, q->ev_clean[g], 0)); q->clean_pending[g] = false; }
     RC(q->ev_begin(1, sa));
-    a.stop_after_walk = 0; a.tail_only = 0; a.defer_limit = (int64_t)q->defer; a.burst_limit = 0; a.round_idx = 0;
     if (q->spec) {
         // lean configurations: a payload that straddles two pushes is walked by the tail kernel (before the acquisition: the frame
         // the previous push left in progress; after it: the one this push ends in); everything else is acquired by the segment
         // waves (kernels.h, SpecSlot) and strung together by the per-channel scouts, which walk by themselves only where no
         // segment wave stood in their exact state.
         SyncArgs t = a;
-        t.tail_only = 1; t.pred = nullptr; t.pred_n = nullptr; t.spec_cap = 0; t.nseg = 0; t.spec_hint = nullptr; t.stats = nullptr;
+        t.tail_only = 1; t.spec_cap = 0; t.nseg = 0; t.seg_jobs = 1; t.walk_hint = nullptr; t.anchor = nullptr; t.stats = nullptr;
         // (Symbols wider than two samples per lane have no lean scout: theirs is the whole state machine, which carries a payload in progress
         //  across pushes by itself, and the two tail launches never find anything to do there.  Leaving them out was measured -- round 6, alternating
         //  runs of a development build, configs[2]: 105.2-106.8 without against 106.7-109.4 Gsample/s with them -- and is not done.)
         HIPCHK(sync_launch_tail(t, sa));
-        // How many segments: enough waves to fill the chip and short chains (a wave's frames are acquired one after the other),
-        // but every segment costs two acquisitions that produce nothing (its first frame, taken from an arbitrary state, and the
-        // frame that links it to the next segment), and its share of the channel's MCRX_SPEC_MAX slots must hold its frames.
-        // F = frames per channel and push, from the hand-offs the most recent finished launch counted (host-mapped, read without
-        // a sync, a launch or two late); before the first report: one segment per 16 Ki samples.  Only speed depends on it.
-        const uint64_t nsamp = (uint64_t)(end - buf_first) > (uint64_t)q->hist_tiles * MCRX_TILE ? (uint64_t)(end - buf_first) - (uint64_t)q->hist_tiles * MCRX_TILE : 1;
-        uint32_t nseg = q->nseg_fixed;
-        if (!nseg) {
-            const uint32_t nj = q->h_hint ? ((volatile uint32_t *)q->h_hint)[7] : 0u;
-            if (nj) q->frames_per_push = 0.5f * q->frames_per_push + 0.5f * ((float)nj / (float)q->nch) * ((float)nsamp / (float)(q->last_nsamp ? q->last_nsamp : nsamp));
-            const float F = q->frames_per_push > 0.f ? q->frames_per_push : (float)nsamp / 16384.0f;
-            float want = F / (float)q->seg_frames;                                   // chains of seg_frames (+ 2) frames ...
-            const float fill = 1536.0f / (float)q->nch;                              // ... shorter while the chip is not full (1.5 waves per SIMD)
-            if (want < fill) want = fill < F / 2.0f ? fill : F / 2.0f;
-            // on a cadence the lattice starts make segments free (no wasted acquisitions), so chains go down to two frames while
-            // all the waves still run at once (2 per SIMD): what a few-channel receiver's push is made of is this chain's latency
-            // (the lean segment waves of the 64-subcarrier designs run acq_lean_waves() to a SIMD, and a frame there is a chain of ~15 us:
-            //  chains of ONE frame while every wave is resident at once)
-            if (q->cadenced) {
-                const int lw = q->seg_walker ? 0 : acq_lean_waves(q->sc);
-                const float conc = (lw ? 1024.0f * (float)lw : 2048.0f) / (float)q->nch, shortest = lw ? F : F / 2.0f;
-                const float c2 = conc < shortest ? conc : shortest;
-                if (want < c2) want = c2;
-            }
-            // (a wave's slots: F / nseg * 1.25 + 4, at most half a window of the scouts' slot headers -- see spw below)
-            const float least = 1.25f * F / (float)(MCRX_SPEC_MAX / 2 - 4);
-            if (want < least) want = least;
-            const float most = q->nch * 128u <= 4096u ? 128.0f : 64.0f;               // (few channels: even 128 waves each leave the chip mostly empty)
-            nseg = want < 1.0f ? 1u : (want > most ? (uint32_t)most : (uint32_t)(want + 0.999f));
-        }
-        if (nseg > MCRX_SEG_MAX) nseg = MCRX_SEG_MAX;
-        // The anchor phase (kernels.h, SyncArgs::seg_phase) is one more launch and one frame's latency in front of everything else: worth it
-        // while most frames follow their predecessor at the distance of the pair before (the scouts count both, place_jobs_kernel
-        // copies the totals to host-mapped words), useless on traffic without a cadence.  Windows of 8 launches; MCRX_ACQ_MODE=3 / 1 pins it.
-        if (q->h_hint && ++q->cad_count >= 8) {
-            volatile uint32_t *h = (volatile uint32_t *)q->h_hint;
-            const uint32_t sm = h[4], fr = h[5];
-            const uint32_t ds = sm >= q->cad_same ? sm - q->cad_same : 0u, df = fr >= q->cad_frames ? fr - q->cad_frames : 0u;     // (mcrx_hip_spec_stats may have reset them)
-            if (df > q->nch) q->cadenced = 2ull * ds > df;
-            q->cad_same = sm; q->cad_frames = fr; q->cad_count = 0;
-            // ... and which anchor.  The lattice carried over from the previous push needs no launch in front of the segment waves: as it
-            // stood in the stream (a continuous stream), or as it stood from the push's beginning (pushes that are bursts of their own, a
-            // replayed slab with a gap at its end).  A wrong one shows: every segment hands off two frames nobody adopts.  So: one
-            // after the other while more than an eighth of the slots filled go to waste, the anchor phase (which finds the lattice inside
-            // every push) when neither holds, and from the start again after 256 launches.
-            const uint32_t sf = h[6], ad = h[3];
-            const uint32_t dsf = sf >= q->anc_filled ? sf - q->anc_filled : 0u, dad = ad >= q->anc_adopted ? ad - q->anc_adopted : 0u;
-            if (q->anchor_kind < 2 && dad > q->nch && dsf > dad + dad / 8) { if (++q->anchor_kind == 2) q->anchor_retry = 256; }
-            q->anc_filled = sf; q->anc_adopted = ad;
-        }
-        if (q->anchor_kind == 2 && q->anchor_retry && --q->anchor_retry == 0) q->anchor_kind = 0;
-        if (q->acq_mode == 3 || q->acq_mode == 5) q->cadenced = true;
-        q->last_nsamp = nsamp;
-        // Slots per wave: its share of MCRX_SPEC_MAX while the push's frames fit there (the scouts then hold every slot header in
-        // registers), else what its frames need -- the channel's slots then exceed the window and the scouts move it along
-        // (ofdmsync.hip: adopt_lookup), which takes two neighbouring waves' slots to fit in one window.
-        uint32_t spw = MCRX_SPEC_MAX / nseg;
-        { const float Fs = q->frames_per_push > 0.f ? q->frames_per_push : (float)nsamp / 16384.0f;
-          const uint32_t need = (uint32_t)(1.25f * Fs / (float)nseg) + 4u;
-          if (need > spw) spw = need > MCRX_SPEC_MAX / 2 ? MCRX_SPEC_MAX / 2 : need; }
-        if ((uint64_t)nseg * spw > q->spec_stride) {
-            // (rare: the first long push of a few-channel stream.  Launches in flight use the old slots: wait for them.)
-            uint32_t ns = q->spec_stride; while (ns < nseg * spw) ns *= 2;
-            SpecSlot *nb = nullptr;
-            HIPCHK(hipDeviceSynchronize());
-            RC(q->alloc(&nb, (size_t)q->nch * ns));
-            q->d_spec = nb; q->spec_stride = ns;            // (the old array stays with the handle until it is destroyed)
-            a.spec = q->d_spec; a.spec_stride = q->spec_stride;
-        }
-        a.nseg = nseg; a.spec_cap = nseg * spw;
-        { const float Fq = q->frames_per_push > 0.f ? q->frames_per_push : (float)nsamp / 16384.0f;
-          const float per = Fq / (float)nseg + 2.0f;                     // its share of the channel's frames + the two at the segment's ends
-          a.seg_jobs = per < 2.0f ? 2u : (per > 32.0f ? 32u : (uint32_t)(per + 0.999f));
-          // ... and all the first blocks together leave the scouts' own hand-offs and second blocks half of the list
-          const uint32_t room = q->max_jobs / 2 / (q->nch * nseg);
-          if (a.seg_jobs > room) a.seg_jobs = room ? room : 1u; }
-        a.walk_hint = q->d_hint ? q->d_hint + 2 : nullptr;
-        if (a.debug & 4) fprintf(stderr, "[host] launch %llu: %u segments per channel, %.1f frames per channel and push expected\n", (unsigned long long)q->seq, nseg, q->frames_per_push);
-        a.anchor = q->d_anchor;
-        if (q->acq_mode == 2) a.spec_cap = 0;                        // (MCRX_ACQ_MODE=2: no segment waves, the scouts walk everything)
-        else if (q->acq_mode == 1 || nseg == 1 || (q->acq_mode == 0 && !q->cadenced)) { a.seg_phase = 0; HIPCHK(sync_launch_spec(a, sa)); }     // one launch, coarse starts
-        else if (q->acq_mode != 3 && q->anchor_kind < 2) { a.seg_phase = 3 + q->anchor_kind; HIPCHK(sync_launch_spec(a, sa)); }       // one launch, anchored on the entry state (a channel that does not stand behind a frame: coarse starts)
-        else {
-            const uint32_t sj = a.seg_jobs;
-            a.seg_phase = 1; a.seg_jobs = 1; HIPCHK(sync_launch_spec(a, sa));        // the first frame of every channel, from its real state: the cadence's anchor
-            a.seg_phase = 2; a.seg_jobs = sj; HIPCHK(sync_launch_spec(a, sa));       // everything behind it, segment-parallel
-        }
-        a.seg_phase = 0;
+        if (a.debug & 4) fprintf(stderr, "[host] launch %llu: %u segments per channel, %.1f frames per channel and push expected\n", (unsigned long long)q->seq, plan.nseg, q->acq.frames_per_push);
+        // the segment waves (acq_plan.hpp): none, one launch from coarse or anchored starts, or the cadence's anchor (the first frame of every
+        // channel, from its real state) and everything behind it, segment-parallel
+        for (int i = 0; i < plan.nphase; i++) { a.seg_phase = plan.phase[i].seg_phase; a.seg_jobs = plan.phase[i].seg_jobs; HIPCHK(sync_launch_spec(a, sa)); }
+        a.seg_phase = 0; a.seg_jobs = plan.seg_jobs;
         if (q->lean_build == 1) HIPCHK(sync_launch_walk(a, sa)); else HIPCHK(sync_launch_lean(a, sa));
         // a frame the lean scout could neither hand off nor defer runs past the end of this buffer: walked up to there
         HIPCHK(sync_launch_tail(t, sa));
@@ -1057,57 +985,96 @@ static int launch_sync(mcrx_hip_t q, const float2 *chan, unsigned stride, unsign
         HIPCHK(sync_launch(a, sa));           // general configurations: one wave per channel walks everything
     }
     RC(q->ev_end(1, sa));
-    if (q->scout) {
-        RC(q->ev_begin(2, sa));               // record placement
-        HIPCHK(sync_launch_payload(a, 0, sa));
-        RC(q->ev_end(2, sa));
-        if (sw != sa) {
-            HIPCHK(hipEventRecord(q->ev_scout[slot], sa));
-            HIPCHK(hipStreamWaitEvent(sw, q->ev_scout[slot], 0));
-        }
-        // (Round 5: the K = 7 decoder's kernel + the general decoder on a stream of their own while convolutional frames arrive, so that the
-        //  next push's workers need not queue behind 0.3 ms of trellis: 8 channels x 100 frames 41.4 -> 35.9 Gsample/s, x 50 frames 25.9 -> 19.8.
-        //  Not kept: streams are not free, scratch/README.md.)
-        // payload workers; the LDS-path packet decoder; the general decoder (nearly always an empty launch: ~12 us.
-        // Giving it a stream of its own was tried: a fifth stream makes the harvest's copy stream share a hardware
-        // queue with a busy one, and every poll then waits a slab's time for its 16-byte copies -- harvest 123 -> 98 Gsample/s)
-        // While the lists of the launch behind the workers (QAM payloads, frames beyond the grid) and of the general decoder have been
-        // empty for 64 launches, those two go to a stream of their own behind this push's decoder, with a decoder launch for their frames
-        // only -- whatever they find is still done, in this push, it just no longer stands between this push's decoder and the next push's
-        // workers (kernels.h, split_rest).  Everything of the push is finished when THAT stream is; a change of mode orders the two.
-        const bool split = sw == q->s_work && q->s_side && q->h_hint && q->d_hint && q->list_seen[0] == 0 && q->list_seen[2] == 0 &&
-                           q->seq >= 8 && a.frames_hint != ~0u && a.frames_hint < 2048u && sync_payload_splits(a);
-        // Round 6: while frames arrive on the general decoder's list (the K = 7 code: 0.25-0.3 ms of trellis per 800 frames, one wave per
-        // frame) THAT launch goes to the fourth stream behind this push's decoder, so that the next push's workers do not queue behind it:
-        // the work stream carried workers + decoder + trellis = 0.47 ms per push of an 8-channel receiver, now 0.2 | 0.3 side by side.  All
-        // general-decoder launches of such a phase follow each other on that one stream (they share the K = 7 scratch).
-        const bool gen_side = !split && sw == q->s_work && q->s_side && q->h_hint && q->d_hint && q->list_seen[2] != 0 && q->seq >= 8 &&
-                              !devel_env("MCRX_NO_GEN_SIDE");
-        hipStream_t sd = sw;
-        if (split) { a.split_rest = 1; a.dec_phase = 1; sd = q->s_side; }
-        else if (gen_side) sd = q->s_side;
-        else if (q->side_last) HIPCHK(hipStreamWaitEvent(sw, q->ev_side_last, 0));       // (back in one line: behind what the other stream still holds)
-        RC(q->ev_begin(3, sw));
-        HIPCHK(sync_launch_payload(a, 1, sw));
-        RC(q->ev_end(3, sw));
-        RC(q->ev_begin(4, sw));
-        HIPCHK(sync_launch_payload(a, 2, sw));
-        if (split) {
-            HIPCHK(hipEventRecord(q->ev_side[slot], sw));
-            HIPCHK(hipStreamWaitEvent(sd, q->ev_side[slot], 0));
-            HIPCHK(sync_launch_payload(a, 4, sd));
-            a.dec_phase = 2;
-            HIPCHK(sync_launch_payload(a, 2, sd));
-        } else if (gen_side) {
-            HIPCHK(hipEventRecord(q->ev_side[slot], sw));
-            HIPCHK(hipStreamWaitEvent(sd, q->ev_side[slot], 0));
-        }
-        HIPCHK(sync_launch_payload(a, 3, sd));
-        RC(q->ev_end(4, sd));
-        if (split || gen_side) HIPCHK(hipEventRecord(q->ev_side_last, sd));
-        q->side_last = split || gen_side;
-        sw = sd;
+    return MCRX_OK;
+}
+
+// Record placement behind the acquisition on `sa`, then payload workers and decoders on `sw` -- or partly on the side stream; `sw`
+// returns as the stream the push's last launch went to.
+static int launch_workers(mcrx_hip_t q, SyncArgs &a, hipStream_t sa, hipStream_t &sw)
+{
+    const unsigned slot = (unsigned)(q->seq % q->nslots);
+    RC(q->ev_begin(2, sa));               // record placement
+    HIPCHK(sync_launch_payload(a, 0, sa));
+    RC(q->ev_end(2, sa));
+    if (sw != sa) {
+        HIPCHK(hipEventRecord(q->ev_scout[slot], sa));
+        HIPCHK(hipStreamWaitEvent(sw, q->ev_scout[slot], 0));
     }
+    // (Round 5: the K = 7 decoder's kernel + the general decoder on a stream of their own while convolutional frames arrive, so that the
+    //  next push's workers need not queue behind 0.3 ms of trellis: 8 channels x 100 frames 41.4 -> 35.9 Gsample/s, x 50 frames 25.9 -> 19.8.
+    //  Not kept: streams are not free, scratch/README.md.)
+    // payload workers; the LDS-path packet decoder; the general decoder (nearly always an empty launch: ~12 us.
+    // Giving it a stream of its own was tried: a fifth stream makes the harvest's copy stream share a hardware
+    // queue with a busy one, and every poll then waits a slab's time for its 16-byte copies -- harvest 123 -> 98 Gsample/s)
+    // While the lists of the launch behind the workers (QAM payloads, frames beyond the grid) and of the general decoder have been
+    // empty for 64 launches, those two go to a stream of their own behind this push's decoder, with a decoder launch for their frames
+    // only -- whatever they find is still done, in this push, it just no longer stands between this push's decoder and the next push's
+    // workers (kernels.h, split_rest).  Everything of the push is finished when THAT stream is; a change of mode orders the two.
+    const bool side = sw == q->s_work && q->s_side && q->h_hint && q->d_hint && q->seq >= 8;
+    const bool split = side && q->acq.list_seen[0] == 0 && q->acq.list_seen[2] == 0 &&
+                       a.frames_hint != ~0u && a.frames_hint < 2048u && sync_payload_splits(a);
+    // Round 6: while frames arrive on the general decoder's list (the K = 7 code: 0.25-0.3 ms of trellis per 800 frames, one wave per
+    // frame) THAT launch goes to the fourth stream behind this push's decoder, so that the next push's workers do not queue behind it:
+    // the work stream carried workers + decoder + trellis = 0.47 ms per push of an 8-channel receiver, now 0.2 | 0.3 side by side.  All
+    // general-decoder launches of such a phase follow each other on that one stream (they share the K = 7 scratch).
+    const bool gen_side = !split && side && q->acq.list_seen[2] != 0 && !devel_env("MCRX_NO_GEN_SIDE");
+    hipStream_t sd = sw;
+    if (split) { a.split_rest = 1; a.dec_phase = 1; sd = q->s_side; }
+    else if (gen_side) sd = q->s_side;
+    else if (q->side_last) HIPCHK(hipStreamWaitEvent(sw, q->ev_side_last, 0));       // (back in one line: behind what the other stream still holds)
+    RC(q->ev_begin(3, sw));
+    HIPCHK(sync_launch_payload(a, 1, sw));
+    RC(q->ev_end(3, sw));
+    RC(q->ev_begin(4, sw));
+    HIPCHK(sync_launch_payload(a, 2, sw));
+    if (split) {
+        HIPCHK(hipEventRecord(q->ev_side[slot], sw));
+        HIPCHK(hipStreamWaitEvent(sd, q->ev_side[slot], 0));
+        HIPCHK(sync_launch_payload(a, 4, sd));
+        a.dec_phase = 2;
+        HIPCHK(sync_launch_payload(a, 2, sd));
+    } else if (gen_side) {
+        HIPCHK(hipEventRecord(q->ev_side[slot], sw));
+        HIPCHK(hipStreamWaitEvent(sd, q->ev_side[slot], 0));
+    }
+    HIPCHK(sync_launch_payload(a, 3, sd));
+    RC(q->ev_end(4, sd));
+    if (split || gen_side) HIPCHK(hipEventRecord(q->ev_side_last, sd));
+    q->side_last = split || gen_side;
+    sw = sd;
+    return MCRX_OK;
+}
+
+// One pass of the synchronizer bank over a channel-tile buffer that is ready in `st`'s order.
+// Pipelined: the acquisition kernels go to s_scout, the payload workers and the decoder to s_work; `st` itself
+// does not wait for them (mcrx_hip_stream_wait / flush / poll do).  Slot reuse: launch k waits for launch k-2's
+// decode, which frees the job counter its placement kernel zeroes and (in order on s_work) its own slot.
+static int launch_sync(mcrx_hip_t q, const float2 *chan, unsigned stride, unsigned off, int64_t buf_first, int64_t end, hipStream_t st)
+{
+    const unsigned slot = (unsigned)(q->seq % q->nslots);
+    const int g = q->gen;
+    const bool own_streams = q->pipelined && q->scout;
+    q->mon.used = false;
+    if (q->mon.on) RC(launch_monitor(q, chan, stride, off, buf_first, end, st));
+    // The host never waits for the device on this path (slots are handed over by stream waits), so a free-running caller
+    // can be any number of launches ahead -- and the hints the kernels leave for the next launch (widest prediction list,
+    // scouts that had to walk) would arrive after everything is enqueued.  Bound the lead to the slots: wait here for the
+    // launch that last used this one (the device still has nslots - 1 launches queued behind it) -- once per turn of the
+    // slots, i.e. a lead of nslots .. 2 nslots - 1 launches: a wait per launch costs a short-slab stream (8 channels,
+    // 0.36 ms per push) 4 %.
+    if (own_streams && q->spec && q->seq >= q->nslots && slot == 0 && !q->free_run) HIPCHK(hipEventSynchronize(q->ev_done[slot]));
+    // the hint block, read once per launch and behind that wait (acq_plan.hpp: the snapshot rule), and what follows from it
+    const bool have_hints = q->h_hint && q->d_hint;
+    uint32_t hints[HINT_WORDS] = {};
+    if (have_hints) for (int i = 0; i < HINT_WORDS; i++) hints[i] = ((volatile uint32_t *)q->h_hint)[i];
+    const AcqInputs in = { (uint64_t)(end - buf_first), q->hist_tiles, q->nch, q->max_jobs, q->acq_mode, q->seg_walker,
+                           q->seg_walker ? 0 : acq_lean_waves(q->sc), have_hints, q->spec };
+    const AcqPlan plan = acq_plan(q->acq, hints, in);
+    RC(sync_lazy_allocs(q, plan));
+    SyncArgs a = sync_args(q, chan, stride, off, buf_first, end, plan);
+    hipStream_t sa = own_streams ? q->s_scout : st, sw = own_streams ? q->s_work : st;
+    RC(launch_acquisition(q, a, plan, st, sa));
+    if (q->scout) RC(launch_workers(q, a, sa, sw));
     if (q->mon.used) {                      // the slot is free again when the monitor has read its tiles, too
         HIPCHK(hipEventRecord(q->mon.ev_out, q->mon.s_mon));
         HIPCHK(hipStreamWaitEvent(sw, q->mon.ev_out, 0));
@@ -1428,8 +1395,7 @@ static int execute_device_any(mcrx_hip_t q, const void *d_iq, size_t nsamples, v
     // optional split into sub-slabs: within one call, sub-slab i+1's channelizer and acquisition overlap sub-slab i's
     // payload workers (consecutive calls overlap in the same way without it)
     const size_t nblocks = nsamples / q->K;
-    size_t chunk = q->cfg.struct_size >= offsetof(mcrx_hip_config, chunk_blocks) + sizeof(uint32_t) && q->cfg.chunk_blocks
-                       ? ((size_t)q->cfg.chunk_blocks + MCRX_TILE - 1) / MCRX_TILE * MCRX_TILE : nblocks;
+    size_t chunk = q->cfg.chunk_blocks ? ((size_t)q->cfg.chunk_blocks + MCRX_TILE - 1) / MCRX_TILE * MCRX_TILE : nblocks;
     const char *x = static_cast<const char *>(d_iq);
     for (size_t b = 0; b < nblocks; b += chunk) {
         const size_t nb = std::min(chunk, nblocks - b);
@@ -1500,7 +1466,7 @@ static int collect(mcrx_hip_t q, int g)
     const uint32_t n = std::min(cnt[0], q->max_rec);
     if (used[0] > q->arena_cap) used[0] = q->arena_cap;
     if (used[1] > q->sarena_cap) used[1] = q->sarena_cap;
-    const bool want_syms = !(q->cfg.struct_size >= offsetof(mcrx_hip_config, skip_framesyms) + sizeof(uint32_t) && q->cfg.skip_framesyms);
+    const bool want_syms = !q->cfg.skip_framesyms;
     if (n) {
         // drop frames already delivered, then append
         if (q->next_frame == q->recs.size()) { q->recs.clear(); q->arena_host.clear(); q->sarena_host.clear(); q->next_frame = 0; }
@@ -1730,11 +1696,8 @@ extern "C" int mcrx_hip_reset_at(mcrx_hip_t q, uint64_t chan_position)
 // ---------------------------------------------------------------- channel monitor: C-ABI
 extern "C" int mcrx_hip_monitor_enable(mcrx_hip_t q, const mcrx_hip_monitor_config *cfg)
 {
-    uint32_t nfft = 64, window = 0;
-    if (cfg) {
-        if (cfg->struct_size >= offsetof(mcrx_hip_monitor_config, nfft) + sizeof(uint32_t) && cfg->nfft) nfft = cfg->nfft;
-        if (cfg->struct_size >= offsetof(mcrx_hip_monitor_config, window) + sizeof(uint32_t)) window = cfg->window;
-    }
+    const mcrx_hip_monitor_config ec = effective_monitor_config(cfg);
+    const uint32_t nfft = ec.nfft ? ec.nfft : 64, window = ec.window;
     if (nfft != 16 && nfft != 32 && nfft != 64 && nfft != 128 && nfft != 256) return fail(MCRX_EINVAL, "monitor: nfft must be 16, 32, 64, 128 or 256");
     if (window > 2) return fail(MCRX_EINVAL, "monitor: window must be 0 (rectangular), 1 (Hann) or 2 (Hamming)");
     if (!q) return fail(MCRX_EINVAL, "null handle");
