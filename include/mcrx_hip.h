@@ -275,7 +275,8 @@ int  mcrx_hip_selftest_device_table(void);             /* the once-per-device bo
  *      (rate > 1: msresamp_crcf_create(2.0, 60), src/flexframe_tx.cc:170) -------------
  * Replaces msresamp_crcf_create(rate, As) / _execute / _destroy as the reference applications
  * call it in front of a synchronizer (src/flexframe_rx.cc:179,240,275; rate computed as in
- * src/multichannel_rx.cc:129-138).  Buffers are device pointers (cf32).  `stream` is a hipStream_t; NULL = the legacy
+ * src/multichannel_rx.cc:129-138).  Buffers are device pointers: the output is cf32, the input cf32 or -- on a handle set to it,
+ * msresamp_hip_set_input_format -- sc16.  `stream` is a hipStream_t; NULL = the legacy
  * default stream (so a receiver handle fed next, which orders against that stream, sees the samples written). */
 typedef struct msresamp_hip_s *msresamp_hip_t;
 int    msresamp_hip_create(msresamp_hip_t *out, float rate, float As);
@@ -290,6 +291,32 @@ float  msresamp_hip_get_delay(msresamp_hip_t q);
 size_t msresamp_hip_max_output(msresamp_hip_t q, size_t nin);
 int    msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out,
                                    size_t out_cap, size_t *nout, void *stream);
+/* Input format of the handle: 0 = cf32 (interleaved float re, im; the default), 1 = sc16 (interleaved int16 re, im, what radios
+ * deliver: 4 bytes a sample, one 32-bit word with re in the low half -- the receiver's input_format = 1).  An sc16 sample (re, im) MEANS
+ * (re * 2^-15, im * 2^-15) -- exact in fp32 for every int16, -32768 included -- and the first stage converts it where it stages its
+ * input, so an sc16 handle gives bit for bit what a cf32 handle gives on those floats, fed in the same pieces, while the largest stream
+ * the resampler reads is half the bytes.  (UHD's own sc16 -> fc32 converter scales by 1 / 32767: the 3e-5 difference in gain is the
+ * caller's business.)  Everything behind the first stage, the output included, stays cf32; reset_at, get_delay, max_output and the
+ * periodic phase arithmetic do not depend on the format.
+ * The format belongs to the handle: msresamp_hip_execute_device_sc16 takes nin sc16 samples = 2 * nin int16 and is otherwise
+ * msresamp_hip_execute_device (*nout, out_cap, stream); a call of the other format's kind returns MCRX_EINVAL, consumes nothing and
+ * leaves the state untouched.  msresamp_hip_set_input_format: MCRX_EINVAL for a null handle or any other value; MCRX_EBUSY while the
+ * handle holds input history (its retained input samples are in the old format) -- allowed on a new handle and directly after
+ * msresamp_hip_reset / _reset_at.
+ * Alignment: d_in needs the alignment of one sample only -- 8 bytes for cf32, 4 bytes for sc16.  (Rates below 1/2 fetch an (even, odd)
+ * pair of samples per lane as one vector where the pair's address allows it, 16 bytes for cf32 and 8 for sc16, and sample by sample
+ * where it does not: a 16- / 8-byte aligned buffer fed in even-sized pieces stays on the vector path.)
+ * Out of scope: sc16 OUTPUT (the transmit applications' msresamp(2.0) -> radio: that needs a gain convention and a clip counter like
+ * mctx_hip_clipped), a host-memory entry point, the C++ classes (std::complex<float> only) and the multi-GPU pipeline. */
+int      msresamp_hip_set_input_format(msresamp_hip_t q, unsigned format);
+unsigned msresamp_hip_input_format(msresamp_hip_t q);                               /* 0 for a null handle */
+int      msresamp_hip_execute_device_sc16(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out,
+                                          size_t out_cap, size_t *nout, void *stream);
+/* Measurement aid: with `enable` set, every following execute call records HIP events around the launch of its first stage -- the
+ * one kernel that reads the caller's samples -- and msresamp_hip_first_stage_ms returns the time between them for the last such call
+ * (it waits for that kernel; MCRX_EINVAL when none has been timed).  Off by default: no events, no cost. */
+int      msresamp_hip_time_first_stage(msresamp_hip_t q, int enable);
+int      msresamp_hip_first_stage_ms(msresamp_hip_t q, float *ms);
 const char *msresamp_hip_last_error(void);
 
 /* ---- alternate front end: 2x-oversampled analysis bank --------------------------------

@@ -110,6 +110,12 @@ _EXPORTS = {
     "msresamp_hip_max_output": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "msresamp_hip_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                               C.POINTER(C.c_size_t), C.c_void_p]),
+    "msresamp_hip_set_input_format": (C.c_int, [C.c_void_p, C.c_uint]),
+    "msresamp_hip_input_format": (C.c_uint, [C.c_void_p]),
+    "msresamp_hip_execute_device_sc16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.POINTER(C.c_size_t), C.c_void_p]),
+    "msresamp_hip_time_first_stage": (C.c_int, [C.c_void_p, C.c_int]),
+    "msresamp_hip_first_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "msresamp_hip_last_error": (C.c_char_p, []),
     "mcrx_hip_pfb2_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint, C.c_uint, C.c_float]),
     "mcrx_hip_pfb2_destroy": (C.c_int, [C.c_void_p]),
@@ -531,10 +537,19 @@ class msresamp(object):
     """GPU mirror of liquid's msresamp_crcf as the reference front ends use it
     (src/flexframe_rx.cc:179,240): msresamp(rate, As); execute(x) -> y, with x / y torch
     complex64 CUDA tensors (IQ stays in HBM).  rate <= 1 decimates (receive front ends), rate > 1 interpolates
-    (the transmit applications' msresamp_crcf_create(2.0, 60), src/flexframe_tx.cc:170)."""
+    (the transmit applications' msresamp_crcf_create(2.0, 60), src/flexframe_tx.cc:170).
+    input_format="sc16" (or 1) makes a resampler of 16-bit integer IQ: execute then takes a torch int16 CUDA tensor of interleaved
+    (re, im) pairs, a sample meaning (re, im) * 2^-15, and returns complex64 as before -- bit for bit what a cf32 handle returns on
+    those floats."""
 
-    def __init__(self, rate, As=60.0):
+    def __init__(self, rate, As=60.0, input_format="cf32"):
         self._h = C.c_void_p()
+        if isinstance(input_format, str):
+            if input_format not in INPUT_FORMATS:
+                raise ValueError("input_format must be one of %s" % sorted(INPUT_FORMATS))
+            input_format = INPUT_FORMATS[input_format]
+        elif input_format not in INPUT_FORMATS.values():
+            raise ValueError("input_format must be one of %s or %s" % (sorted(INPUT_FORMATS), sorted(INPUT_FORMATS.values())))
         rc = lib().msresamp_hip_create(C.byref(self._h), rate, As)
         if rc != MCRX_OK:
             self._h = C.c_void_p()
@@ -543,6 +558,15 @@ class msresamp(object):
                 raise ValueError(msg)
             raise McrxError("msresamp_hip_create failed (%d): %s" % (rc, msg))
         self.rate = rate
+        if input_format:
+            rc = lib().msresamp_hip_set_input_format(self._h, int(input_format))
+            if rc != MCRX_OK:
+                raise McrxError("msresamp_hip_set_input_format failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
+
+    @property
+    def input_format(self):
+        """0 (cf32) or 1 (sc16): INPUT_FORMATS"""
+        return int(lib().msresamp_hip_input_format(self._h))
 
     def get_delay(self):
         return float(lib().msresamp_hip_get_delay(self._h))
@@ -556,15 +580,45 @@ class msresamp(object):
             raise McrxError("msresamp_hip_reset_at failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
 
     def execute(self, x, stream=None):
+        """x: the new samples, a torch CUDA tensor -- complex64, or on an sc16 resampler int16 of 2 n elements (interleaved re, im;
+        shape (n, 2) is fine).  Returns complex64.  TypeError on a tensor of the other format's dtype."""
         import torch
-        n = int(x.numel())
+        sc16 = self.input_format == INPUT_FORMATS["sc16"]
+        if sc16:
+            if x.dtype != torch.int16:
+                raise TypeError("this resampler takes int16 device tensors (interleaved re, im), not %s" % x.dtype)
+            if not x.is_contiguous():
+                raise ValueError("device samples must be contiguous")
+            if x.numel() % 2:
+                raise ValueError("an sc16 buffer holds (re, im) pairs: odd number of int16")
+            n = int(x.numel()) // 2
+            fn, name = lib().msresamp_hip_execute_device_sc16, "msresamp_hip_execute_device_sc16"
+        else:
+            if x.dtype == torch.int16:
+                raise TypeError("int16 samples need a resampler made with input_format=\"sc16\"")
+            n = int(x.numel())
+            fn, name = lib().msresamp_hip_execute_device, "msresamp_hip_execute_device"
         cap = int(lib().msresamp_hip_max_output(self._h, n)) + 8
         y = torch.empty(cap, dtype=torch.complex64, device=x.device)
         nout = C.c_size_t(0)
-        rc = lib().msresamp_hip_execute_device(self._h, _dptr(x), n, _dptr(y), cap, C.byref(nout), _stream_ptr(stream))
+        rc = fn(self._h, _dptr(x), n, _dptr(y), cap, C.byref(nout), _stream_ptr(stream))
         if rc != MCRX_OK:
-            raise McrxError("msresamp_hip_execute_device failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
+            raise McrxError("%s failed (%d): %s" % (name, rc, lib().msresamp_hip_last_error().decode()))
         return y[:nout.value]
+
+    def time_first_stage(self, enable=True):
+        """Measurement aid (msresamp_hip_time_first_stage): time the kernel that reads the caller's samples, call by call."""
+        rc = lib().msresamp_hip_time_first_stage(self._h, int(bool(enable)))
+        if rc != MCRX_OK:
+            raise McrxError("msresamp_hip_time_first_stage failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
+
+    def first_stage_ms(self):
+        """Milliseconds the first stage of the last timed execute took on the device (waits for it)."""
+        ms = C.c_float(0)
+        rc = lib().msresamp_hip_first_stage_ms(self._h, C.byref(ms))
+        if rc != MCRX_OK:
+            raise McrxError("msresamp_hip_first_stage_ms failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
+        return float(ms.value)
 
     def close(self):
         if self._h:

@@ -39,21 +39,43 @@ using namespace mcrx;
 #define RS_OB 1024                  // outputs per workgroup (256 threads x 4)
 #define RS_HROW 16                  // floats per row of the padded branch table (14 taps + 2): one row = 4 x 16-B loads
 
+// Input formats of the caller's buffer (template parameter FMT of the kernels that can be a first stage; msresamp_hip_set_input_format).
+// An sc16 sample is one 32-bit word, int16 re in the low half and int16 im in the high half -- the word channelizer.hip reads -- and
+// means (re, im) * 2^-15: conversion and scaling are exact in fp32 for every int16.  The word stays packed from the load to the store
+// into the LDS span (rs_cvt), half the bytes and half the registers of a cf32 sample in flight; behind that store the source is the
+// cf32 build's, so that the two formats share every later rounding.  Only the caller's buffer and its retained tail (in[0]) are in
+// the handle's format: every later stage buffer is cf32.
+#define RS_IN_CF32 0
+#define RS_IN_SC16 1
+template <int FMT> struct RsElem { typedef float2 type; };
+template <> struct RsElem<RS_IN_SC16> { typedef uint32_t type; };
+
 // A stage input: samples [tail_base, cur_base) in `tail` (the retained end of the previous call's input, may be NULL),
 // [cur_base, end) in `cur`; everything before sample 0 is zero.
-struct RsIn { const float2 *tail; long long tail_base; const float2 *cur; long long cur_base, end; };
+template <int FMT> struct RsInT { const typename RsElem<FMT>::type *tail; long long tail_base; const typename RsElem<FMT>::type *cur; long long cur_base, end; };
+typedef RsInT<RS_IN_CF32> RsIn;
 
-__device__ __forceinline__ float2 rs_fetch(const RsIn &s, long long t)
+__device__ __forceinline__ float2 rs_cvt(float2 v) { return v; }
+__device__ __forceinline__ float2 rs_cvt(uint32_t w) { return make_float2((float)(int16_t)(w & 0xffffu) * 0x1p-15f, (float)((int32_t)w >> 16) * 0x1p-15f); }
+template <int FMT> __device__ __forceinline__ typename RsElem<FMT>::type rs_zero()
 {
-    if (t >= s.cur_base) return t < s.end ? s.cur[t - s.cur_base] : make_float2(0.f, 0.f);
+    if constexpr (FMT == RS_IN_SC16) return 0u; else return make_float2(0.f, 0.f);
+}
+
+// sample t as it lies in memory (sc16: the packed word; the zero word is the zero sample)
+template <int FMT> __device__ __forceinline__ typename RsElem<FMT>::type rs_fetch(const RsInT<FMT> &s, long long t)
+{
+    if (t >= s.cur_base) return t < s.end ? s.cur[t - s.cur_base] : rs_zero<FMT>();
     if (s.tail && t >= s.tail_base && t >= 0) return s.tail[t - s.tail_base];
-    return make_float2(0.f, 0.f);
+    return rs_zero<FMT>();
 }
 
 // Half-band decimator, outputs k in [k0, k1) -> out[k - k0].  A workgroup stages the 2 x (1024 + 13) input samples of
 // its 1024 outputs in LDS, de-interleaved (the filter branch reads even samples, the delay branch odd ones), with
-// coalesced loads; every thread then makes 4 outputs from conflict-free LDS reads.  HBM: 8 B in + 4 B out per input sample.
-__global__ __launch_bounds__(256) void halfband_kernel(RsIn in, float2 *out, long long k0, long long k1, const float *h1)
+// coalesced loads; every thread then makes 4 outputs from conflict-free LDS reads.  HBM: 8 B in + 4 B out per input sample
+// (4 B in where it is the first stage of an sc16 handle: FMT, converted on the way into LDS).
+template <int FMT>
+__global__ __launch_bounds__(256) void halfband_kernel(RsInT<FMT> in, float2 *out, long long k0, long long k1, const float *h1)
 {
     __shared__ float2 ev[RS_OB + RS_TAPS], od[RS_OB + RS_TAPS];
     const long long kb = k0 + (long long)blockIdx.x * RS_OB;
@@ -61,8 +83,8 @@ __global__ __launch_bounds__(256) void halfband_kernel(RsIn in, float2 *out, lon
     const long long tb = 2 * (kb - (RS_TAPS - 1));          // sample behind ev[0]
     const int np = (int)min((long long)RS_OB, k1 - kb) + RS_TAPS - 1;
     for (int p = tid; p < np; p += 256) {
-        ev[p] = rs_fetch(in, tb + 2 * p);
-        od[p] = rs_fetch(in, tb + 2 * p + 1);
+        ev[p] = rs_cvt(rs_fetch(in, tb + 2 * p));
+        od[p] = rs_cvt(rs_fetch(in, tb + 2 * p + 1));
     }
     __syncthreads();
     float h[RS_TAPS];
@@ -125,8 +147,8 @@ __global__ __launch_bounds__(256) void halfband_interp_kernel(RsIn in, float2 *o
 // for 11 algorithmic ones.  Chunks of 512 outputs there (the raw span is twice the half-band span), 40 KB of LDS.
 #define RS_CHUNKS 8
 #define RS_HT_ROW (RS_NPFB + RS_NPFB / 32)
-template <bool FIXED, bool HB>
-__global__ __launch_bounds__(256) void arbitrary_kernel(RsIn in, float2 *out, long long j0, long long j1,
+template <bool FIXED, bool HB, int FMT>
+__global__ __launch_bounds__(256) void arbitrary_kernel(RsInT<FMT> in, float2 *out, long long j0, long long j1,
                                                         unsigned long long step, const float *hpfb, const float *h1)
 {
     constexpr int RS_OBK = HB ? RS_OB / 2 : RS_OB;          // outputs per chunk
@@ -170,34 +192,49 @@ __global__ __launch_bounds__(256) void arbitrary_kernel(RsIn in, float2 *out, lo
         np = (int)(nl - nf) + RS_TAPS;
         return true;
     };
-    float2 pre[RS_PER], pro[HB ? RS_PER : 1];
+    typedef typename RsElem<FMT>::type elem_t;              // a sample as fetched: it waits in registers in the caller's format
+    elem_t pre[RS_PER], pro[HB ? RS_PER : 1];
     auto fetch = [&](long long nf, int np) {
         if constexpr (HB) {     // y[nf - 13 + p], p < np, read raw pairs q < np + 13 from sample tb = 2 (nf - 26) on
             const long long tb = 2 * (nf - 2 * (RS_TAPS - 1));
             const int nq = np + RS_TAPS - 1;
             // inside the new samples, on a 16-byte boundary (all chunks but a call's first and last, while calls are even-sized): one
             // 16-byte load per (even, odd) pair, whole lines per instruction
-            const bool whole = tb >= in.cur_base && tb + 2 * (long long)nq <= in.end && (((tb - in.cur_base) & 1) == 0) && ((reinterpret_cast<size_t>(in.cur) & 15) == 0);
+            // (sc16: a pair is 8 bytes, and what has to line up is the pair's own address -- a buffer that is only 4-byte aligned takes
+            //  this path whenever tb falls on an odd sample of it)
+            bool whole = tb >= in.cur_base && tb + 2 * (long long)nq <= in.end;
+            if constexpr (FMT == RS_IN_SC16) whole = whole && ((reinterpret_cast<size_t>(in.cur + (tb - in.cur_base)) & 7) == 0);
+            else whole = whole && (((tb - in.cur_base) & 1) == 0) && ((reinterpret_cast<size_t>(in.cur) & 15) == 0);
             if (whole) {
-                const float4 *src = reinterpret_cast<const float4 *>(in.cur + (tb - in.cur_base));
+                if constexpr (FMT == RS_IN_SC16) {
+                    const uint2 *src = reinterpret_cast<const uint2 *>(in.cur + (tb - in.cur_base));
 #pragma unroll
-                for (int i = 0; i < RS_PER; i++) {
-                    const int q = tid + 256 * i;
-                    const float4 v = src[q < nq ? q : 0];
-                    pre[i] = make_float2(v.x, v.y); pro[i] = make_float2(v.z, v.w);
+                    for (int i = 0; i < RS_PER; i++) {
+                        const int q = tid + 256 * i;
+                        const uint2 v = src[q < nq ? q : 0];
+                        pre[i] = v.x; pro[i] = v.y;
+                    }
+                } else {
+                    const float4 *src = reinterpret_cast<const float4 *>(in.cur + (tb - in.cur_base));
+#pragma unroll
+                    for (int i = 0; i < RS_PER; i++) {
+                        const int q = tid + 256 * i;
+                        const float4 v = src[q < nq ? q : 0];
+                        pre[i] = make_float2(v.x, v.y); pro[i] = make_float2(v.z, v.w);
+                    }
                 }
             } else {
 #pragma unroll
                 for (int i = 0; i < RS_PER; i++) {
                     const int q = tid + 256 * i;
                     const bool on = q < nq;
-                    pre[i] = on ? rs_fetch(in, tb + 2 * q) : make_float2(0.f, 0.f);
-                    pro[i] = on ? rs_fetch(in, tb + 2 * q + 1) : make_float2(0.f, 0.f);
+                    pre[i] = on ? rs_fetch(in, tb + 2 * q) : rs_zero<FMT>();
+                    pro[i] = on ? rs_fetch(in, tb + 2 * q + 1) : rs_zero<FMT>();
                 }
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < RS_PER; i++) { const int p = tid + 256 * i; pre[i] = p < np ? rs_fetch(in, nf - (RS_TAPS - 1) + p) : make_float2(0.f, 0.f); }
+            for (int i = 0; i < RS_PER; i++) { const int p = tid + 256 * i; pre[i] = p < np ? rs_fetch(in, nf - (RS_TAPS - 1) + p) : rs_zero<FMT>(); }
         }
     };
     long long jb, je, nf; int np;
@@ -207,10 +244,10 @@ __global__ __launch_bounds__(256) void arbitrary_kernel(RsIn in, float2 *out, lo
         __syncthreads();                                     // (the previous chunk's reads of x; the table's writes)
         if constexpr (HB) {
 #pragma unroll
-            for (int i = 0; i < RS_PER; i++) { const int q = tid + 256 * i; if (q < np + RS_TAPS - 1) { ev[q] = pre[i]; od[q] = pro[i]; } }
+            for (int i = 0; i < RS_PER; i++) { const int q = tid + 256 * i; if (q < np + RS_TAPS - 1) { ev[q] = rs_cvt(pre[i]); od[q] = rs_cvt(pro[i]); } }
         } else {
 #pragma unroll
-            for (int i = 0; i < RS_PER; i++) { const int p = tid + 256 * i; if (p < np) x[p] = pre[i]; }
+            for (int i = 0; i < RS_PER; i++) { const int p = tid + 256 * i; if (p < np) x[p] = rs_cvt(pre[i]); }
         }
         __syncthreads();
         const long long cjb = jb, cje = je, cnf = nf;
@@ -260,25 +297,27 @@ __global__ __launch_bounds__(256) void arbitrary_kernel(RsIn in, float2 *out, lo
 // (FIXED needs the branch of output j to depend on j mod 256 only, and a thread's outputs to share it: the step's low 16 bits clear)
 static inline bool rs_fixed_rate(unsigned long long step) { return (step & 0xFFFFull) == 0; }
 // h1 != nullptr: `in` is the input of the last half-band decimator, folded into the launch (arbitrary_kernel, HB)
-static inline void rs_launch_arbitrary(const RsIn &in, float2 *out, long long j0, long long j1, unsigned long long step, const float *hpfb, hipStream_t st,
+template <int FMT>
+static inline void rs_launch_arbitrary(const RsInT<FMT> &in, float2 *out, long long j0, long long j1, unsigned long long step, const float *hpfb, hipStream_t st,
                                        const float *h1 = nullptr)
 {
     const unsigned n = (unsigned)(j1 - j0), ob = h1 ? RS_OB / 2 : RS_OB, grid = (n + ob * RS_CHUNKS - 1) / (ob * RS_CHUNKS);
     if (h1) {
-        if (rs_fixed_rate(step)) hipLaunchKernelGGL((arbitrary_kernel<true, true>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
-        else hipLaunchKernelGGL((arbitrary_kernel<false, true>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
+        if (rs_fixed_rate(step)) hipLaunchKernelGGL((arbitrary_kernel<true, true, FMT>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
+        else hipLaunchKernelGGL((arbitrary_kernel<false, true, FMT>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
     } else {
-        if (rs_fixed_rate(step)) hipLaunchKernelGGL((arbitrary_kernel<true, false>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
-        else hipLaunchKernelGGL((arbitrary_kernel<false, false>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
+        if (rs_fixed_rate(step)) hipLaunchKernelGGL((arbitrary_kernel<true, false, FMT>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
+        else hipLaunchKernelGGL((arbitrary_kernel<false, false, FMT>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
     }
 }
 
 // the last RS_KEEP samples of a two-segment input become the next call's tail (one workgroup, staged through registers
-// because source and destination may overlap)
-__global__ void tail_save_kernel(RsIn in, float2 *tail, long long new_base)
+// because source and destination may overlap).  The tail stays in the format of the input: sc16 words are copied as they are.
+template <int FMT>
+__global__ void tail_save_kernel(RsInT<FMT> in, typename RsElem<FMT>::type *tail, long long new_base)
 {
     const int i = threadIdx.x;
-    const float2 v = rs_fetch(in, new_base + i);
+    const typename RsElem<FMT>::type v = rs_fetch(in, new_base + i);
     __syncthreads();
     if (new_base + i < in.end) tail[i] = v;
 }
@@ -303,6 +342,16 @@ struct msresamp_hip_s {
     long long out_count = 0;        // outputs of the arbitrary stage produced so far (j), less the whole periods taken off by rs_rebase
     long long per_in = 1, per_out = 1;      // one period of the phase: step / g inputs, 2^24 / g outputs of the arbitrary stage
     hipStream_t stream = nullptr;
+    unsigned in_fmt = RS_IN_CF32;   // format of the caller's samples and of in[0], their retained tail (msresamp_hip_set_input_format)
+    hipEvent_t ev_first[2] = { nullptr, nullptr };      // msresamp_hip_time_first_stage: around the launch that reads the caller's samples
+    bool time_first = false, timed_first = false;
+};
+
+// events around the first stage's launch (the kernel that reads the caller's buffer), when the handle is asked to time it
+struct FirstStageTimer {
+    msresamp_hip_s *q; hipStream_t st;
+    FirstStageTimer(msresamp_hip_s *q_, hipStream_t st_) : q(q_), st(st_) { if (q->time_first) (void)hipEventRecord(q->ev_first[0], st); }
+    ~FirstStageTimer() { if (q->time_first) { (void)hipEventRecord(q->ev_first[1], st); q->timed_first = true; } }
 };
 
 static int stage_reserve(msresamp_hip_t q, StageBuf &b, size_t extra, hipStream_t st)
@@ -314,7 +363,7 @@ static int stage_reserve(msresamp_hip_t q, StageBuf &b, size_t extra, hipStream_
     if (keep + extra <= b.cap) {                        // slide the tail to the front (stream ordered, no allocation)
         if (keep) {
             const RsIn me = { nullptr, 0, b.d, b.base, b.end };
-            hipLaunchKernelGGL(tail_save_kernel, dim3(1), dim3(RS_KEEP), 0, st, me, b.d, b.end - (long long)keep);
+            hipLaunchKernelGGL(tail_save_kernel<RS_IN_CF32>, dim3(1), dim3(RS_KEEP), 0, st, me, b.d, b.end - (long long)keep);
             RSCHK(hipGetLastError());
         }
         b.base = b.end - (long long)keep;
@@ -406,6 +455,7 @@ extern "C" int msresamp_hip_destroy(msresamp_hip_t q)
     for (auto &b : q->in) if (b.d) (void)hipFree(b.d);
     (void)hipFree(q->d_h1); (void)hipFree(q->d_hpfb);
     if (q->stream) (void)hipStreamDestroy(q->stream);
+    for (hipEvent_t e : q->ev_first) if (e) (void)hipEventDestroy(e);
     delete q;
     return MCRX_OK;
 }
@@ -442,12 +492,52 @@ extern "C" float msresamp_hip_get_delay(msresamp_hip_t q)
 extern "C" size_t msresamp_hip_max_output(msresamp_hip_t q, size_t nin)
 { return q ? (size_t)((double)nin * q->rate * 1.0001) + (q->interp ? (4u << q->num_stages) : 4) : 0; }
 
-// d_in: nin new input samples in device memory; d_out receives *nout <= out_cap samples
-extern "C" int msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out,
-                                           size_t out_cap, size_t *nout, void *stream)
+// The format of the caller's samples belongs to the handle.  It may change only while in[0] is empty -- a new handle, or directly after
+// a reset -- because the retained tail is in the old format otherwise.
+extern "C" int msresamp_hip_set_input_format(msresamp_hip_t q, unsigned format)
+{
+    if (!q) { g_rs_err = "null argument"; return MCRX_EINVAL; }
+    if (format != RS_IN_CF32 && format != RS_IN_SC16) { g_rs_err = "msresamp: input format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
+    if (q->in[0].end > q->in[0].base) { g_rs_err = "msresamp: the input format cannot change while the handle holds input history (reset first)"; return MCRX_EBUSY; }
+    q->in_fmt = format;
+    return MCRX_OK;
+}
+
+extern "C" unsigned msresamp_hip_input_format(msresamp_hip_t q) { return q ? q->in_fmt : 0; }
+
+// Measurement aid (bench_resamp_sc16.py): HIP events around the first stage's launch of every following execute call.
+extern "C" int msresamp_hip_time_first_stage(msresamp_hip_t q, int enable)
 {
     DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_rs_err = "null argument"; return MCRX_EINVAL; }
+    if (enable) for (hipEvent_t &e : q->ev_first) if (!e) RSCHK(hipEventCreate(&e));
+    q->time_first = enable != 0; q->timed_first = false;
+    return MCRX_OK;
+}
+
+// ... and the time between them for the last such call (waits for it).  MCRX_EINVAL when no first stage has been timed.
+extern "C" int msresamp_hip_first_stage_ms(msresamp_hip_t q, float *ms)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q || !ms) { g_rs_err = "null argument"; return MCRX_EINVAL; }
+    if (!q->timed_first) { g_rs_err = "msresamp: no first stage has been timed (msresamp_hip_time_first_stage)"; return MCRX_EINVAL; }
+    RSCHK(hipEventSynchronize(q->ev_first[1]));
+    RSCHK(hipEventElapsedTime(ms, q->ev_first[0], q->ev_first[1]));
+    return MCRX_OK;
+}
+
+// d_in: nin new input samples in device memory, in format FMT; d_out receives *nout <= out_cap samples (cf32)
+template <int FMT>
+static int rs_execute(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out, size_t out_cap, size_t *nout, void *stream)
+{
+    typedef typename RsElem<FMT>::type elem_t;
+    DevScope dev_scope_(q ? q->device : -1);
     if (!q || !nout || (!d_in && nin) || !d_out) { g_rs_err = "null argument"; return MCRX_EINVAL; }
+    if (q->in_fmt != (unsigned)FMT) {       // (before anything is counted: the call consumes nothing)
+        g_rs_err = FMT == RS_IN_SC16 ? "msresamp: input format mismatch, an sc16 call on a cf32 handle (msresamp_hip_set_input_format)"
+                                     : "msresamp: input format mismatch, a cf32 call on an sc16 handle (msresamp_hip_execute_device_sc16)";
+        return MCRX_EINVAL;
+    }
     // NULL = the legacy default stream, like the other stage operators: what a caller enqueues next -- on that stream or on a
     // receiver handle's own (blocking) streams -- is ordered behind the resampler's kernels.  (A private stream here left
     // msresamp -> multichannelrx chains on the default stream unordered: the bank could read samples not yet written.)
@@ -457,13 +547,13 @@ extern "C" int msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, s
     // the first stage reads [retained tail | the caller's new samples]; nothing is copied
     StageBuf &b0 = q->in[0];
     int rc;
-    if (!b0.d) { RSCHK(hipMalloc((void **)&b0.d, RS_KEEP * sizeof(float2))); b0.cap = RS_KEEP; }
+    if (!b0.d) { RSCHK(hipMalloc((void **)&b0.d, RS_KEEP * sizeof(float2))); b0.cap = RS_KEEP; }    // (room for either format)
     const long long end0 = b0.end + (long long)nin;
-    const RsIn src0 = { b0.end > b0.base ? b0.d : nullptr, b0.base, (const float2 *)d_in, b0.end, end0 };
+    const RsInT<FMT> src0 = { b0.end > b0.base ? (const elem_t *)b0.d : nullptr, b0.base, (const elem_t *)d_in, b0.end, end0 };
     auto keep_tail = [&]() -> int {
         const long long nb = std::max(b0.base, end0 - (long long)RS_KEEP);
         if (end0 > nb) {
-            hipLaunchKernelGGL(tail_save_kernel, dim3(1), dim3(RS_KEEP), 0, st, src0, b0.d, nb);
+            hipLaunchKernelGGL(tail_save_kernel<FMT>, dim3(1), dim3(RS_KEEP), 0, st, src0, (elem_t *)b0.d, nb);
             RSCHK(hipGetLastError());
         }
         b0.base = nb; b0.end = end0;
@@ -486,6 +576,7 @@ extern "C" int msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, s
             b1.end += j1 - j0;
         }
         if (j1 > j0) {
+            FirstStageTimer timer(q, st);
             rs_launch_arbitrary(src0, dst, j0, j1, q->step, q->d_hpfb, st);
             RSCHK(hipGetLastError());
         }
@@ -525,8 +616,9 @@ extern "C" int msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, s
         if (k1 > k0) {
             if ((rc = stage_reserve(q, bo, (size_t)(k1 - k0), st))) return rc;
             const unsigned n = (unsigned)(k1 - k0);
-            hipLaunchKernelGGL(halfband_kernel, dim3((n + OB - 1) / OB), dim3(256), 0, st,
-                               s ? stage_in(q->in[s]) : src0, bo.d + (bo.end - bo.base), k0, k1, q->d_h1);
+            float2 *o = bo.d + (bo.end - bo.base);
+            if (s) hipLaunchKernelGGL(halfband_kernel<RS_IN_CF32>, dim3((n + OB - 1) / OB), dim3(256), 0, st, stage_in(q->in[s]), o, k0, k1, q->d_h1);
+            else { FirstStageTimer timer(q, st); hipLaunchKernelGGL(halfband_kernel<FMT>, dim3((n + OB - 1) / OB), dim3(256), 0, st, src0, o, k0, k1, q->d_h1); }
             RSCHK(hipGetLastError());
             bo.end = k1;
         }
@@ -541,8 +633,12 @@ extern "C" int msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, s
     if ((size_t)(j1 - j0) > out_cap) { g_rs_err = "output buffer too small"; return MCRX_EINVAL; }
     if (j1 > j0) {
         const unsigned ns = q->num_stages;
-        if (ns) rs_launch_arbitrary(ns > 1 ? stage_in(q->in[ns - 1]) : src0, (float2 *)d_out, j0, j1, q->step, q->d_hpfb, st, q->d_h1);
-        else rs_launch_arbitrary(src0, (float2 *)d_out, j0, j1, q->step, q->d_hpfb, st);
+        if (ns > 1) rs_launch_arbitrary(stage_in(q->in[ns - 1]), (float2 *)d_out, j0, j1, q->step, q->d_hpfb, st, q->d_h1);
+        else {
+            FirstStageTimer timer(q, st);
+            if (ns) rs_launch_arbitrary(src0, (float2 *)d_out, j0, j1, q->step, q->d_hpfb, st, q->d_h1);
+            else rs_launch_arbitrary(src0, (float2 *)d_out, j0, j1, q->step, q->d_hpfb, st);
+        }
         RSCHK(hipGetLastError());
     }
     q->out_count = j1;
@@ -550,5 +646,14 @@ extern "C" int msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, s
     *nout = (size_t)(j1 - j0);
     return MCRX_OK;
 }
+
+extern "C" int msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out,
+                                           size_t out_cap, size_t *nout, void *stream)
+{ return rs_execute<RS_IN_CF32>(q, d_in, nin, d_out, out_cap, nout, stream); }
+
+// the same for a handle whose input format is sc16: nin samples = 2 * nin int16 (any 4-byte-aligned d_in)
+extern "C" int msresamp_hip_execute_device_sc16(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out,
+                                                size_t out_cap, size_t *nout, void *stream)
+{ return rs_execute<RS_IN_SC16>(q, d_in, nin, d_out, out_cap, nout, stream); }
 
 extern "C" const char *msresamp_hip_last_error(void) { return g_rs_err.c_str(); }
