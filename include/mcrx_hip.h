@@ -275,8 +275,8 @@ int  mcrx_hip_selftest_device_table(void);             /* the once-per-device bo
  *      (rate > 1: msresamp_crcf_create(2.0, 60), src/flexframe_tx.cc:170) -------------
  * Replaces msresamp_crcf_create(rate, As) / _execute / _destroy as the reference applications
  * call it in front of a synchronizer (src/flexframe_rx.cc:179,240,275; rate computed as in
- * src/multichannel_rx.cc:129-138).  Buffers are device pointers: the output is cf32, the input cf32 or -- on a handle set to it,
- * msresamp_hip_set_input_format -- sc16.  `stream` is a hipStream_t; NULL = the legacy
+ * src/multichannel_rx.cc:129-138).  Buffers are device pointers: input and output are cf32 or -- on a handle set to it,
+ * msresamp_hip_set_input_format / msresamp_hip_set_output_format -- sc16.  `stream` is a hipStream_t; NULL = the legacy
  * default stream (so a receiver handle fed next, which orders against that stream, sees the samples written). */
 typedef struct msresamp_hip_s *msresamp_hip_t;
 int    msresamp_hip_create(msresamp_hip_t *out, float rate, float As);
@@ -296,8 +296,8 @@ int    msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, size_t ni
  * (re * 2^-15, im * 2^-15) -- exact in fp32 for every int16, -32768 included -- and the first stage converts it where it stages its
  * input, so an sc16 handle gives bit for bit what a cf32 handle gives on those floats, fed in the same pieces, while the largest stream
  * the resampler reads is half the bytes.  (UHD's own sc16 -> fc32 converter scales by 1 / 32767: the 3e-5 difference in gain is the
- * caller's business.)  Everything behind the first stage, the output included, stays cf32; reset_at, get_delay, max_output and the
- * periodic phase arithmetic do not depend on the format.
+ * caller's business.)  Everything behind the first stage stays cf32, up to the store of the output (below); reset_at, get_delay,
+ * max_output and the periodic phase arithmetic do not depend on the format.
  * The format belongs to the handle: msresamp_hip_execute_device_sc16 takes nin sc16 samples = 2 * nin int16 and is otherwise
  * msresamp_hip_execute_device (*nout, out_cap, stream); a call of the other format's kind returns MCRX_EINVAL, consumes nothing and
  * leaves the state untouched.  msresamp_hip_set_input_format: MCRX_EINVAL for a null handle or any other value; MCRX_EBUSY while the
@@ -306,12 +306,38 @@ int    msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, size_t ni
  * Alignment: d_in needs the alignment of one sample only -- 8 bytes for cf32, 4 bytes for sc16.  (Rates below 1/2 fetch an (even, odd)
  * pair of samples per lane as one vector where the pair's address allows it, 16 bytes for cf32 and 8 for sc16, and sample by sample
  * where it does not: a 16- / 8-byte aligned buffer fed in even-sized pieces stays on the vector path.)
- * Out of scope: sc16 OUTPUT (the transmit applications' msresamp(2.0) -> radio: that needs a gain convention and a clip counter like
- * mctx_hip_clipped), a host-memory entry point, the C++ classes (std::complex<float> only) and the multi-GPU pipeline. */
+ * Out of scope for both sc16 sides: a host-memory entry point, the C++ classes (std::complex<float> only) and the multi-GPU pipeline. */
 int      msresamp_hip_set_input_format(msresamp_hip_t q, unsigned format);
 unsigned msresamp_hip_input_format(msresamp_hip_t q);                               /* 0 for a null handle */
 int      msresamp_hip_execute_device_sc16(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out,
                                           size_t out_cap, size_t *nout, void *stream);
+/* Output gain and output format of the handle (the transmit applications' msresamp(2.0) -> g * y -> radio, src/flexframe_tx.cc:170-243).
+ * Let y be the fp32 value the resampler computes for one component of an output sample.  A handle has an output gain g (default 1) and
+ * stores v = y * g: one fp32 multiply of its own, nothing fused into it; with g = 1 the output is y, word for word.  Output format
+ * 0 = cf32 stores v (the default); 1 = sc16 stores Q(v), the transmitter's quantiser (mctx_hip_set_output_format):
+ *   Q(v) = clamp(rint(v * 32768.0f), -32768, 32767)      round half to even, in fp32; NaN stores 0, infinities saturate
+ * as interleaved int16 re, im -- 4 bytes a sample, the word input_format = 1 reads, with no scale factor in between.  The integers are
+ * a function of the cf32 output alone.  A sample is CLIPPED when the rounded value of its re or its im lies outside the int16 range
+ * (NaN does not count).
+ * There are no new execute entry points: msresamp_hip_execute_device and _execute_device_sc16 (that name refers to the INPUT) write
+ * *nout samples to d_out in the handle's output format; out_cap and *nout count samples in both formats, and msresamp_hip_max_output,
+ * get_delay, reset_at and the periodic phase arithmetic do not change.
+ * msresamp_hip_set_output_format: MCRX_EINVAL for a null handle or a value other than 0 and 1.  msresamp_hip_set_output_gain:
+ * MCRX_EINVAL for a null handle or a gain that is not finite; the gain applies to both output formats.  No output state is retained
+ * between calls -- every buffer between the stages is an input buffer and stays cf32, only the store to d_out knows format and gain --
+ * so both may change between any two calls, in mid-stream too: there is no MCRX_EBUSY case.  The getters return 0 for a null handle.
+ * msresamp_hip_clipped: *samples = the samples clipped by sc16-output calls since the count was last reset (reset = 1 starts a new
+ * count; samples may be NULL) -- mctx_hip_clipped's semantics: a 64-bit device counter and an event recorded on the caller's stream
+ * behind every sc16-output call, and the read waits for that event only.  Always 0 on a handle that never wrote sc16.  Counter and
+ * event are allocated when sc16 output is first selected; a handle that never selects it allocates nothing.
+ * Alignment of d_out: for sc16 that of one sample, 4 bytes (MCRX_EINVAL otherwise).  At rates above 2 the last stage writes an
+ * (even, odd) pair of outputs per input: as one 8-byte word where d_out is 8-byte aligned and as two 4-byte stores where it is not,
+ * the same choice for a whole call -- so a caller may append consecutive calls' outputs to one buffer.  cf32 output: as before. */
+int      msresamp_hip_set_output_format(msresamp_hip_t q, unsigned format);
+unsigned msresamp_hip_output_format(msresamp_hip_t q);                              /* 0 for a null handle */
+int      msresamp_hip_set_output_gain(msresamp_hip_t q, float gain);
+float    msresamp_hip_output_gain(msresamp_hip_t q);                                /* 0 for a null handle */
+int      msresamp_hip_clipped(msresamp_hip_t q, uint64_t *samples, int reset);
 /* Measurement aid: with `enable` set, every following execute call records HIP events around the launch of its first stage -- the
  * one kernel that reads the caller's samples -- and msresamp_hip_first_stage_ms returns the time between them for the last such call
  * (it waits for that kernel; MCRX_EINVAL when none has been timed).  Off by default: no events, no cost. */

@@ -10,6 +10,7 @@ raises.  (The CPU oracle under ``oracle/`` is test infrastructure and is never i
 this package.)
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -114,6 +115,11 @@ _EXPORTS = {
     "msresamp_hip_input_format": (C.c_uint, [C.c_void_p]),
     "msresamp_hip_execute_device_sc16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                    C.POINTER(C.c_size_t), C.c_void_p]),
+    "msresamp_hip_set_output_format": (C.c_int, [C.c_void_p, C.c_uint]),
+    "msresamp_hip_output_format": (C.c_uint, [C.c_void_p]),
+    "msresamp_hip_set_output_gain": (C.c_int, [C.c_void_p, C.c_float]),
+    "msresamp_hip_output_gain": (C.c_float, [C.c_void_p]),
+    "msresamp_hip_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
     "msresamp_hip_time_first_stage": (C.c_int, [C.c_void_p, C.c_int]),
     "msresamp_hip_first_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "msresamp_hip_last_error": (C.c_char_p, []),
@@ -540,10 +546,22 @@ class msresamp(object):
     (the transmit applications' msresamp_crcf_create(2.0, 60), src/flexframe_tx.cc:170).
     input_format="sc16" (or 1) makes a resampler of 16-bit integer IQ: execute then takes a torch int16 CUDA tensor of interleaved
     (re, im) pairs, a sample meaning (re, im) * 2^-15, and returns complex64 as before -- bit for bit what a cf32 handle returns on
-    those floats."""
+    those floats.
+    gain (default 1.0) multiplies every output component, one fp32 multiply.  output_format="sc16" (or 1) makes execute return a
+    contiguous torch int16 CUDA tensor of shape (nout, 2), the transmitter's quantiser applied to what a cf32 resampler of the same
+    gain returns (msresamp_hip_set_output_format); clipped() counts the samples that left the int16 range."""
 
-    def __init__(self, rate, As=60.0, input_format="cf32"):
+    def __init__(self, rate, As=60.0, input_format="cf32", output_format="cf32", gain=1.0):
         self._h = C.c_void_p()
+        if isinstance(output_format, str):
+            if output_format not in OUTPUT_FORMATS:
+                raise ValueError("output_format must be one of %s" % sorted(OUTPUT_FORMATS))
+            output_format = OUTPUT_FORMATS[output_format]
+        elif output_format not in OUTPUT_FORMATS.values():
+            raise ValueError("output_format must be one of %s or %s" % (sorted(OUTPUT_FORMATS), sorted(OUTPUT_FORMATS.values())))
+        gain = float(gain)
+        if not math.isfinite(gain):
+            raise ValueError("gain must be finite")
         if isinstance(input_format, str):
             if input_format not in INPUT_FORMATS:
                 raise ValueError("input_format must be one of %s" % sorted(INPUT_FORMATS))
@@ -562,11 +580,49 @@ class msresamp(object):
             rc = lib().msresamp_hip_set_input_format(self._h, int(input_format))
             if rc != MCRX_OK:
                 raise McrxError("msresamp_hip_set_input_format failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
+        if output_format:
+            self.output_format = output_format
+        if gain != 1.0:
+            self.gain = gain
+
+    def _chk(self, rc, name):
+        if rc == MCRX_EINVAL:
+            raise ValueError(lib().msresamp_hip_last_error().decode())
+        if rc != MCRX_OK:
+            raise McrxError("%s failed (%d): %s" % (name, rc, lib().msresamp_hip_last_error().decode()))
 
     @property
     def input_format(self):
         """0 (cf32) or 1 (sc16): INPUT_FORMATS"""
         return int(lib().msresamp_hip_input_format(self._h))
+
+    @property
+    def output_format(self):
+        """0 (cf32) or 1 (sc16): OUTPUT_FORMATS.  May be set between any two execute calls."""
+        return int(lib().msresamp_hip_output_format(self._h))
+
+    @output_format.setter
+    def output_format(self, v):
+        if isinstance(v, str):
+            if v not in OUTPUT_FORMATS:
+                raise ValueError("output_format must be one of %s" % sorted(OUTPUT_FORMATS))
+            v = OUTPUT_FORMATS[v]
+        self._chk(lib().msresamp_hip_set_output_format(self._h, int(v)), "msresamp_hip_set_output_format")
+
+    @property
+    def gain(self):
+        """The output gain (msresamp_hip_set_output_gain): finite, applies to both output formats, may be set between any two calls."""
+        return float(lib().msresamp_hip_output_gain(self._h))
+
+    @gain.setter
+    def gain(self, v):
+        self._chk(lib().msresamp_hip_set_output_gain(self._h, float(v)), "msresamp_hip_set_output_gain")
+
+    def clipped(self, reset=False):
+        """Samples clipped by sc16-output calls since the count was last reset (waits for the last such call's kernels only)."""
+        n = C.c_uint64(0)
+        self._chk(lib().msresamp_hip_clipped(self._h, C.byref(n), 1 if reset else 0), "msresamp_hip_clipped")
+        return int(n.value)
 
     def get_delay(self):
         return float(lib().msresamp_hip_get_delay(self._h))
@@ -581,7 +637,8 @@ class msresamp(object):
 
     def execute(self, x, stream=None):
         """x: the new samples, a torch CUDA tensor -- complex64, or on an sc16 resampler int16 of 2 n elements (interleaved re, im;
-        shape (n, 2) is fine).  Returns complex64.  TypeError on a tensor of the other format's dtype."""
+        shape (n, 2) is fine).  Returns complex64, or on an sc16-output resampler int16 of shape (nout, 2).  TypeError on a tensor of
+        the other input format's dtype."""
         import torch
         sc16 = self.input_format == INPUT_FORMATS["sc16"]
         if sc16:
@@ -599,7 +656,10 @@ class msresamp(object):
             n = int(x.numel())
             fn, name = lib().msresamp_hip_execute_device, "msresamp_hip_execute_device"
         cap = int(lib().msresamp_hip_max_output(self._h, n)) + 8
-        y = torch.empty(cap, dtype=torch.complex64, device=x.device)
+        if self.output_format == OUTPUT_FORMATS["sc16"]:
+            y = torch.empty((cap, 2), dtype=torch.int16, device=x.device)
+        else:
+            y = torch.empty(cap, dtype=torch.complex64, device=x.device)
         nout = C.c_size_t(0)
         rc = fn(self._h, _dptr(x), n, _dptr(y), cap, C.byref(nout), _stream_ptr(stream))
         if rc != MCRX_OK:

@@ -22,8 +22,10 @@
 #include "../../include/mcrx_hip.h"
 #include "design.hpp"
 #include "devscope.hpp"
+#include "sc16_out.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -47,6 +49,17 @@ using namespace mcrx;
 // the handle's format: every later stage buffer is cf32.
 #define RS_IN_CF32 0
 #define RS_IN_SC16 1
+// Output formats of the caller's buffer (msresamp_hip_set_output_format), in the kernels that can be a last stage.
+// Let y be the fp32 value the stage computes for one component.  The store to the caller's buffer is v = y * gain (one multiply of its
+// own; gain = 1 stores y) as cf32, or Q(v) as sc16: the transmitter's quantiser and clip count (sc16_out.hpp), one packed 4-byte word
+// a sample.  Only that store knows the format: stage buffers between the kernels are cf32 and are written with gain = 1.
+// In the builds that can store sc16 (template parameter SC16) the format is a run-time choice at the store (clip != NULL: sc16), inside
+// one body that keeps the cf32 store, as in txgen.hip's txfir_column and for its reason: a build that ended in the 4-byte store alone
+// contracted the multiply-adds of the tap sums differently from its cf32 twin (more than half of them left as a multiply and an add),
+// and Q is a function of the cf32 value only if that value is the same.  With both stores in the body the sums compile to the cf32
+// build's fused multiply-adds.  The builds without SC16 are the cf32 handles': no branch, no clip count, the parent's registers.
+#define RS_OUT_CF32 0
+#define RS_OUT_SC16 1
 template <int FMT> struct RsElem { typedef float2 type; };
 template <> struct RsElem<RS_IN_SC16> { typedef uint32_t type; };
 
@@ -104,7 +117,12 @@ __global__ __launch_bounds__(256) void halfband_kernel(RsInT<FMT> in, float2 *ou
 }
 
 // Half-band interpolator: inputs k in [k0, k1) -> outputs 2k, 2k+1 at out[2 (k - k0)]
-__global__ __launch_bounds__(256) void halfband_interp_kernel(RsIn in, float2 *out, long long k0, long long k1, const float *h1)
+// SC16 and clip != NULL, sc16 (only where `out` is the caller's buffer): the pair is two packed words, stored as one 8-byte word where `out` is 8-byte
+// aligned and as two 4-byte stores where it is not -- pair p lies at out + 8 p bytes, so the choice is the same for every lane of a
+// launch.  The clip count stays in a lane register and leaves once per wave, behind the loop and its per-lane break.
+template <bool SC16>
+__global__ __launch_bounds__(256) void halfband_interp_kernel(RsIn in, float2 *out, long long k0, long long k1, const float *h1, float gain,
+                                                              unsigned long long *clip)
 {
     __shared__ float2 x[RS_OB + RS_TAPS];
     const long long kb = k0 + (long long)blockIdx.x * RS_OB;
@@ -115,6 +133,8 @@ __global__ __launch_bounds__(256) void halfband_interp_kernel(RsIn in, float2 *o
     float h[RS_TAPS];
 #pragma unroll
     for (int i = 0; i < RS_TAPS; i++) h[i] = h1[i];
+    uint32_t nclip = 0;
+    const bool pair8 = (reinterpret_cast<size_t>(out) & 7) == 0;
 #pragma unroll
     for (int r = 0; r < RS_OB / 256; r++) {
         const int o = tid + 256 * r;
@@ -124,8 +144,15 @@ __global__ __launch_bounds__(256) void halfband_interp_kernel(RsIn in, float2 *o
 #pragma unroll
         for (int i = 0; i < RS_TAPS; i++) { const float2 v = x[o + i]; acc.x += h[i] * v.x; acc.y += h[i] * v.y; }
         const float2 d = x[o + RS_TAPS - 1 - RS_M];         // u[k-7]
-        reinterpret_cast<float4 *>(out)[k - k0] = make_float4(d.x, d.y, acc.x, acc.y);
+        const float4 v = make_float4(d.x * gain, d.y * gain, acc.x * gain, acc.y * gain);
+        if (SC16 && clip) {
+            uint32_t *o32 = reinterpret_cast<uint32_t *>(out) + 2 * (k - k0);
+            const uint32_t w0 = sc16_sample(v.x, v.y, nclip), w1 = sc16_sample(v.z, v.w, nclip);
+            if (pair8) *reinterpret_cast<uint2 *>(o32) = make_uint2(w0, w1);
+            else { o32[0] = w0; o32[1] = w1; }
+        } else reinterpret_cast<float4 *>(out)[k - k0] = v;
     }
+    if (SC16 && clip) sc16_clip_commit(clip, nclip);
 }
 
 // Arbitrary stage, outputs j in [j0, j1): input index and branch are closed forms of j (64-bit phase).  The input span
@@ -147,9 +174,13 @@ __global__ __launch_bounds__(256) void halfband_interp_kernel(RsIn in, float2 *o
 // for 11 algorithmic ones.  Chunks of 512 outputs there (the raw span is twice the half-band span), 40 KB of LDS.
 #define RS_CHUNKS 8
 #define RS_HT_ROW (RS_NPFB + RS_NPFB / 32)
-template <bool FIXED, bool HB, int FMT>
+// SC16 and clip != NULL, sc16 (only where `out` is the caller's buffer): one packed 4-byte store per lane and output; the clip count stays in a lane
+// register through all chunks and leaves once per wave at the end, behind the output loop's per-lane break (the exits in front of it,
+// a workgroup without a chunk, are taken by whole workgroups).
+template <bool FIXED, bool HB, int FMT, bool SC16>
 __global__ __launch_bounds__(256) void arbitrary_kernel(RsInT<FMT> in, float2 *out, long long j0, long long j1,
-                                                        unsigned long long step, const float *hpfb, const float *h1)
+                                                        unsigned long long step, const float *hpfb, const float *h1, float gain,
+                                                        unsigned long long *clip)
 {
     constexpr int RS_OBK = HB ? RS_OB / 2 : RS_OB;          // outputs per chunk
     constexpr int RS_SPAN = 2 * RS_OBK + RS_TAPS + 2;       // samples of the arbitrary stage's input behind a chunk (step <= 2 per output)
@@ -238,6 +269,7 @@ __global__ __launch_bounds__(256) void arbitrary_kernel(RsInT<FMT> in, float2 *o
         }
     };
     long long jb, je, nf; int np;
+    uint32_t nclip = 0;
     if (!geom(0, jb, je, nf, np)) return;
     fetch(nf, np);
     for (int c = 0; c < RS_CHUNKS; c++) {
@@ -289,26 +321,40 @@ __global__ __launch_bounds__(256) void arbitrary_kernel(RsInT<FMT> in, float2 *o
                     acc.x += h.y * v1.x; acc.y += h.y * v1.y;
                 }
             }
-            out[j - j0] = acc;
+            const float2 v = make_float2(acc.x * gain, acc.y * gain);
+            if (SC16 && clip) reinterpret_cast<uint32_t *>(out)[j - j0] = sc16_sample(v.x, v.y, nclip);
+            else out[j - j0] = v;
         }
         if (!more) break;
     }
+    if (SC16 && clip) sc16_clip_commit(clip, nclip);
 }
 // (FIXED needs the branch of output j to depend on j mod 256 only, and a thread's outputs to share it: the step's low 16 bits clear)
 static inline bool rs_fixed_rate(unsigned long long step) { return (step & 0xFFFFull) == 0; }
+// How a launch stores its outputs: into a stage buffer (the default: cf32, gain 1) or into the caller's buffer (rs_caller_out)
+struct RsOut { void *d; float gain; unsigned long long *clip; };       // clip != NULL: sc16, and where the clipped samples are counted
+static inline RsOut rs_stage_out(float2 *d) { return RsOut{ d, 1.0f, nullptr }; }
 // h1 != nullptr: `in` is the input of the last half-band decimator, folded into the launch (arbitrary_kernel, HB)
-template <int FMT>
-static inline void rs_launch_arbitrary(const RsInT<FMT> &in, float2 *out, long long j0, long long j1, unsigned long long step, const float *hpfb, hipStream_t st,
-                                       const float *h1 = nullptr)
+template <int FMT, bool SC16>
+static inline void rs_launch_arbitrary_out(const RsInT<FMT> &in, const RsOut &o, long long j0, long long j1, unsigned long long step, const float *hpfb, hipStream_t st,
+                                           const float *h1)
 {
     const unsigned n = (unsigned)(j1 - j0), ob = h1 ? RS_OB / 2 : RS_OB, grid = (n + ob * RS_CHUNKS - 1) / (ob * RS_CHUNKS);
+    float2 *out = (float2 *)o.d;
     if (h1) {
-        if (rs_fixed_rate(step)) hipLaunchKernelGGL((arbitrary_kernel<true, true, FMT>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
-        else hipLaunchKernelGGL((arbitrary_kernel<false, true, FMT>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
+        if (rs_fixed_rate(step)) hipLaunchKernelGGL((arbitrary_kernel<true, true, FMT, SC16>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1, o.gain, o.clip);
+        else hipLaunchKernelGGL((arbitrary_kernel<false, true, FMT, SC16>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1, o.gain, o.clip);
     } else {
-        if (rs_fixed_rate(step)) hipLaunchKernelGGL((arbitrary_kernel<true, false, FMT>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
-        else hipLaunchKernelGGL((arbitrary_kernel<false, false, FMT>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1);
+        if (rs_fixed_rate(step)) hipLaunchKernelGGL((arbitrary_kernel<true, false, FMT, SC16>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1, o.gain, o.clip);
+        else hipLaunchKernelGGL((arbitrary_kernel<false, false, FMT, SC16>), dim3(grid), dim3(256), 0, st, in, out, j0, j1, step, hpfb, h1, o.gain, o.clip);
     }
+}
+template <int FMT>
+static inline void rs_launch_arbitrary(const RsInT<FMT> &in, const RsOut &o, long long j0, long long j1, unsigned long long step, const float *hpfb, hipStream_t st,
+                                       const float *h1 = nullptr)
+{
+    if (o.clip) rs_launch_arbitrary_out<FMT, true>(in, o, j0, j1, step, hpfb, st, h1);
+    else rs_launch_arbitrary_out<FMT, false>(in, o, j0, j1, step, hpfb, st, h1);
 }
 
 // the last RS_KEEP samples of a two-segment input become the next call's tail (one workgroup, staged through registers
@@ -343,6 +389,13 @@ struct msresamp_hip_s {
     long long per_in = 1, per_out = 1;      // one period of the phase: step / g inputs, 2^24 / g outputs of the arbitrary stage
     hipStream_t stream = nullptr;
     unsigned in_fmt = RS_IN_CF32;   // format of the caller's samples and of in[0], their retained tail (msresamp_hip_set_input_format)
+    // The caller's output (msresamp_hip_set_output_format, _set_output_gain): read at every call and nowhere retained -- no stage buffer
+    // is an output buffer -- so both may change between any two calls.
+    unsigned out_fmt = RS_OUT_CF32;
+    float out_gain = 1.0f;
+    unsigned long long *d_clip = nullptr;               // clipped samples since sc16 output was first selected (device, 64 bits)
+    unsigned long long clip_base = 0;                   // ... of them, already reported and reset (msresamp_hip_clipped)
+    hipEvent_t clip_ev = nullptr; bool clip_pending = false;    // recorded behind the last sc16-output call's kernels
     hipEvent_t ev_first[2] = { nullptr, nullptr };      // msresamp_hip_time_first_stage: around the launch that reads the caller's samples
     bool time_first = false, timed_first = false;
 };
@@ -456,6 +509,8 @@ extern "C" int msresamp_hip_destroy(msresamp_hip_t q)
     (void)hipFree(q->d_h1); (void)hipFree(q->d_hpfb);
     if (q->stream) (void)hipStreamDestroy(q->stream);
     for (hipEvent_t e : q->ev_first) if (e) (void)hipEventDestroy(e);
+    if (q->d_clip) (void)hipFree(q->d_clip);
+    if (q->clip_ev) (void)hipEventDestroy(q->clip_ev);
     delete q;
     return MCRX_OK;
 }
@@ -505,6 +560,57 @@ extern "C" int msresamp_hip_set_input_format(msresamp_hip_t q, unsigned format)
 
 extern "C" unsigned msresamp_hip_input_format(msresamp_hip_t q) { return q ? q->in_fmt : 0; }
 
+// The output format and gain belong to the handle too, but no state is kept in them: every stage buffer is an INPUT buffer and stays
+// cf32, so either may change between any two calls, in mid-stream as well (no MCRX_EBUSY case).  The clip counter and its event are
+// allocated when sc16 output is first selected; a handle that never selects it allocates nothing.
+extern "C" int msresamp_hip_set_output_format(msresamp_hip_t q, unsigned format)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_rs_err = "null argument"; return MCRX_EINVAL; }
+    if (format != RS_OUT_CF32 && format != RS_OUT_SC16) { g_rs_err = "msresamp: output format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
+    if (format == RS_OUT_SC16 && !q->d_clip) {
+        unsigned long long *d = nullptr;
+        RSCHK(hipMalloc((void **)&d, sizeof(unsigned long long)));
+        if (hipMemset(d, 0, sizeof(unsigned long long)) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipEventCreateWithFlags(&q->clip_ev, hipEventDisableTiming) != hipSuccess) {
+            (void)hipFree(d); g_rs_err = "device allocation failed"; return MCRX_EHIP;
+        }
+        q->d_clip = d;
+    }
+    q->out_fmt = format;
+    return MCRX_OK;
+}
+
+extern "C" unsigned msresamp_hip_output_format(msresamp_hip_t q) { return q ? q->out_fmt : 0u; }
+
+extern "C" int msresamp_hip_set_output_gain(msresamp_hip_t q, float gain)
+{
+    if (!q) { g_rs_err = "null argument"; return MCRX_EINVAL; }
+    if (!std::isfinite(gain)) { g_rs_err = "msresamp: the output gain must be finite"; return MCRX_EINVAL; }
+    q->out_gain = gain;
+    return MCRX_OK;
+}
+
+extern "C" float msresamp_hip_output_gain(msresamp_hip_t q) { return q ? q->out_gain : 0.0f; }
+
+// Samples clipped by sc16-output calls since the last reset of the count (mctx_hip_clipped's semantics): waits for the event behind the
+// last such call only, not for the stream.  0 on a handle that never selected sc16 output.
+extern "C" int msresamp_hip_clipped(msresamp_hip_t q, uint64_t *samples, int reset)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_rs_err = "null argument"; return MCRX_EINVAL; }
+    uint64_t n = 0;
+    if (q->d_clip) {
+        if (q->clip_pending) { RSCHK(hipEventSynchronize(q->clip_ev)); q->clip_pending = false; }
+        unsigned long long seen = 0;
+        RSCHK(hipMemcpy(&seen, q->d_clip, sizeof(seen), hipMemcpyDeviceToHost));
+        n = seen - q->clip_base;
+        if (reset) q->clip_base = seen;
+    }
+    if (samples) *samples = n;
+    return MCRX_OK;
+}
+
 // Measurement aid (bench_resamp_sc16.py): HIP events around the first stage's launch of every following execute call.
 extern "C" int msresamp_hip_time_first_stage(msresamp_hip_t q, int enable)
 {
@@ -526,7 +632,7 @@ extern "C" int msresamp_hip_first_stage_ms(msresamp_hip_t q, float *ms)
     return MCRX_OK;
 }
 
-// d_in: nin new input samples in device memory, in format FMT; d_out receives *nout <= out_cap samples (cf32)
+// d_in: nin new input samples in device memory, in format FMT; d_out receives *nout <= out_cap samples in the handle's output format
 template <int FMT>
 static int rs_execute(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out, size_t out_cap, size_t *nout, void *stream)
 {
@@ -543,6 +649,16 @@ static int rs_execute(msresamp_hip_t q, const void *d_in, size_t nin, void *d_ou
     // msresamp -> multichannelrx chains on the default stream unordered: the bank could read samples not yet written.)
     hipStream_t st = (hipStream_t)stream;
     *nout = 0;
+    // the last stage's store: the handle's format and gain as they are now (sc16: any 4-byte-aligned d_out)
+    const bool sc16_out = q->out_fmt == RS_OUT_SC16;
+    if (sc16_out && (reinterpret_cast<uintptr_t>(d_out) & 3u)) { g_rs_err = "sc16 output must be 4-byte aligned"; return MCRX_EINVAL; }
+    const RsOut caller = { d_out, q->out_gain, sc16_out ? q->d_clip : nullptr };
+    auto clip_mark = [&]() -> int {         // behind the launch that wrote the caller's sc16 samples: what msresamp_hip_clipped waits for
+        if (!sc16_out) return MCRX_OK;
+        RSCHK(hipEventRecord(q->clip_ev, st));
+        q->clip_pending = true;
+        return MCRX_OK;
+    };
     rs_rebase(q);
     // the first stage reads [retained tail | the caller's new samples]; nothing is copied
     StageBuf &b0 = q->in[0];
@@ -568,17 +684,20 @@ static int rs_execute(msresamp_hip_t q, const void *d_in, size_t nin, void *d_ou
         if (j1 < j0) j1 = j0;
         const size_t total_out = (size_t)(j1 - j0) << q->num_stages;
         if (total_out > out_cap) { g_rs_err = "output buffer too small"; return MCRX_EINVAL; }
-        float2 *dst = (float2 *)d_out;
+        RsOut dst = caller;
         if (q->num_stages) {
             StageBuf &b1 = q->in[1];
             if ((rc = stage_reserve(q, b1, (size_t)(j1 - j0), st))) return rc;
-            dst = b1.d + (b1.end - b1.base);
+            dst = rs_stage_out(b1.d + (b1.end - b1.base));
             b1.end += j1 - j0;
         }
         if (j1 > j0) {
-            FirstStageTimer timer(q, st);
-            rs_launch_arbitrary(src0, dst, j0, j1, q->step, q->d_hpfb, st);
+            {
+                FirstStageTimer timer(q, st);
+                rs_launch_arbitrary(src0, dst, j0, j1, q->step, q->d_hpfb, st);
+            }
             RSCHK(hipGetLastError());
+            if (!q->num_stages && (rc = clip_mark())) return rc;
         }
         q->out_count = j1;
         if ((rc = keep_tail())) return rc;
@@ -587,17 +706,21 @@ static int rs_execute(msresamp_hip_t q, const void *d_in, size_t nin, void *d_ou
         for (unsigned s = 0; s < q->num_stages; s++) {
             StageBuf &bi = q->in[1 + s];
             const long long k1 = bi.end;
-            float2 *o = (float2 *)d_out;
-            if (s + 1 < q->num_stages) {
+            const bool last = s + 1 == q->num_stages;
+            RsOut o = caller;
+            if (!last) {
                 StageBuf &bo = q->in[2 + s];
                 if ((rc = stage_reserve(q, bo, (size_t)(2 * (k1 - k0)), st))) return rc;
-                o = bo.d + (bo.end - bo.base);
+                o = rs_stage_out(bo.d + (bo.end - bo.base));
                 bo.end += 2 * (k1 - k0);
             }
             if (k1 > k0) {
                 const unsigned n = (unsigned)(k1 - k0);
-                hipLaunchKernelGGL(halfband_interp_kernel, dim3((n + OB - 1) / OB), dim3(256), 0, st, stage_in(bi), o, k0, k1, q->d_h1);
+                const dim3 grid((n + OB - 1) / OB);
+                if (o.clip) hipLaunchKernelGGL(halfband_interp_kernel<true>, grid, dim3(256), 0, st, stage_in(bi), (float2 *)o.d, k0, k1, q->d_h1, o.gain, o.clip);
+                else hipLaunchKernelGGL(halfband_interp_kernel<false>, grid, dim3(256), 0, st, stage_in(bi), (float2 *)o.d, k0, k1, q->d_h1, o.gain, o.clip);
                 RSCHK(hipGetLastError());
+                if (last && (rc = clip_mark())) return rc;
             }
             k0 *= 2;
         }
@@ -633,13 +756,14 @@ static int rs_execute(msresamp_hip_t q, const void *d_in, size_t nin, void *d_ou
     if ((size_t)(j1 - j0) > out_cap) { g_rs_err = "output buffer too small"; return MCRX_EINVAL; }
     if (j1 > j0) {
         const unsigned ns = q->num_stages;
-        if (ns > 1) rs_launch_arbitrary(stage_in(q->in[ns - 1]), (float2 *)d_out, j0, j1, q->step, q->d_hpfb, st, q->d_h1);
+        if (ns > 1) rs_launch_arbitrary(stage_in(q->in[ns - 1]), caller, j0, j1, q->step, q->d_hpfb, st, q->d_h1);
         else {
             FirstStageTimer timer(q, st);
-            if (ns) rs_launch_arbitrary(src0, (float2 *)d_out, j0, j1, q->step, q->d_hpfb, st, q->d_h1);
-            else rs_launch_arbitrary(src0, (float2 *)d_out, j0, j1, q->step, q->d_hpfb, st);
+            if (ns) rs_launch_arbitrary(src0, caller, j0, j1, q->step, q->d_hpfb, st, q->d_h1);
+            else rs_launch_arbitrary(src0, caller, j0, j1, q->step, q->d_hpfb, st);
         }
         RSCHK(hipGetLastError());
+        if ((rc = clip_mark())) return rc;
     }
     q->out_count = j1;
     if ((rc = keep_tail())) return rc;
