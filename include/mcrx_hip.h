@@ -492,6 +492,53 @@ int    mctx_hip_stream_generate(mctx_hip_t q, float *buffer);
 int    mctx_hip_stream_reset(mctx_hip_t q);
 const char *mctx_hip_last_error(void);
 
+/* ---- channel emulator: what lies between a transmitter and a receiver ---------------------
+ * A stateful streaming operator on the wideband stream (the one mctx_hip_generate writes and mcrx_hip_execute_device / msresamp read):
+ * sparse multipath, a carrier offset, white Gaussian noise, cf32 or sc16 out.  Everything is a function of the ABSOLUTE sample index n,
+ * never of how the stream is cut into calls.  x[n] = the cf32 input, zero in front of the last reset; taps (d_i, a_i), i < T, in any order:
+ *   s[n] = sum_{i<T} a_i x[n - d_i]                        in table order
+ *   r[n] = s[n] exp(+j 2 pi th_n / 2^32)                   th_n = phase0 + cfo_step n mod 2^32; skipped when cfo_step == 0 && phase0 == 0
+ *   v[n] = gain r[n] + noise_std w[n]                      w skipped (no random number drawn) when noise_std == 0
+ *   out  = v[n] (cf32), or Q(v[n]) (sc16: mctx_hip_set_output_format's quantiser, interleaved int16 re, im)
+ * Delays are wideband samples: with K = 2N channels a delay of K is one channel-rate sample, so taps at 0, K + 3, 3K put a three-ray,
+ * frequency-selective channel inside every user channel.  w[n]: Philox4x32-10 with counter (lo32(n >> 1), hi32(n >> 1), 0, 0) and key
+ * (lo32(seed), hi32(seed)); sample n takes the words w[j], w[j + 1], j = 2 (n & 1): u1 = ((w[j] >> 9) + 0.5) 2^-23, u2 = (w[j + 1] >> 8) 2^-24,
+ * w[n] = sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2) -- unit variance per component.  The integers of an sc16 handle are Q of a cf32
+ * handle's output exactly, and a stream cut anywhere gives the one-shot output bit for bit.
+ * The handle keeps the 64-bit position of the next input sample and the last max d_i input samples (device memory); successive calls
+ * must be ordered on the device (one stream, or events of the caller's).  In-place use is refused: the taps read behind the write front. */
+#define MCRX_CHANEMU_MAX_TAPS  8
+#define MCRX_CHANEMU_MAX_DELAY 65535
+typedef struct mcrx_hip_chanemu_s *mcrx_hip_chanemu_t;
+typedef struct {
+    uint32_t struct_size, num_taps;                         /* sizeof(mcrx_hip_chanemu_config); 1 .. MCRX_CHANEMU_MAX_TAPS */
+    uint32_t delay[MCRX_CHANEMU_MAX_TAPS];                  /* <= MCRX_CHANEMU_MAX_DELAY wideband samples */
+    float    tap_re[MCRX_CHANEMU_MAX_TAPS], tap_im[MCRX_CHANEMU_MAX_TAPS];
+    uint32_t cfo_step, phase0;      /* 2^32 * cycles per wideband sample; start phase */
+    float    gain, noise_std;       /* noise_std: per component (re and im each) */
+    uint64_t seed;
+    uint32_t output_format;         /* 0 = cf32, 1 = sc16 */
+} mcrx_hip_chanemu_config;
+/* MCRX_EINVAL (before a device is looked for): null pointers, a wrong struct_size, num_taps outside 1 .. 8, a delay above the maximum,
+ * a tap, gain or noise_std that is not finite, a negative noise_std, another output_format. */
+int      mcrx_hip_chanemu_create(mcrx_hip_chanemu_t *out, const mcrx_hip_chanemu_config *cfg);
+int      mcrx_hip_chanemu_destroy(mcrx_hip_chanemu_t q);
+int      mcrx_hip_chanemu_reset(mcrx_hip_chanemu_t q);                               /* zero history, position 0 */
+/* zero history, the stream continues at absolute index `position` (any 64-bit value): phase and noise counter follow from it */
+int      mcrx_hip_chanemu_reset_at(mcrx_hip_chanemu_t q, uint64_t position);
+uint64_t mcrx_hip_chanemu_position(mcrx_hip_chanemu_t q);                            /* 0 for a null handle */
+unsigned mcrx_hip_chanemu_output_format(mcrx_hip_chanemu_t q);                       /* 0 for a null handle */
+/* n cf32 samples at d_in -> n samples at d_out in the handle's output format, asynchronously on `stream` (a hipStream_t, NULL = the
+ * default stream); at most 2^32 samples a call.  MCRX_EINVAL: a null handle or buffer, d_in not 8-byte aligned, d_out not 8-byte (cf32) /
+ * 4-byte (sc16) aligned, ranges that overlap.  (Pairs of samples go as 16-byte (sc16 out: 8-byte) words where the addresses allow.) */
+int      mcrx_hip_chanemu_execute_device(mcrx_hip_chanemu_t q, const void *d_in, size_t n, void *d_out, void *stream);
+/* mctx_hip_clipped's semantics: a 64-bit device counter, an event recorded on the caller's stream behind every sc16 call, and the read
+ * waits for that event only.  Counter and event exist only on a handle created with sc16 output; always 0 on a cf32 handle. */
+int      mcrx_hip_chanemu_clipped(mcrx_hip_chanemu_t q, uint64_t *samples, int reset);
+/* host: the two Philox words sample `position` draws under `seed` (the same code the kernel compiles; needs no GPU) */
+int      mcrx_hip_chanemu_selftest_words(uint64_t seed, uint64_t position, uint32_t out[2]);
+const char *mcrx_hip_chanemu_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

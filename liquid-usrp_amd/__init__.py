@@ -168,6 +168,16 @@ _EXPORTS = {
     "mctx_hip_stream_generate": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mctx_hip_stream_reset": (C.c_int, [C.c_void_p]),
     "mctx_hip_last_error": (C.c_char_p, []),
+    "mcrx_hip_chanemu_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcrx_hip_chanemu_destroy": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_chanemu_reset": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_chanemu_reset_at": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "mcrx_hip_chanemu_position": (C.c_uint64, [C.c_void_p]),
+    "mcrx_hip_chanemu_output_format": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_chanemu_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_chanemu_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
+    "mcrx_hip_chanemu_selftest_words": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "mcrx_hip_chanemu_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -683,6 +693,117 @@ class msresamp(object):
     def close(self):
         if self._h:
             lib().msresamp_hip_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+CHANEMU_MAX_TAPS, CHANEMU_MAX_DELAY = 8, 65535      # MCRX_CHANEMU_MAX_TAPS, MCRX_CHANEMU_MAX_DELAY
+
+
+class ChanemuConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_taps", C.c_uint32), ("delay", C.c_uint32 * CHANEMU_MAX_TAPS),
+                ("tap_re", C.c_float * CHANEMU_MAX_TAPS), ("tap_im", C.c_float * CHANEMU_MAX_TAPS),
+                ("cfo_step", C.c_uint32), ("phase0", C.c_uint32), ("gain", C.c_float), ("noise_std", C.c_float),
+                ("seed", C.c_uint64), ("output_format", C.c_uint32)]
+
+
+def chanemu_cfo_step(spacings, M, num_channels):
+    """The chanemu cfo_step (2^32 * cycles per wideband sample, mod 2^32) of a carrier offset of `spacings` subcarrier spacings as
+    every channel's synchronizer sees it: a channel-rate sample is 2 * num_channels wideband samples, a spacing 1 / M cycles of those."""
+    return int(round(float(spacings) / (M * 2 * num_channels) * 4294967296.0)) % (1 << 32)
+
+
+class chanemu(object):
+    """Channel emulator on the wideband stream, between multichanneltx and multichannelrx / msresamp (mcrx_hip_chanemu_*):
+
+        chanemu(taps=[(delay, complex), ...], cfo_step=0, phase0=0, gain=1.0, noise_std=0.0, seed=0, output_format="cf32")
+
+    1 .. 8 taps, delays in wideband samples (<= 65535), summed in the order given; cfo_step / phase0 are 32-bit phases (chanemu_cfo_step);
+    noise_std is per component.  Everything is a function of the absolute sample index, so a stream may be cut into execute calls
+    anywhere.  execute(x) takes a torch complex64 CUDA tensor and returns complex64, or with output_format="sc16" a contiguous int16
+    tensor of shape (n, 2) -- the transmitter's quantiser applied to what a cf32 emulator returns; clipped() counts the samples that
+    left the int16 range."""
+
+    def __init__(self, taps=((0, 1.0),), cfo_step=0, phase0=0, gain=1.0, noise_std=0.0, seed=0, output_format="cf32"):
+        self._h = C.c_void_p()
+        if isinstance(output_format, str):
+            if output_format not in OUTPUT_FORMATS:
+                raise ValueError("output_format must be one of %s" % sorted(OUTPUT_FORMATS))
+            output_format = OUTPUT_FORMATS[output_format]
+        taps = list(taps)
+        if not 1 <= len(taps) <= CHANEMU_MAX_TAPS:
+            raise ValueError("1 .. %d taps" % CHANEMU_MAX_TAPS)
+        c = ChanemuConfig()
+        c.struct_size, c.num_taps = C.sizeof(ChanemuConfig), len(taps)
+        for i, (d, a) in enumerate(taps):
+            if int(d) != d or not 0 <= int(d) < (1 << 32):
+                raise ValueError("a delay is a whole number of wideband samples, 0 .. %d" % CHANEMU_MAX_DELAY)
+            c.delay[i], c.tap_re[i], c.tap_im[i] = int(d), complex(a).real, complex(a).imag
+        if int(output_format) != output_format or not 0 <= int(output_format) < (1 << 32):
+            raise ValueError("output_format must be one of %s or %s" % (sorted(OUTPUT_FORMATS), sorted(OUTPUT_FORMATS.values())))
+        c.cfo_step, c.phase0 = int(cfo_step) % (1 << 32), int(phase0) % (1 << 32)
+        c.gain, c.noise_std, c.seed, c.output_format = float(gain), float(noise_std), int(seed) % (1 << 64), int(output_format)
+        rc = lib().mcrx_hip_chanemu_create(C.byref(self._h), C.addressof(c))
+        if rc != MCRX_OK:
+            self._h = C.c_void_p()
+            self._chk(rc, "mcrx_hip_chanemu_create")
+        self.taps, self.output_format = [(int(d), complex(a)) for d, a in taps], int(output_format)
+
+    @staticmethod
+    def _chk(rc, name):
+        if rc == MCRX_EINVAL:
+            raise ValueError(lib().mcrx_hip_chanemu_last_error().decode())
+        if rc != MCRX_OK:
+            raise McrxError("%s failed (%d): %s" % (name, rc, lib().mcrx_hip_chanemu_last_error().decode()))
+
+    def execute(self, x, out=None, stream=None):
+        """x: the next samples of the stream, a contiguous torch complex64 CUDA tensor.  out (optional): where they go -- complex64 of
+        at least as many elements, or on an sc16 emulator int16 of shape (>= n, 2); it must not overlap x.  Returns the n samples
+        written.  Asynchronous on `stream` (default: torch's current stream of x's device)."""
+        import torch
+        if x.dtype != torch.complex64:
+            raise TypeError("the emulator takes complex64 device tensors, not %s" % x.dtype)
+        if not x.is_cuda or not x.is_contiguous():
+            raise ValueError("device samples must be contiguous CUDA tensors")
+        n = int(x.numel())
+        sc16 = self.output_format == OUTPUT_FORMATS["sc16"]
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.int16, device=x.device) if sc16 else torch.empty(n, dtype=torch.complex64, device=x.device)
+        else:
+            if out.dtype != (torch.int16 if sc16 else torch.complex64):
+                raise TypeError("out must be %s for this emulator" % ("int16" if sc16 else "complex64"))
+            if not out.is_cuda or not out.is_contiguous() or int(out.numel()) < (2 * n if sc16 else n):
+                raise ValueError("out must be a contiguous CUDA tensor with room for %d samples" % n)
+        if n == 0:              # (an empty tensor has no address to pass)
+            return out.view(-1, 2)[:0] if sc16 else out.view(-1)[:0]
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        self._chk(lib().mcrx_hip_chanemu_execute_device(self._h, _dptr(x), n, _dptr(out), _stream_ptr(stream)),
+                  "mcrx_hip_chanemu_execute_device")
+        return out.view(-1, 2)[:n] if sc16 else out.view(-1)[:n]
+
+    def reset(self, at=0):
+        """Zero history; the stream continues at absolute sample `at` (any 64-bit value): phase and noise follow from it."""
+        self._chk(lib().mcrx_hip_chanemu_reset_at(self._h, int(at) % (1 << 64)), "mcrx_hip_chanemu_reset_at")
+
+    def position(self):
+        """absolute index of the next input sample"""
+        return int(lib().mcrx_hip_chanemu_position(self._h))
+
+    def clipped(self, reset=False):
+        """Samples clipped by the sc16 calls since the count was last reset (waits for the last such call only); 0 on a cf32 emulator."""
+        n = C.c_uint64(0)
+        self._chk(lib().mcrx_hip_chanemu_clipped(self._h, C.byref(n), 1 if reset else 0), "mcrx_hip_chanemu_clipped")
+        return int(n.value)
+
+    def close(self):
+        if self._h:
+            lib().mcrx_hip_chanemu_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -1,0 +1,303 @@
+// chanemu.hip -- channel emulator on the wideband stream for gfx950: sparse multipath, carrier offset, white noise, cf32 or sc16 out
+// (mcrx_hip_chanemu_*).
+//
+// Everything is a function of the ABSOLUTE sample index n, never of how the stream is cut into calls or of the launch geometry:
+//   s[n] = sum_{i<T} a_i x[n - d_i]                    table order, two explicit fused multiply-adds per tap and component
+//   r[n] = s[n] e^{+j 2 pi th_n / 2^32}                 th_n = phase0 + cfo_step n mod 2^32 (closed form), sincos_u32, cmul_fx's shape
+//   v[n] = gain r[n] + noise_std w[n]                   one multiply, one fused multiply-add per component
+//   out  = v[n] (cf32)  or  Q(v[n]) (sc16: sc16_out.hpp, the transmitter's quantiser as it stands)
+// w[n]: Box-Muller on the words Philox4x32-10 gives for counter (n >> 1, 0, 0) and key seed; sample n takes words 2 (n & 1), 2 (n & 1) + 1.
+//
+// chanemu_kernel<ROT, NOISE, FMT>: streaming, no LDS.  A lane owns the index-aligned pair (2k, 2k + 1): one Philox evaluation serves
+// it, and its accesses are 16 bytes where the address allows (a uniform choice per tap: all lanes' pairs have the same parity).  A tap's
+// reads are the input shifted by d_i -- coalesced, re-reading lines the neighbouring lanes and workgroups fetch anyway.  Reads in
+// front of the call's first sample come from the handle's history (the last D = max d_i inputs), of which hist_len are valid; the rest
+// are the zeros in front of the last reset.  Builds without rotation / noise carry none of that code (template parameters).
+// chanemu_history_kernel brings the history up to date behind it, from the old history and the call's input into the OTHER of two
+// buffers (a call shorter than D shifts the history, which cannot be done in place).
+//
+// Contraction is switched off for this file: sincos_u32's polynomials and everything else round the same way in every build, so the
+// integers of an sc16 handle are Q of a cf32 handle's floats, and the products that matter are written as fmaf.
+#pragma clang fp contract(off)
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <stdint.h>
+#include <string>
+#include "../../include/mcrx_hip.h"
+#include "devmath.h"
+#include "devscope.hpp"
+#include "sc16_out.hpp"
+
+namespace mcrx {
+
+// Philox4x32-10 (Salmon et al., SC'11), the same code on host (mcrx_hip_chanemu_selftest_words) and device
+struct Philox4 { uint32_t w[4]; };
+__host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    Philox4 o; o.w[0] = c0; o.w[1] = c1; o.w[2] = c2; o.w[3] = c3;
+    return o;
+}
+// the words of the pair that holds absolute sample n
+__host__ __device__ inline Philox4 chanemu_pair_words(uint64_t seed, uint64_t n)
+{
+    const uint64_t c = n >> 1;
+    return philox4x32_10((uint32_t)c, (uint32_t)(c >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+struct ChanemuArgs {
+    const float2 *in; void *out; const float2 *hist;        // hist[D]: x[pos - D .. pos), its last hist_len entries valid
+    unsigned long long *clip;                               // sc16 builds: the handle's count of clipped samples
+    uint64_t pos, n;                                        // absolute index of in[0]; samples of this call
+    uint32_t D, hist_len, T;
+    uint32_t delay[MCRX_CHANEMU_MAX_TAPS];
+    float are[MCRX_CHANEMU_MAX_TAPS], aim[MCRX_CHANEMU_MAX_TAPS];
+    uint32_t cfo_step, phase0;
+    float gain, nstd;
+    uint64_t seed;
+};
+
+// x[pos + r] for one sample: the input, the history, or a zero in front of the last reset (and for the masked half of an edge pair)
+__device__ __forceinline__ float2 chanemu_fetch(const ChanemuArgs &a, long long r)
+{
+    if (r >= 0) return r < (long long)a.n ? a.in[r] : make_float2(0.f, 0.f);
+    return -r <= (long long)a.hist_len ? a.hist[(long long)a.D + r] : make_float2(0.f, 0.f);
+}
+// the pair x[pos + r], x[pos + r + 1]
+__device__ __forceinline__ void chanemu_fetch_pair(const ChanemuArgs &a, long long r, float2 &x0, float2 &x1)
+{
+    if (r >= 0 && r + 1 < (long long)a.n) {
+        const float2 *p = a.in + r;
+        if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0) {          // (uniform: r = 2 lane + a constant)
+            const float4 v = *reinterpret_cast<const float4 *>(p);
+            x0 = make_float2(v.x, v.y); x1 = make_float2(v.z, v.w);
+        } else { x0 = p[0]; x1 = p[1]; }
+    } else { x0 = chanemu_fetch(a, r); x1 = chanemu_fetch(a, r + 1); }
+}
+
+template <bool ROT, bool NOISE>
+__device__ __forceinline__ float2 chanemu_sample(const ChanemuArgs &a, float2 s, uint64_t nabs, uint32_t w0, uint32_t w1)
+{
+    float2 r = s;
+    if (ROT) {
+        float sn, cs;
+        sincos_u32(a.phase0 + a.cfo_step * (uint32_t)nabs, sn, cs);
+        r = make_float2(fmaf(s.x, cs, -(s.y * sn)), fmaf(s.x, sn, s.y * cs));
+    }
+    float2 v = make_float2(a.gain * r.x, a.gain * r.y);
+    if (NOISE) {
+        const float u1 = ((float)(w0 >> 9) + 0.5f) * 1.1920928955078125e-07f;      // 2^-23: exact, in (0, 1)
+        const float rho = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincos_u32((w1 >> 8) << 8, sn, cs);                                       // 2 pi u2, u2 = (w1 >> 8) 2^-24
+        const float wr = rho * cs, wi = rho * sn;
+        v = make_float2(fmaf(a.nstd, wr, v.x), fmaf(a.nstd, wi, v.y));
+    }
+    return v;
+}
+
+template <bool ROT, bool NOISE, int FMT>
+__global__ __launch_bounds__(256) void chanemu_kernel(ChanemuArgs a)
+{
+    // lane g owns absolute samples base + 2 g, + 1 with base = pos & ~1: relative to in[0] that is m0 = 2 g - (pos & 1), m0 + 1
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint32_t odd = (uint32_t)(a.pos & 1u);
+    const long long m0 = (long long)(2 * g) - (long long)odd;
+    const bool ok0 = m0 >= 0 && m0 < (long long)a.n, ok1 = m0 + 1 < (long long)a.n;      // (m0 + 1 >= 0 always)
+    uint32_t nclip = 0;
+    if (ok0 || ok1) {
+        float2 x0[MCRX_CHANEMU_MAX_TAPS], x1[MCRX_CHANEMU_MAX_TAPS];
+#pragma unroll
+        for (int i = 0; i < MCRX_CHANEMU_MAX_TAPS; i++)                 // every tap's loads first: T pairs in flight
+            if (i < (int)a.T) chanemu_fetch_pair(a, m0 - (long long)a.delay[i], x0[i], x1[i]);
+        float2 s0 = make_float2(0.f, 0.f), s1 = s0;
+#pragma unroll
+        for (int i = 0; i < MCRX_CHANEMU_MAX_TAPS; i++)
+            if (i < (int)a.T) {
+                const float ar = a.are[i], ai = a.aim[i];
+                s0.x = fmaf(ar, x0[i].x, fmaf(-ai, x0[i].y, s0.x)); s0.y = fmaf(ar, x0[i].y, fmaf(ai, x0[i].x, s0.y));
+                s1.x = fmaf(ar, x1[i].x, fmaf(-ai, x1[i].y, s1.x)); s1.y = fmaf(ar, x1[i].y, fmaf(ai, x1[i].x, s1.y));
+            }
+        const uint64_t nabs = (a.pos - odd) + 2 * g;                    // even; wraps with the 64-bit position
+        Philox4 w = {};
+        if (NOISE) w = chanemu_pair_words(a.seed, nabs);
+        const float2 v0 = chanemu_sample<ROT, NOISE>(a, s0, nabs, w.w[0], w.w[1]);
+        const float2 v1 = chanemu_sample<ROT, NOISE>(a, s1, nabs + 1, w.w[2], w.w[3]);
+        if (FMT == TX_SC16) {
+            uint32_t *o = reinterpret_cast<uint32_t *>(a.out) + m0;
+            uint32_t c0 = 0, c1 = 0;
+            const uint32_t q0 = sc16_sample(v0.x, v0.y, c0), q1 = sc16_sample(v1.x, v1.y, c1);
+            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(o) & 7u) == 0) *reinterpret_cast<uint2 *>(o) = make_uint2(q0, q1);
+            else { if (ok0) o[0] = q0; if (ok1) o[1] = q1; }
+            nclip = (ok0 ? c0 : 0u) + (ok1 ? c1 : 0u);
+        } else {
+            float2 *o = reinterpret_cast<float2 *>(a.out) + m0;
+            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) *reinterpret_cast<float4 *>(o) = make_float4(v0.x, v0.y, v1.x, v1.y);
+            else { if (ok0) o[0] = v0; if (ok1) o[1] = v1; }
+        }
+    }
+    if (FMT == TX_SC16) sc16_clip_commit(a.clip, nclip);               // every lane of every wave gets here
+}
+
+// next[j] = x[pos + n - D + j], j < D: from the old history while j + n < D, from the input behind it
+__global__ __launch_bounds__(256) void chanemu_history_kernel(ChanemuArgs a, float2 *next)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= a.D) return;
+    next[j] = chanemu_fetch(a, (long long)a.n - (long long)a.D + (long long)j);
+}
+
+}  // namespace mcrx
+
+using namespace mcrx;
+
+static thread_local std::string g_ce_err;
+#define CECHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_ce_err = std::string(#x) + ": " + hipGetErrorString(e_); return MCRX_EHIP; } } while (0)
+
+struct mcrx_hip_chanemu_s {
+    int device = -1;            // the HIP device the handle was created on: every entry point runs with it current (devscope.hpp)
+    mcrx_hip_chanemu_config cfg;
+    uint32_t D = 0;             // max d_i
+    uint64_t pos = 0;           // absolute index of the next input sample
+    uint32_t hist_len = 0;      // valid samples at the end of hist[cur] (the rest: zeros in front of the last reset)
+    float2 *hist[2] = { nullptr, nullptr }; int cur = 0;
+    unsigned long long *d_clip = nullptr;               // sc16 handles only: clipped samples since the handle was made (device, 64 bits)
+    unsigned long long clip_base = 0;                   // ... of them, already reported and reset
+    hipEvent_t clip_ev = nullptr; bool clip_pending = false;    // recorded behind the last sc16 call
+};
+
+extern "C" const char *mcrx_hip_chanemu_last_error(void) { return g_ce_err.c_str(); }
+
+extern "C" int mcrx_hip_chanemu_selftest_words(uint64_t seed, uint64_t position, uint32_t out[2])
+{
+    if (!out) { g_ce_err = "null pointer"; return MCRX_EINVAL; }
+    const Philox4 w = chanemu_pair_words(seed, position);
+    const unsigned j = 2u * (unsigned)(position & 1u);
+    out[0] = w.w[j]; out[1] = w.w[j + 1];
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_chanemu_create(mcrx_hip_chanemu_t *out, const mcrx_hip_chanemu_config *cfg)
+{
+    if (!out) { g_ce_err = "null pointer"; return MCRX_EINVAL; }
+    *out = nullptr;
+    if (!cfg) { g_ce_err = "null configuration"; return MCRX_EINVAL; }
+    if (cfg->struct_size != sizeof(mcrx_hip_chanemu_config)) { g_ce_err = "mcrx_hip_chanemu_config: wrong struct_size"; return MCRX_EINVAL; }
+    if (cfg->num_taps < 1 || cfg->num_taps > MCRX_CHANEMU_MAX_TAPS) { g_ce_err = "num_taps must be 1 .. 8"; return MCRX_EINVAL; }
+    uint32_t D = 0;
+    for (uint32_t i = 0; i < cfg->num_taps; i++) {
+        if (cfg->delay[i] > MCRX_CHANEMU_MAX_DELAY) { g_ce_err = "a delay exceeds MCRX_CHANEMU_MAX_DELAY"; return MCRX_EINVAL; }
+        if (!std::isfinite(cfg->tap_re[i]) || !std::isfinite(cfg->tap_im[i])) { g_ce_err = "taps must be finite"; return MCRX_EINVAL; }
+        D = cfg->delay[i] > D ? cfg->delay[i] : D;
+    }
+    if (!std::isfinite(cfg->gain)) { g_ce_err = "gain must be finite"; return MCRX_EINVAL; }
+    if (!std::isfinite(cfg->noise_std) || cfg->noise_std < 0.f) { g_ce_err = "noise_std must be finite and not negative"; return MCRX_EINVAL; }
+    if (cfg->output_format != TX_CF32 && cfg->output_format != TX_SC16) { g_ce_err = "output format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { g_ce_err = "no HIP device (no CPU fallback)"; return MCRX_EHIP; }
+    mcrx_hip_chanemu_t q = new mcrx_hip_chanemu_s();
+    q->device = current_device();
+    q->cfg = *cfg; q->D = D;
+    auto fail = [&](hipError_t e, const char *what) { g_ce_err = std::string(what) + ": " + hipGetErrorString(e); mcrx_hip_chanemu_destroy(q); return MCRX_EHIP; };
+    hipError_t e;
+    for (int b = 0; b < 2 && D; b++)
+        if ((e = hipMalloc((void **)&q->hist[b], (size_t)D * sizeof(float2))) != hipSuccess) return fail(e, "hipMalloc(history)");
+    if (cfg->output_format == TX_SC16) {
+        if ((e = hipMalloc((void **)&q->d_clip, sizeof(unsigned long long))) != hipSuccess) return fail(e, "hipMalloc(clip counter)");
+        if ((e = hipMemset(q->d_clip, 0, sizeof(unsigned long long))) != hipSuccess) return fail(e, "hipMemset(clip counter)");
+        if ((e = hipDeviceSynchronize()) != hipSuccess) return fail(e, "hipDeviceSynchronize");
+        if ((e = hipEventCreateWithFlags(&q->clip_ev, hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
+    }
+    *out = q;
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_chanemu_destroy(mcrx_hip_chanemu_t q)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) return MCRX_OK;
+    (void)hipDeviceSynchronize();
+    for (float2 *p : q->hist) if (p) (void)hipFree(p);
+    if (q->d_clip) (void)hipFree(q->d_clip);
+    if (q->clip_ev) (void)hipEventDestroy(q->clip_ev);
+    delete q;
+    return MCRX_OK;
+}
+
+// no device work: the history is marked empty, and what the kernels read in front of it are zeros
+extern "C" int mcrx_hip_chanemu_reset_at(mcrx_hip_chanemu_t q, uint64_t position)
+{
+    if (!q) { g_ce_err = "null handle"; return MCRX_EINVAL; }
+    q->pos = position; q->hist_len = 0;
+    return MCRX_OK;
+}
+extern "C" int mcrx_hip_chanemu_reset(mcrx_hip_chanemu_t q) { return mcrx_hip_chanemu_reset_at(q, 0); }
+extern "C" uint64_t mcrx_hip_chanemu_position(mcrx_hip_chanemu_t q) { return q ? q->pos : 0; }
+extern "C" unsigned mcrx_hip_chanemu_output_format(mcrx_hip_chanemu_t q) { return q ? q->cfg.output_format : 0u; }
+
+template <int FMT>
+static void chanemu_launch(const ChanemuArgs &a, bool rot, bool noise, dim3 grid, hipStream_t st)
+{
+    if (rot) { if (noise) hipLaunchKernelGGL((chanemu_kernel<true, true, FMT>), grid, dim3(256), 0, st, a);
+               else       hipLaunchKernelGGL((chanemu_kernel<true, false, FMT>), grid, dim3(256), 0, st, a); }
+    else     { if (noise) hipLaunchKernelGGL((chanemu_kernel<false, true, FMT>), grid, dim3(256), 0, st, a);
+               else       hipLaunchKernelGGL((chanemu_kernel<false, false, FMT>), grid, dim3(256), 0, st, a); }
+}
+
+extern "C" int mcrx_hip_chanemu_execute_device(mcrx_hip_chanemu_t q, const void *d_in, size_t n, void *d_out, void *stream)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_ce_err = "null handle"; return MCRX_EINVAL; }
+    if (!d_in || !d_out) { g_ce_err = "null buffer"; return MCRX_EINVAL; }
+    const bool sc16 = q->cfg.output_format == TX_SC16;
+    const uintptr_t pi = reinterpret_cast<uintptr_t>(d_in), po = reinterpret_cast<uintptr_t>(d_out);
+    if (pi & 7u) { g_ce_err = "d_in must be 8-byte aligned"; return MCRX_EINVAL; }
+    if (po & (sc16 ? 3u : 7u)) { g_ce_err = sc16 ? "d_out must be 4-byte aligned" : "d_out must be 8-byte aligned"; return MCRX_EINVAL; }
+    if (n > ((size_t)1 << 32)) { g_ce_err = "at most 2^32 samples a call"; return MCRX_EINVAL; }      // (a lane per pair, 2^31 lanes a launch)
+    const size_t bi = n * 8u, bo = n * (sc16 ? 4u : 8u);
+    if (pi < po + bo && po < pi + bi) { g_ce_err = "d_in and d_out overlap: the taps read behind the write front, in-place use is not possible"; return MCRX_EINVAL; }
+    if (n == 0) return MCRX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const mcrx_hip_chanemu_config &c = q->cfg;
+    ChanemuArgs a = {};
+    a.in = static_cast<const float2 *>(d_in); a.out = d_out; a.hist = q->hist[q->cur]; a.clip = q->d_clip;
+    a.pos = q->pos; a.n = n; a.D = q->D; a.hist_len = q->hist_len; a.T = c.num_taps;
+    for (uint32_t i = 0; i < c.num_taps; i++) { a.delay[i] = c.delay[i]; a.are[i] = c.tap_re[i]; a.aim[i] = c.tap_im[i]; }
+    a.cfo_step = c.cfo_step; a.phase0 = c.phase0; a.gain = c.gain; a.nstd = c.noise_std; a.seed = c.seed;
+    const uint64_t pairs = ((q->pos & 1u) + n + 1) >> 1;
+    const dim3 grid((unsigned)((pairs + 255) / 256));
+    const bool rot = c.cfo_step != 0 || c.phase0 != 0, noise = c.noise_std != 0.f;
+    if (sc16) chanemu_launch<TX_SC16>(a, rot, noise, grid, st); else chanemu_launch<TX_CF32>(a, rot, noise, grid, st);
+    CECHK(hipGetLastError());
+    if (q->D) {
+        hipLaunchKernelGGL(chanemu_history_kernel, dim3((q->D + 255) / 256), dim3(256), 0, st, a, q->hist[q->cur ^ 1]);
+        CECHK(hipGetLastError());
+        q->cur ^= 1;
+        q->hist_len = (uint32_t)((uint64_t)q->hist_len + n < q->D ? q->hist_len + n : q->D);
+    }
+    q->pos += n;
+    if (sc16) { CECHK(hipEventRecord(q->clip_ev, st)); q->clip_pending = true; }
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_chanemu_clipped(mcrx_hip_chanemu_t q, uint64_t *samples, int reset)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_ce_err = "null handle"; return MCRX_EINVAL; }
+    uint64_t n = 0;
+    if (q->d_clip) {
+        if (q->clip_pending) { CECHK(hipEventSynchronize(q->clip_ev)); q->clip_pending = false; }
+        unsigned long long seen = 0;
+        CECHK(hipMemcpy(&seen, q->d_clip, sizeof(seen), hipMemcpyDeviceToHost));
+        n = seen - q->clip_base;
+        if (reset) q->clip_base = seen;
+    }
+    if (samples) *samples = n;
+    return MCRX_OK;
+}
