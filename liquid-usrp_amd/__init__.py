@@ -219,6 +219,47 @@ def _check(rc, allow=()):
     return rc
 
 
+def _raise_rc(rc, name, last_error, einval_is_value_error=True):
+    """The return code of the C call `name`: nothing on MCRX_OK, else ValueError (MCRX_EINVAL at the sites where that is an argument
+    error) or McrxError, with the text of the operator's own last-error function."""
+    if rc == MCRX_OK:
+        return
+    msg = last_error()
+    msg = msg.decode() if msg else ""
+    if rc == MCRX_EINVAL and einval_is_value_error:
+        raise ValueError(msg)
+    raise McrxError("%s failed (%d): %s" % (name, rc, msg))
+
+
+def _format_code(value, table, what):
+    """The code of a format given as one of `table`'s names or as a number equal to one of its codes; ValueError otherwise.  Touches
+    no library: a bad format is an argument error on a machine without a device too."""
+    code = table.get(value) if isinstance(value, str) else next((c for c in table.values() if c == value), None)
+    if code is None:
+        raise ValueError("%s must be one of %s or %s, not %r" % (what, sorted(table), sorted(table.values()), value))
+    return code
+
+
+def _empty_samples(n, fmt, device):
+    """An uninitialised torch tensor of n samples in format `fmt` on `device`: int16 of shape (n, 2), or complex64 of shape (n,)."""
+    import torch
+    if fmt == OUTPUT_FORMATS["sc16"]:
+        return torch.empty((n, 2), dtype=torch.int16, device=device)
+    return torch.empty(n, dtype=torch.complex64, device=device)
+
+
+def _sc16_device_samples(x, what):
+    """The number of samples in x, an sc16 device tensor handed to a `what` ("receiver", "resampler"): int16, contiguous, whole pairs."""
+    import torch
+    if x.dtype != torch.int16:
+        raise TypeError("this %s takes int16 device tensors (interleaved re, im), not %s" % (what, x.dtype))
+    if not x.is_contiguous():
+        raise ValueError("device samples must be contiguous")
+    if x.numel() % 2:
+        raise ValueError("an sc16 buffer holds (re, im) pairs: odd number of int16")
+    return int(x.numel()) // 2
+
+
 class Frame(object):
     """Arguments of one framesync_callback invocation (include/multichannelrx.h:45)."""
     __slots__ = ("channel", "header", "header_valid", "payload", "payload_valid", "evm", "rssi", "cfo",
@@ -307,19 +348,12 @@ class multichannelrx(object):
         c.struct_size = C.sizeof(Config)
         c.payload_soft = 1
         for k, v in cfg.items():
-            if k == "input_format" and isinstance(v, str):
-                if v not in INPUT_FORMATS:
-                    raise ValueError("input_format must be one of %s" % sorted(INPUT_FORMATS))
-                v = INPUT_FORMATS[v]
-            setattr(c, k, v)
+            setattr(c, k, _format_code(v, INPUT_FORMATS, "input_format") if k == "input_format" else v)
         rc = lib().mcrx_hip_create(C.byref(self._h), num_channels, M, cp_len, taper_len,
                                    None if parr is None else parr.ctypes.data, C.addressof(c))
         if rc != MCRX_OK:
             self._h = C.c_void_p()
-            msg = lib().mcrx_hip_last_error().decode()
-            if rc == MCRX_EINVAL:
-                raise ValueError(msg)           # the reference prints the message and throws
-            raise McrxError("mcrx_hip_create failed (%d): %s" % (rc, msg))
+            _raise_rc(rc, "mcrx_hip_create", lib().mcrx_hip_last_error)      # (MCRX_EINVAL: the reference prints the message and throws)
         self.userdata = list(userdata) if userdata is not None else [None] * num_channels
         self.callback = list(callback) if callback is not None else [None] * num_channels
         self.frames = []            # every frame delivered so far (also handed to the callbacks)
@@ -340,11 +374,8 @@ class multichannelrx(object):
         if hasattr(x, "is_cuda") and x.is_cuda:
             import torch
             if sc16:
-                if x.dtype != torch.int16:
-                    raise TypeError("this receiver takes int16 device tensors (interleaved re, im), not %s" % x.dtype)
-                if not x.is_contiguous():
-                    raise ValueError("device samples must be contiguous")
-                n = int(x.numel()) // 2 if num_samples is None else int(num_samples)
+                n = _sc16_device_samples(x, "receiver")
+                n = n if num_samples is None else int(num_samples)
                 _check(lib().mcrx_hip_execute_device_sc16(self._h, _dptr(x), n, _stream_ptr(stream)))
                 return
             if x.dtype == torch.int16:
@@ -563,43 +594,26 @@ class msresamp(object):
 
     def __init__(self, rate, As=60.0, input_format="cf32", output_format="cf32", gain=1.0):
         self._h = C.c_void_p()
-        if isinstance(output_format, str):
-            if output_format not in OUTPUT_FORMATS:
-                raise ValueError("output_format must be one of %s" % sorted(OUTPUT_FORMATS))
-            output_format = OUTPUT_FORMATS[output_format]
-        elif output_format not in OUTPUT_FORMATS.values():
-            raise ValueError("output_format must be one of %s or %s" % (sorted(OUTPUT_FORMATS), sorted(OUTPUT_FORMATS.values())))
+        output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
         gain = float(gain)
         if not math.isfinite(gain):
             raise ValueError("gain must be finite")
-        if isinstance(input_format, str):
-            if input_format not in INPUT_FORMATS:
-                raise ValueError("input_format must be one of %s" % sorted(INPUT_FORMATS))
-            input_format = INPUT_FORMATS[input_format]
-        elif input_format not in INPUT_FORMATS.values():
-            raise ValueError("input_format must be one of %s or %s" % (sorted(INPUT_FORMATS), sorted(INPUT_FORMATS.values())))
+        input_format = _format_code(input_format, INPUT_FORMATS, "input_format")
         rc = lib().msresamp_hip_create(C.byref(self._h), rate, As)
         if rc != MCRX_OK:
             self._h = C.c_void_p()
-            msg = lib().msresamp_hip_last_error().decode()
-            if rc == MCRX_EINVAL:
-                raise ValueError(msg)
-            raise McrxError("msresamp_hip_create failed (%d): %s" % (rc, msg))
+            self._chk(rc, "msresamp_hip_create")
         self.rate = rate
         if input_format:
-            rc = lib().msresamp_hip_set_input_format(self._h, int(input_format))
-            if rc != MCRX_OK:
-                raise McrxError("msresamp_hip_set_input_format failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
+            self._chk(lib().msresamp_hip_set_input_format(self._h, input_format), "msresamp_hip_set_input_format", False)
         if output_format:
             self.output_format = output_format
         if gain != 1.0:
             self.gain = gain
 
-    def _chk(self, rc, name):
-        if rc == MCRX_EINVAL:
-            raise ValueError(lib().msresamp_hip_last_error().decode())
-        if rc != MCRX_OK:
-            raise McrxError("%s failed (%d): %s" % (name, rc, lib().msresamp_hip_last_error().decode()))
+    @staticmethod
+    def _chk(rc, name, einval_is_value_error=True):
+        _raise_rc(rc, name, lib().msresamp_hip_last_error, einval_is_value_error)
 
     @property
     def input_format(self):
@@ -613,11 +627,8 @@ class msresamp(object):
 
     @output_format.setter
     def output_format(self, v):
-        if isinstance(v, str):
-            if v not in OUTPUT_FORMATS:
-                raise ValueError("output_format must be one of %s" % sorted(OUTPUT_FORMATS))
-            v = OUTPUT_FORMATS[v]
-        self._chk(lib().msresamp_hip_set_output_format(self._h, int(v)), "msresamp_hip_set_output_format")
+        v = _format_code(v, OUTPUT_FORMATS, "output_format")
+        self._chk(lib().msresamp_hip_set_output_format(self._h, v), "msresamp_hip_set_output_format")
 
     @property
     def gain(self):
@@ -639,11 +650,7 @@ class msresamp(object):
 
     def reset(self, at=0):
         """Start over with zero history, at input sample `at` of the stream (msresamp_hip_reset_at: a multiple of 2^num_stages)."""
-        rc = lib().msresamp_hip_reset_at(self._h, int(at))
-        if rc == MCRX_EINVAL:
-            raise ValueError(lib().msresamp_hip_last_error().decode())
-        if rc != MCRX_OK:
-            raise McrxError("msresamp_hip_reset_at failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
+        self._chk(lib().msresamp_hip_reset_at(self._h, int(at)), "msresamp_hip_reset_at")
 
     def execute(self, x, stream=None):
         """x: the new samples, a torch CUDA tensor -- complex64, or on an sc16 resampler int16 of 2 n elements (interleaved re, im;
@@ -652,13 +659,7 @@ class msresamp(object):
         import torch
         sc16 = self.input_format == INPUT_FORMATS["sc16"]
         if sc16:
-            if x.dtype != torch.int16:
-                raise TypeError("this resampler takes int16 device tensors (interleaved re, im), not %s" % x.dtype)
-            if not x.is_contiguous():
-                raise ValueError("device samples must be contiguous")
-            if x.numel() % 2:
-                raise ValueError("an sc16 buffer holds (re, im) pairs: odd number of int16")
-            n = int(x.numel()) // 2
+            n = _sc16_device_samples(x, "resampler")
             fn, name = lib().msresamp_hip_execute_device_sc16, "msresamp_hip_execute_device_sc16"
         else:
             if x.dtype == torch.int16:
@@ -666,28 +667,19 @@ class msresamp(object):
             n = int(x.numel())
             fn, name = lib().msresamp_hip_execute_device, "msresamp_hip_execute_device"
         cap = int(lib().msresamp_hip_max_output(self._h, n)) + 8
-        if self.output_format == OUTPUT_FORMATS["sc16"]:
-            y = torch.empty((cap, 2), dtype=torch.int16, device=x.device)
-        else:
-            y = torch.empty(cap, dtype=torch.complex64, device=x.device)
+        y = _empty_samples(cap, self.output_format, x.device)
         nout = C.c_size_t(0)
-        rc = fn(self._h, _dptr(x), n, _dptr(y), cap, C.byref(nout), _stream_ptr(stream))
-        if rc != MCRX_OK:
-            raise McrxError("%s failed (%d): %s" % (name, rc, lib().msresamp_hip_last_error().decode()))
+        self._chk(fn(self._h, _dptr(x), n, _dptr(y), cap, C.byref(nout), _stream_ptr(stream)), name, False)
         return y[:nout.value]
 
     def time_first_stage(self, enable=True):
         """Measurement aid (msresamp_hip_time_first_stage): time the kernel that reads the caller's samples, call by call."""
-        rc = lib().msresamp_hip_time_first_stage(self._h, int(bool(enable)))
-        if rc != MCRX_OK:
-            raise McrxError("msresamp_hip_time_first_stage failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
+        self._chk(lib().msresamp_hip_time_first_stage(self._h, int(bool(enable))), "msresamp_hip_time_first_stage", False)
 
     def first_stage_ms(self):
         """Milliseconds the first stage of the last timed execute took on the device (waits for it)."""
         ms = C.c_float(0)
-        rc = lib().msresamp_hip_first_stage_ms(self._h, C.byref(ms))
-        if rc != MCRX_OK:
-            raise McrxError("msresamp_hip_first_stage_ms failed (%d): %s" % (rc, lib().msresamp_hip_last_error().decode()))
+        self._chk(lib().msresamp_hip_first_stage_ms(self._h, C.byref(ms)), "msresamp_hip_first_stage_ms", False)
         return float(ms.value)
 
     def close(self):
@@ -731,10 +723,7 @@ class chanemu(object):
 
     def __init__(self, taps=((0, 1.0),), cfo_step=0, phase0=0, gain=1.0, noise_std=0.0, seed=0, output_format="cf32"):
         self._h = C.c_void_p()
-        if isinstance(output_format, str):
-            if output_format not in OUTPUT_FORMATS:
-                raise ValueError("output_format must be one of %s" % sorted(OUTPUT_FORMATS))
-            output_format = OUTPUT_FORMATS[output_format]
+        output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
         taps = list(taps)
         if not 1 <= len(taps) <= CHANEMU_MAX_TAPS:
             raise ValueError("1 .. %d taps" % CHANEMU_MAX_TAPS)
@@ -744,22 +733,17 @@ class chanemu(object):
             if int(d) != d or not 0 <= int(d) < (1 << 32):
                 raise ValueError("a delay is a whole number of wideband samples, 0 .. %d" % CHANEMU_MAX_DELAY)
             c.delay[i], c.tap_re[i], c.tap_im[i] = int(d), complex(a).real, complex(a).imag
-        if int(output_format) != output_format or not 0 <= int(output_format) < (1 << 32):
-            raise ValueError("output_format must be one of %s or %s" % (sorted(OUTPUT_FORMATS), sorted(OUTPUT_FORMATS.values())))
         c.cfo_step, c.phase0 = int(cfo_step) % (1 << 32), int(phase0) % (1 << 32)
-        c.gain, c.noise_std, c.seed, c.output_format = float(gain), float(noise_std), int(seed) % (1 << 64), int(output_format)
+        c.gain, c.noise_std, c.seed, c.output_format = float(gain), float(noise_std), int(seed) % (1 << 64), output_format
         rc = lib().mcrx_hip_chanemu_create(C.byref(self._h), C.addressof(c))
         if rc != MCRX_OK:
             self._h = C.c_void_p()
             self._chk(rc, "mcrx_hip_chanemu_create")
-        self.taps, self.output_format = [(int(d), complex(a)) for d, a in taps], int(output_format)
+        self.taps, self.output_format = [(int(d), complex(a)) for d, a in taps], output_format
 
     @staticmethod
     def _chk(rc, name):
-        if rc == MCRX_EINVAL:
-            raise ValueError(lib().mcrx_hip_chanemu_last_error().decode())
-        if rc != MCRX_OK:
-            raise McrxError("%s failed (%d): %s" % (name, rc, lib().mcrx_hip_chanemu_last_error().decode()))
+        _raise_rc(rc, name, lib().mcrx_hip_chanemu_last_error)
 
     def execute(self, x, out=None, stream=None):
         """x: the next samples of the stream, a contiguous torch complex64 CUDA tensor.  out (optional): where they go -- complex64 of
@@ -773,7 +757,7 @@ class chanemu(object):
         n = int(x.numel())
         sc16 = self.output_format == OUTPUT_FORMATS["sc16"]
         if out is None:
-            out = torch.empty((n, 2), dtype=torch.int16, device=x.device) if sc16 else torch.empty(n, dtype=torch.complex64, device=x.device)
+            out = _empty_samples(n, self.output_format, x.device)
         else:
             if out.dtype != (torch.int16 if sc16 else torch.complex64):
                 raise TypeError("out must be %s for this emulator" % ("int16" if sc16 else "complex64"))
@@ -828,10 +812,7 @@ class TxTraffic(object):
                                            fec1, seed & 0xFFFFFFFF, hdr.ctypes.data, pay.ctypes.data, _stream_ptr(st))
         if rc != MCRX_OK:
             self._t = C.c_void_p()
-            msg = lib().mctx_hip_last_error().decode()
-            if rc == MCRX_EINVAL:
-                raise ValueError(msg)
-            raise McrxError("mctx_hip_traffic_create failed (%d): %s" % (rc, msg))
+            _raise_rc(rc, "mctx_hip_traffic_create", lib().mctx_hip_last_error)
         self.blocks = int(lib().mctx_hip_blocks_for(tx._h, frames, payload_len, mod, fec0, fec1))
         self.sent = [[(bytes(hdr[c, f]), bytes(pay[c, f, :payload_len])) for f in range(frames)] for c in range(channel_count)]
 
@@ -840,9 +821,8 @@ class TxTraffic(object):
         import torch
         assert nblocks % 8 == 0 and out.numel() >= nblocks * self.channel_count
         st = stream if stream is not None else torch.cuda.current_stream(out.device)
-        rc = lib().mctx_hip_traffic_tiles(self._t, first_block, nblocks, _dptr(out), _stream_ptr(st))
-        if rc != MCRX_OK:
-            raise McrxError("mctx_hip_traffic_tiles failed (%d): %s" % (rc, lib().mctx_hip_last_error().decode()))
+        _raise_rc(lib().mctx_hip_traffic_tiles(self._t, first_block, nblocks, _dptr(out), _stream_ptr(st)),
+                  "mctx_hip_traffic_tiles", lib().mctx_hip_last_error, False)
         return out
 
     def close(self):
@@ -865,9 +845,7 @@ class pipeline(object):
     @staticmethod
     def unique_id():
         buf = (C.c_uint8 * 128)()
-        rc = lib().mcrx_hip_pipeline_unique_id(buf)
-        if rc != MCRX_OK:
-            raise McrxError("mcrx_hip_pipeline_unique_id failed (%d): %s" % (rc, lib().mcrx_hip_pipeline_last_error().decode()))
+        pipeline._chk(lib().mcrx_hip_pipeline_unique_id(buf), "unique_id")
         return bytes(buf)
 
     def __init__(self, rx, rank, world, sub_blocks, unique_id=None, nbuf=3):
@@ -877,9 +855,9 @@ class pipeline(object):
         self._chk(lib().mcrx_hip_pipeline_create(C.byref(self._h), rx._h, rank, world, uid, sub_blocks, nbuf), "create")
         self.rounds = 0
 
-    def _chk(self, rc, what):
-        if rc != MCRX_OK:
-            raise McrxError("mcrx_hip_pipeline_%s failed (%d): %s" % (what, rc, lib().mcrx_hip_pipeline_last_error().decode()))
+    @staticmethod
+    def _chk(rc, what):
+        _raise_rc(rc, "mcrx_hip_pipeline_" + what, lib().mcrx_hip_pipeline_last_error, False)
 
     def push(self, iq_sub, halo=None, after=None, ready=False):
         """`after`: the torch stream that produced iq_sub / halo (default: the current one) -- the round starts behind what is enqueued
@@ -946,12 +924,7 @@ class multichanneltx(object):
 
     def __init__(self, num_channels, M, cp_len, taper_len, p=None, max_payload_len=2048, output_format="cf32"):
         self._h = C.c_void_p()
-        if isinstance(output_format, str):
-            if output_format not in OUTPUT_FORMATS:
-                raise ValueError("output_format must be one of %s" % sorted(OUTPUT_FORMATS))
-            output_format = OUTPUT_FORMATS[output_format]
-        elif output_format not in OUTPUT_FORMATS.values():
-            raise ValueError("output_format must be one of %s or %s" % (sorted(OUTPUT_FORMATS), sorted(OUTPUT_FORMATS.values())))
+        output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
         self.N, self.K, self.M, self.cp = num_channels, 2 * num_channels, M, cp_len
         self.max_payload_len, self._stream_max = max_payload_len, -1
         parr = None if p is None else np.ascontiguousarray(np.frombuffer(bytes(bytearray(p)), np.uint8))
@@ -959,12 +932,9 @@ class multichanneltx(object):
                                    None if parr is None else parr.ctypes.data)
         if rc != MCRX_OK:
             self._h = C.c_void_p()
-            msg = lib().mctx_hip_last_error().decode()
-            if rc == MCRX_EINVAL:
-                raise ValueError(msg)
-            raise McrxError("mctx_hip_create failed (%d): %s" % (rc, msg))
+            self._chk(rc, "mctx_hip_create")
         if output_format:
-            self._chk(lib().mctx_hip_set_output_format(self._h, int(output_format)), "mctx_hip_set_output_format")
+            self._chk(lib().mctx_hip_set_output_format(self._h, output_format), "mctx_hip_set_output_format")
 
     def GetNumChannels(self):
         return self.N
@@ -983,10 +953,7 @@ class multichanneltx(object):
 
     def _slab(self, nsamples, device):
         """an output buffer of nsamples wideband samples in the transmitter's format"""
-        import torch
-        if self.output_format == OUTPUT_FORMATS["sc16"]:
-            return torch.empty((nsamples, 2), dtype=torch.int16, device=device)
-        return torch.empty(nsamples, dtype=torch.complex64, device=device)
+        return _empty_samples(nsamples, self.output_format, device)
 
     def generate(self, frames_per_channel, payload_len, mod=LIQUID_MODEM_QPSK, fec0=LIQUID_FEC_NONE,
                  fec1=LIQUID_FEC_HAMMING128, gain=None, seed=0xC0FFEE, nblocks=None, device=None):
@@ -1001,8 +968,7 @@ class multichanneltx(object):
         stream = torch.cuda.current_stream(iq.device)
         rc = lib().mctx_hip_generate(self._h, _dptr(iq), nb, frames_per_channel, payload_len, mod, fec0, fec1, g,
                                      seed & 0xFFFFFFFF, hdr.ctypes.data, pay.ctypes.data, _stream_ptr(stream))
-        if rc != MCRX_OK:
-            raise McrxError("mctx_hip_generate failed (%d): %s" % (rc, lib().mctx_hip_last_error().decode()))
+        self._chk(rc, "mctx_hip_generate", False)
         sent = [[(bytes(hdr[c, f]), bytes(pay[c, f, :payload_len])) for f in range(frames_per_channel)]
                 for c in range(self.N)]
         return iq, sent
@@ -1025,8 +991,7 @@ class multichanneltx(object):
         rc = lib().mctx_hip_generate_ragged(self._h, _dptr(iq), nb, maxf, len_lo, len_hi, gap_max, long_every, long_max, mod, fec0, fec1,
                                             g, seed & 0xFFFFFFFF, cnt.ctypes.data, hdr.ctypes.data, ln.ctypes.data, pay.ctypes.data,
                                             start.ctypes.data, _stream_ptr(stream))
-        if rc != MCRX_OK:
-            raise McrxError("mctx_hip_generate_ragged failed (%d): %s" % (rc, lib().mctx_hip_last_error().decode()))
+        self._chk(rc, "mctx_hip_generate_ragged", False)
         sent = [[(bytes(hdr[c, f]), bytes(pay[c, f, :ln[c, f]])) for f in range(int(cnt[c]))] for c in range(self.N)]
         starts = [[int(start[c, f]) for f in range(int(cnt[c]))] for c in range(self.N)]
         return iq, sent, starts
@@ -1062,12 +1027,9 @@ class multichanneltx(object):
             self._stream_max = max(int(self.max_payload_len), int(payload_len))
             self._chk(lib().mctx_hip_stream_begin(self._h, self._stream_max), "mctx_hip_stream_begin")
 
-    def _chk(self, rc, what):
-        if rc != MCRX_OK:
-            msg = lib().mctx_hip_last_error().decode()
-            if rc == MCRX_EINVAL:
-                raise ValueError(msg)
-            raise McrxError("%s failed (%d): %s" % (what, rc, msg))
+    @staticmethod
+    def _chk(rc, what, einval_is_value_error=True):
+        _raise_rc(rc, what, lib().mctx_hip_last_error, einval_is_value_error)
 
     def Reset(self):
         if self._stream_max >= 0:
@@ -1138,10 +1100,7 @@ class firpfbch2(object):
         rc = lib().mcrx_hip_pfb2_create(C.byref(self._h), num_channels, m, As)
         if rc != MCRX_OK:
             self._h = C.c_void_p()
-            msg = lib().mcrx_hip_pfb2_last_error().decode()
-            if rc == MCRX_EINVAL:
-                raise ValueError(msg)
-            raise McrxError("mcrx_hip_pfb2_create failed (%d): %s" % (rc, msg))
+            _raise_rc(rc, "mcrx_hip_pfb2_create", lib().mcrx_hip_pfb2_last_error)
         self._hist = None
         self._step = 0
 
@@ -1166,8 +1125,7 @@ class firpfbch2(object):
         stream = torch.cuda.current_stream(x.device)
         rc = lib().mcrx_hip_pfb2_analyze(self._h, C.c_void_p(buf.data_ptr() + 8 * lead), lead, ns, self._step, _dptr(out),
                                          _stream_ptr(stream))
-        if rc != MCRX_OK:
-            raise McrxError("mcrx_hip_pfb2_analyze failed (%d): %s" % (rc, lib().mcrx_hip_pfb2_last_error().decode()))
+        _raise_rc(rc, "mcrx_hip_pfb2_analyze", lib().mcrx_hip_pfb2_last_error, False)
         self._hist = buf[-depth:].clone() if buf.numel() > depth else buf.clone()
         self._step += ns
         return out

@@ -5,7 +5,7 @@
 //   s[n] = sum_{i<T} a_i x[n - d_i]                    table order, two explicit fused multiply-adds per tap and component
 //   r[n] = s[n] e^{+j 2 pi th_n / 2^32}                 th_n = phase0 + cfo_step n mod 2^32 (closed form), sincos_u32, cmul_fx's shape
 //   v[n] = gain r[n] + noise_std w[n]                   one multiply, one fused multiply-add per component
-//   out  = v[n] (cf32)  or  Q(v[n]) (sc16: sc16_out.hpp, the transmitter's quantiser as it stands)
+//   out  = v[n] (cf32)  or  Q(v[n]) (sc16: sc16.hpp, the shared quantiser as it stands)
 // w[n]: Box-Muller on the words Philox4x32-10 gives for counter (n >> 1, 0, 0) and key seed; sample n takes words 2 (n & 1), 2 (n & 1) + 1.
 //
 // chanemu_kernel<ROT, NOISE, FMT>: streaming, no LDS.  A lane owns the index-aligned pair (2k, 2k + 1): one Philox evaluation serves
@@ -26,7 +26,7 @@
 #include "../../include/mcrx_hip.h"
 #include "devmath.h"
 #include "devscope.hpp"
-#include "sc16_out.hpp"
+#include "sc16.hpp"
 
 namespace mcrx {
 
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void chanemu_kernel(ChanemuArgs a)
         if (NOISE) w = chanemu_pair_words(a.seed, nabs);
         const float2 v0 = chanemu_sample<ROT, NOISE>(a, s0, nabs, w.w[0], w.w[1]);
         const float2 v1 = chanemu_sample<ROT, NOISE>(a, s1, nabs + 1, w.w[2], w.w[3]);
-        if (FMT == TX_SC16) {
+        if (FMT == IQ_SC16) {
             uint32_t *o = reinterpret_cast<uint32_t *>(a.out) + m0;
             uint32_t c0 = 0, c1 = 0;
             const uint32_t q0 = sc16_sample(v0.x, v0.y, c0), q1 = sc16_sample(v1.x, v1.y, c1);
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(256) void chanemu_kernel(ChanemuArgs a)
             else { if (ok0) o[0] = v0; if (ok1) o[1] = v1; }
         }
     }
-    if (FMT == TX_SC16) sc16_clip_commit(a.clip, nclip);               // every lane of every wave gets here
+    if (FMT == IQ_SC16) sc16_clip_commit(a.clip, nclip);               // every lane of every wave gets here
 }
 
 // next[j] = x[pos + n - D + j], j < D: from the old history while j + n < D, from the input behind it
@@ -167,9 +167,7 @@ struct mcrx_hip_chanemu_s {
     uint64_t pos = 0;           // absolute index of the next input sample
     uint32_t hist_len = 0;      // valid samples at the end of hist[cur] (the rest: zeros in front of the last reset)
     float2 *hist[2] = { nullptr, nullptr }; int cur = 0;
-    unsigned long long *d_clip = nullptr;               // sc16 handles only: clipped samples since the handle was made (device, 64 bits)
-    unsigned long long clip_base = 0;                   // ... of them, already reported and reset
-    hipEvent_t clip_ev = nullptr; bool clip_pending = false;    // recorded behind the last sc16 call
+    Sc16ClipCount clip;         // sc16 handles only (allocated at creation): clipped samples since the handle was made
 };
 
 extern "C" const char *mcrx_hip_chanemu_last_error(void) { return g_ce_err.c_str(); }
@@ -198,7 +196,7 @@ extern "C" int mcrx_hip_chanemu_create(mcrx_hip_chanemu_t *out, const mcrx_hip_c
     }
     if (!std::isfinite(cfg->gain)) { g_ce_err = "gain must be finite"; return MCRX_EINVAL; }
     if (!std::isfinite(cfg->noise_std) || cfg->noise_std < 0.f) { g_ce_err = "noise_std must be finite and not negative"; return MCRX_EINVAL; }
-    if (cfg->output_format != TX_CF32 && cfg->output_format != TX_SC16) { g_ce_err = "output format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
+    if (cfg->output_format != IQ_CF32 && cfg->output_format != IQ_SC16) { g_ce_err = "output format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { g_ce_err = "no HIP device (no CPU fallback)"; return MCRX_EHIP; }
     mcrx_hip_chanemu_t q = new mcrx_hip_chanemu_s();
@@ -208,11 +206,8 @@ extern "C" int mcrx_hip_chanemu_create(mcrx_hip_chanemu_t *out, const mcrx_hip_c
     hipError_t e;
     for (int b = 0; b < 2 && D; b++)
         if ((e = hipMalloc((void **)&q->hist[b], (size_t)D * sizeof(float2))) != hipSuccess) return fail(e, "hipMalloc(history)");
-    if (cfg->output_format == TX_SC16) {
-        if ((e = hipMalloc((void **)&q->d_clip, sizeof(unsigned long long))) != hipSuccess) return fail(e, "hipMalloc(clip counter)");
-        if ((e = hipMemset(q->d_clip, 0, sizeof(unsigned long long))) != hipSuccess) return fail(e, "hipMemset(clip counter)");
-        if ((e = hipDeviceSynchronize()) != hipSuccess) return fail(e, "hipDeviceSynchronize");
-        if ((e = hipEventCreateWithFlags(&q->clip_ev, hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
+    if (cfg->output_format == IQ_SC16) {
+        if ((e = q->clip.ensure()) != hipSuccess) return fail(e, "clip counter");
     }
     *out = q;
     return MCRX_OK;
@@ -224,8 +219,7 @@ extern "C" int mcrx_hip_chanemu_destroy(mcrx_hip_chanemu_t q)
     if (!q) return MCRX_OK;
     (void)hipDeviceSynchronize();
     for (float2 *p : q->hist) if (p) (void)hipFree(p);
-    if (q->d_clip) (void)hipFree(q->d_clip);
-    if (q->clip_ev) (void)hipEventDestroy(q->clip_ev);
+    q->clip.release();
     delete q;
     return MCRX_OK;
 }
@@ -255,7 +249,7 @@ extern "C" int mcrx_hip_chanemu_execute_device(mcrx_hip_chanemu_t q, const void 
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_ce_err = "null handle"; return MCRX_EINVAL; }
     if (!d_in || !d_out) { g_ce_err = "null buffer"; return MCRX_EINVAL; }
-    const bool sc16 = q->cfg.output_format == TX_SC16;
+    const bool sc16 = q->cfg.output_format == IQ_SC16;
     const uintptr_t pi = reinterpret_cast<uintptr_t>(d_in), po = reinterpret_cast<uintptr_t>(d_out);
     if (pi & 7u) { g_ce_err = "d_in must be 8-byte aligned"; return MCRX_EINVAL; }
     if (po & (sc16 ? 3u : 7u)) { g_ce_err = sc16 ? "d_out must be 4-byte aligned" : "d_out must be 8-byte aligned"; return MCRX_EINVAL; }
@@ -266,14 +260,14 @@ extern "C" int mcrx_hip_chanemu_execute_device(mcrx_hip_chanemu_t q, const void 
     hipStream_t st = (hipStream_t)stream;
     const mcrx_hip_chanemu_config &c = q->cfg;
     ChanemuArgs a = {};
-    a.in = static_cast<const float2 *>(d_in); a.out = d_out; a.hist = q->hist[q->cur]; a.clip = q->d_clip;
+    a.in = static_cast<const float2 *>(d_in); a.out = d_out; a.hist = q->hist[q->cur]; a.clip = q->clip.device();
     a.pos = q->pos; a.n = n; a.D = q->D; a.hist_len = q->hist_len; a.T = c.num_taps;
     for (uint32_t i = 0; i < c.num_taps; i++) { a.delay[i] = c.delay[i]; a.are[i] = c.tap_re[i]; a.aim[i] = c.tap_im[i]; }
     a.cfo_step = c.cfo_step; a.phase0 = c.phase0; a.gain = c.gain; a.nstd = c.noise_std; a.seed = c.seed;
     const uint64_t pairs = ((q->pos & 1u) + n + 1) >> 1;
     const dim3 grid((unsigned)((pairs + 255) / 256));
     const bool rot = c.cfo_step != 0 || c.phase0 != 0, noise = c.noise_std != 0.f;
-    if (sc16) chanemu_launch<TX_SC16>(a, rot, noise, grid, st); else chanemu_launch<TX_CF32>(a, rot, noise, grid, st);
+    if (sc16) chanemu_launch<IQ_SC16>(a, rot, noise, grid, st); else chanemu_launch<IQ_CF32>(a, rot, noise, grid, st);
     CECHK(hipGetLastError());
     if (q->D) {
         hipLaunchKernelGGL(chanemu_history_kernel, dim3((q->D + 255) / 256), dim3(256), 0, st, a, q->hist[q->cur ^ 1]);
@@ -282,7 +276,7 @@ extern "C" int mcrx_hip_chanemu_execute_device(mcrx_hip_chanemu_t q, const void 
         q->hist_len = (uint32_t)((uint64_t)q->hist_len + n < q->D ? q->hist_len + n : q->D);
     }
     q->pos += n;
-    if (sc16) { CECHK(hipEventRecord(q->clip_ev, st)); q->clip_pending = true; }
+    if (sc16) CECHK(q->clip.mark(st));
     return MCRX_OK;
 }
 
@@ -291,13 +285,7 @@ extern "C" int mcrx_hip_chanemu_clipped(mcrx_hip_chanemu_t q, uint64_t *samples,
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_ce_err = "null handle"; return MCRX_EINVAL; }
     uint64_t n = 0;
-    if (q->d_clip) {
-        if (q->clip_pending) { CECHK(hipEventSynchronize(q->clip_ev)); q->clip_pending = false; }
-        unsigned long long seen = 0;
-        CECHK(hipMemcpy(&seen, q->d_clip, sizeof(seen), hipMemcpyDeviceToHost));
-        n = seen - q->clip_base;
-        if (reset) q->clip_base = seen;
-    }
+    CECHK(q->clip.read(&n, reset != 0));
     if (samples) *samples = n;
     return MCRX_OK;
 }

@@ -39,15 +39,15 @@
 // column's FIR output lands in the LDS tile; the taps of 1024 columns x 28 do not fit LDS beside the tile (112 + 68 KB), so
 // the newest TL = 22 of every column live in LDS and the oldest six come from a table in L2 at the start of every round.
 //
-// Input formats (template parameter IN; kernels.h: CH_IN_CF32 / CH_IN_SC16).  An sc16 sample is one 32-bit word, int16 re in the low half
-// and int16 im in the high half, and means (re, im) * 2^-15.  The word stays packed from the load to the mixer, which converts the halves
-// and scales them (both exact for every int16) where the sample is first used: from there on the arithmetic is the cf32 launch's on the
+// Input formats (template parameter IN: IQ_CF32 / IQ_SC16, an sc16 sample as sc16.hpp defines it).  The word stays packed from the
+// load to the mixer, which unpacks it where the sample is first used: from there on the arithmetic is the cf32 launch's on the
 // dequantised floats, word for word.  (Folding the 2^-15 into the oscillator value is just as exact and four multiplies per block
 // cheaper, but that build of K = 1024 spilled 32 bytes where this one and its cf32 twin spill none.)  8 B read + 4 B written per
 // wideband sample become 4 + 4.
 #include "devel.h"
 #include "devmath.h"
 #include "kernels.h"
+#include "sc16.hpp"
 #include "devscope.hpp"
 
 namespace mcrx {
@@ -76,7 +76,7 @@ __device__ __forceinline__ void lds_barrier()
 
 // what a thread holds of one sample between the load and the mixer
 template <int IN> struct RawOf { typedef float2 type; };
-template <> struct RawOf<CH_IN_SC16> { typedef uint32_t type; };
+template <> struct RawOf<IQ_SC16> { typedef uint32_t type; };
 
 template <int K> struct Log2 { enum { v = 1 + Log2<K / 2>::v }; };
 template <> struct Log2<1> { enum { v = 0 }; };
@@ -157,7 +157,7 @@ template <int K, int C, int T, int P, bool SHIFT, int IN, bool EDGE>
 __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *tile)
 {
     typedef typename RawOf<IN>::type Raw;
-    constexpr bool SC16 = IN == CH_IN_SC16;
+    constexpr bool SC16 = IN == IQ_SC16;
     constexpr int TPS = K / C;              // threads per slab
     constexpr int NS = T / TPS;             // slabs per workgroup
     constexpr int N = K / 2;
@@ -265,6 +265,7 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
         for (int c = 0; c < C; c++) {
             if (c > 0) { const float s2 = fmaf(sn, cd1, cs * sd1), c2 = fmaf(cs, cd1, -(sn * sd1)); sn = s2; cs = c2; }
             float x, y;
+            // sc16_unpack's expression spelled out: through the call this kernel's registers are allocated differently
             if constexpr (SC16) { x = (float)(int16_t)(src[c] & 0xffffu) * 0x1p-15f; y = (float)((int32_t)src[c] >> 16) * 0x1p-15f; }
             else { x = src[c].x; y = src[c].y; }
             dst[c] = make_float2(fmaf(x, cs, y * sn), fmaf(y, cs, -(x * sn)));
@@ -526,7 +527,7 @@ static hipError_t launch_one(const ChanArgs &a, hipStream_t st)
     if ((unsigned long long)(K / 2) * ((unsigned long long)a.ntiles + (unsigned long long)NS * a.slab_blocks / MCRX_TILE_S + 1ull) * (MCRX_TILE_S / 2) >= (1ull << 32))
         return hipErrorInvalidValue;
     // sc16 interior loads are addressed by 32-bit sample offsets from a.x: 4 Gi samples (16 GB of input) per launch
-    if (IN == CH_IN_SC16 && (unsigned long long)a.nblocks * K >= (1ull << 32)) return hipErrorInvalidValue;
+    if (IN == IQ_SC16 && (unsigned long long)a.nblocks * K >= (1ull << 32)) return hipErrorInvalidValue;
     static PerDeviceOnce attr_done;          // (per instantiation; devscope.hpp)
     hipError_t e = raise_lds_limit((const void *)channelizer_kernel<K, C, T, P, SHIFT, IN>, lds, attr_done);
     if (e != hipSuccess) return e;
@@ -546,9 +547,8 @@ static hipError_t launch_one(const ChanArgs &a, hipStream_t st)
 // one wideband sample as cf32: an sc16 word converted and scaled (both exact), so that the two formats share every later rounding
 template <int IN> __device__ __forceinline__ float2 sample_cf32(const void *p, size_t i)
 {
-    if constexpr (IN == CH_IN_SC16) {
-        const uint32_t v = static_cast<const uint32_t *>(p)[i];
-        return make_float2((float)(int16_t)(v & 0xffffu) * 0x1p-15f, (float)((int32_t)v >> 16) * 0x1p-15f);
+    if constexpr (IN == IQ_SC16) {
+        return sc16_unpack(static_cast<const uint32_t *>(p)[i]);
     } else return static_cast<const float2 *>(p)[i];
 }
 template <int IN>
@@ -678,8 +678,8 @@ static hipError_t launch_format(unsigned K, unsigned P, const ChanArgs &a, hipSt
 
 hipError_t channelizer_launch(unsigned K, unsigned P, unsigned in_fmt, const ChanArgs &a, hipStream_t st)
 {
-    if (in_fmt == CH_IN_CF32) return launch_format<CH_IN_CF32>(K, P, a, st);
-    if (in_fmt == CH_IN_SC16) return launch_format<CH_IN_SC16>(K, P, a, st);
+    if (in_fmt == IQ_CF32) return launch_format<IQ_CF32>(K, P, a, st);
+    if (in_fmt == IQ_SC16) return launch_format<IQ_SC16>(K, P, a, st);
     return hipErrorInvalidValue;
 }
 

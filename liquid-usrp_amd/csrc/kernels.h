@@ -13,9 +13,7 @@ namespace mcrx {
 #define MCRX_HDR_DEC 14
 
 // ---------------------------------------------------------------- channelizer.hip
-// wideband input formats (== mcrx_hip_config::input_format): cf32 = interleaved float re, im; sc16 = interleaved int16 re, im,
-// a sample meaning (re, im) * 2^-15 -- both the conversion and the scaling are exact in fp32 for every int16
-enum { CH_IN_CF32 = 0, CH_IN_SC16 = 1 };
+// wideband input formats (== mcrx_hip_config::input_format): IQ_CF32 = interleaved float re, im; IQ_SC16 as sc16.hpp defines it
 struct ChanArgs {
     const void *x;              // new wideband samples, nblocks * K, in the launch's input format (8 or 4 bytes each)
     const void *halo;           // the P - 1 blocks preceding x, same format (NULL = zeros: cold start)
@@ -33,7 +31,7 @@ int channelizer_supported(unsigned K);
 // blocks per workgroup slab such that the grid is a whole number of waves over `ncu` compute units
 uint32_t channelizer_auto_slab(unsigned K, size_t nblocks, unsigned ncu);
 // P = taps per column: 14 = the reference's bank (any even K <= 2048), 28 = the oversampled front end's composite bank (power-of-two K <= 1024);
-// in_fmt = CH_IN_CF32 / CH_IN_SC16: what a.x and a.halo hold
+// in_fmt = IQ_CF32 / IQ_SC16 (sc16.hpp): what a.x and a.halo hold
 hipError_t channelizer_launch(unsigned K, unsigned P, unsigned in_fmt, const ChanArgs &a, hipStream_t st);
 
 // ---------------------------------------------------------------- ofdmsync.hip

@@ -9,6 +9,7 @@
 #include "devmath.h"
 #include "devscope.hpp"
 #include "kernels.h"
+#include "sc16.hpp"
 #include "txcode.hpp"
 
 #include <algorithm>
@@ -207,9 +208,9 @@ struct mcrx_hip_s {
     uint64_t total_samples = 0;             // wideband samples accepted since creation (NCO phase)
     uint64_t stage_first = 0;               // absolute index of h_stage[0]
     int64_t chan_samples = 0;               // channel-rate samples produced since creation
-    // the handle's wideband input format (mcrx_hip_config::input_format == kernels.h: CH_IN_*) and its bytes per sample.  The raw-sample
+    // the handle's wideband input format (mcrx_hip_config::input_format == sc16.hpp: IQ_*) and its bytes per sample.  The raw-sample
     // history, both stagings and the bulk path's device buffers hold samples in that format: bytes, indexed in samples * ss
-    uint32_t in_fmt = CH_IN_CF32; size_t ss = sizeof(float2);
+    uint32_t in_fmt = IQ_CF32; size_t ss = sizeof(float2);
     char *d_hist[2] = { nullptr, nullptr }; int hist_cur = 0;
     char *d_in = nullptr;                   // device staging (stage_cap samples)
     char *h_stage = nullptr; size_t stage_cap = 0, stage_fill = 0;     // pinned host staging (samples)
@@ -600,10 +601,10 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
     const bool bypass = ec.single_channel != 0;
     if (bypass && N != 1) return fail(MCRX_EINVAL, "single_channel needs num_channels == 1");
     const uint32_t in_fmt = ec.input_format;
-    if (in_fmt != CH_IN_CF32 && in_fmt != CH_IN_SC16) return fail(MCRX_EINVAL, "input_format must be 0 (cf32) or 1 (sc16)");
+    if (in_fmt != IQ_CF32 && in_fmt != IQ_SC16) return fail(MCRX_EINVAL, "input_format must be 0 (cf32) or 1 (sc16)");
     // sc16 ends where the channelizer's oscillator multiplies: configurations without channelizer_kernel in front take cf32 only
-    if (in_fmt == CH_IN_SC16 && bypass) return fail(MCRX_EUNSUPP, "input_format = 1 (sc16) needs the channelizer: not with single_channel");
-    if (in_fmt == CH_IN_SC16 && ec.front_end == 2)
+    if (in_fmt == IQ_SC16 && bypass) return fail(MCRX_EUNSUPP, "input_format = 1 (sc16) needs the channelizer: not with single_channel");
+    if (in_fmt == IQ_SC16 && ec.front_end == 2)
         return fail(MCRX_EUNSUPP, "input_format = 1 (sc16) is not built for front_end = 2 (the oversampled front end stage by stage)");
     if (!bypass && !channelizer_supported(2 * N)) return fail(MCRX_EUNSUPP, "at most 1024 channels");
     if (M > 1024) return fail(MCRX_EUNSUPP, "at most 1024 subcarriers");
@@ -614,7 +615,7 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
     mcrx_hip_t q = new mcrx_hip_s();
     q->device = current_device();
     q->N = N; q->K = bypass ? 1 : 2 * N; q->M = M; q->cp = cp; q->taper = taper; q->bypass = bypass;
-    q->in_fmt = in_fmt; q->ss = in_fmt == CH_IN_SC16 ? 2 * sizeof(int16_t) : sizeof(float2);
+    q->in_fmt = in_fmt; q->ss = in_fmt == IQ_SC16 ? 2 * sizeof(int16_t) : sizeof(float2);
     if (q->od.init(M, cp, taper, p) != 0) { delete q; return fail(MCRX_EINVAL, "invalid subcarrier allocation"); }
     q->cfg = ec;
     q->max_payload = q->cfg.max_payload_len ? q->cfg.max_payload_len : 2048;
@@ -1247,7 +1248,7 @@ static int run_blocks(mcrx_hip_t q, const void *x, size_t nblocks, uint64_t firs
     if (!q->bypass && !q->oversampled) {
         const uint64_t nh = (uint64_t)q->hist_blocks * q->K;
         const dim3 hg((unsigned)((nh + 255) / 256));
-        if (q->in_fmt == CH_IN_SC16)
+        if (q->in_fmt == IQ_SC16)
             hipLaunchKernelGGL(hist_update_kernel<uint32_t>, hg, dim3(256), 0, sc, reinterpret_cast<const uint32_t *>(q->d_hist[q->hist_cur]),
                                static_cast<const uint32_t *>(x), (uint64_t)nblocks * q->K, reinterpret_cast<uint32_t *>(q->d_hist[1 - q->hist_cur]), nh);
         else
@@ -1376,14 +1377,14 @@ extern "C" int mcrx_hip_execute_host(mcrx_hip_t q, const float *iq, size_t nsamp
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q || (!iq && nsamples)) return fail(MCRX_EINVAL, "null argument");
-    if (q->in_fmt != CH_IN_CF32) return fail(MCRX_EINVAL, k_fmt_mismatch);
+    if (q->in_fmt != IQ_CF32) return fail(MCRX_EINVAL, k_fmt_mismatch);
     return execute_host_any(q, reinterpret_cast<const char *>(iq), nsamples);
 }
 extern "C" int mcrx_hip_execute_host_sc16(mcrx_hip_t q, const int16_t *iq, size_t nsamples)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q || (!iq && nsamples)) return fail(MCRX_EINVAL, "null argument");
-    if (q->in_fmt != CH_IN_SC16) return fail(MCRX_EINVAL, k_fmt_mismatch);
+    if (q->in_fmt != IQ_SC16) return fail(MCRX_EINVAL, k_fmt_mismatch);
     return execute_host_any(q, reinterpret_cast<const char *>(iq), nsamples);
 }
 
@@ -1410,14 +1411,14 @@ extern "C" int mcrx_hip_execute_device(mcrx_hip_t q, const void *d_iq, size_t ns
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q || (!d_iq && nsamples)) return fail(MCRX_EINVAL, "null argument");
-    if (q->in_fmt != CH_IN_CF32) return fail(MCRX_EINVAL, k_fmt_mismatch);
+    if (q->in_fmt != IQ_CF32) return fail(MCRX_EINVAL, k_fmt_mismatch);
     return execute_device_any(q, d_iq, nsamples, stream);
 }
 extern "C" int mcrx_hip_execute_device_sc16(mcrx_hip_t q, const void *d_iq, size_t nsamples, void *stream)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q || (!d_iq && nsamples)) return fail(MCRX_EINVAL, "null argument");
-    if (q->in_fmt != CH_IN_SC16) return fail(MCRX_EINVAL, k_fmt_mismatch);
+    if (q->in_fmt != IQ_SC16) return fail(MCRX_EINVAL, k_fmt_mismatch);
     return execute_device_any(q, d_iq, nsamples, stream);
 }
 

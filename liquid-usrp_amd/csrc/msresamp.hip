@@ -22,7 +22,7 @@
 #include "../../include/mcrx_hip.h"
 #include "design.hpp"
 #include "devscope.hpp"
-#include "sc16_out.hpp"
+#include "sc16.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -41,38 +41,33 @@ using namespace mcrx;
 #define RS_OB 1024                  // outputs per workgroup (256 threads x 4)
 #define RS_HROW 16                  // floats per row of the padded branch table (14 taps + 2): one row = 4 x 16-B loads
 
-// Input formats of the caller's buffer (template parameter FMT of the kernels that can be a first stage; msresamp_hip_set_input_format).
-// An sc16 sample is one 32-bit word, int16 re in the low half and int16 im in the high half -- the word channelizer.hip reads -- and
-// means (re, im) * 2^-15: conversion and scaling are exact in fp32 for every int16.  The word stays packed from the load to the store
+// Input formats of the caller's buffer (template parameter FMT of the kernels that can be a first stage; msresamp_hip_set_input_format):
+// IQ_CF32 / IQ_SC16, an sc16 sample as sc16.hpp defines it.  The word stays packed from the load to the store
 // into the LDS span (rs_cvt), half the bytes and half the registers of a cf32 sample in flight; behind that store the source is the
 // cf32 build's, so that the two formats share every later rounding.  Only the caller's buffer and its retained tail (in[0]) are in
 // the handle's format: every later stage buffer is cf32.
-#define RS_IN_CF32 0
-#define RS_IN_SC16 1
 // Output formats of the caller's buffer (msresamp_hip_set_output_format), in the kernels that can be a last stage.
 // Let y be the fp32 value the stage computes for one component.  The store to the caller's buffer is v = y * gain (one multiply of its
-// own; gain = 1 stores y) as cf32, or Q(v) as sc16: the transmitter's quantiser and clip count (sc16_out.hpp), one packed 4-byte word
+// own; gain = 1 stores y) as cf32, or Q(v) as sc16: the shared quantiser and clip count (sc16.hpp), one packed 4-byte word
 // a sample.  Only that store knows the format: stage buffers between the kernels are cf32 and are written with gain = 1.
 // In the builds that can store sc16 (template parameter SC16) the format is a run-time choice at the store (clip != NULL: sc16), inside
 // one body that keeps the cf32 store, as in txgen.hip's txfir_column and for its reason: a build that ended in the 4-byte store alone
 // contracted the multiply-adds of the tap sums differently from its cf32 twin (more than half of them left as a multiply and an add),
 // and Q is a function of the cf32 value only if that value is the same.  With both stores in the body the sums compile to the cf32
 // build's fused multiply-adds.  The builds without SC16 are the cf32 handles': no branch, no clip count, the parent's registers.
-#define RS_OUT_CF32 0
-#define RS_OUT_SC16 1
 template <int FMT> struct RsElem { typedef float2 type; };
-template <> struct RsElem<RS_IN_SC16> { typedef uint32_t type; };
+template <> struct RsElem<IQ_SC16> { typedef uint32_t type; };
 
 // A stage input: samples [tail_base, cur_base) in `tail` (the retained end of the previous call's input, may be NULL),
 // [cur_base, end) in `cur`; everything before sample 0 is zero.
 template <int FMT> struct RsInT { const typename RsElem<FMT>::type *tail; long long tail_base; const typename RsElem<FMT>::type *cur; long long cur_base, end; };
-typedef RsInT<RS_IN_CF32> RsIn;
+typedef RsInT<IQ_CF32> RsIn;
 
 __device__ __forceinline__ float2 rs_cvt(float2 v) { return v; }
-__device__ __forceinline__ float2 rs_cvt(uint32_t w) { return make_float2((float)(int16_t)(w & 0xffffu) * 0x1p-15f, (float)((int32_t)w >> 16) * 0x1p-15f); }
+__device__ __forceinline__ float2 rs_cvt(uint32_t w) { return sc16_unpack(w); }
 template <int FMT> __device__ __forceinline__ typename RsElem<FMT>::type rs_zero()
 {
-    if constexpr (FMT == RS_IN_SC16) return 0u; else return make_float2(0.f, 0.f);
+    if constexpr (FMT == IQ_SC16) return 0u; else return make_float2(0.f, 0.f);
 }
 
 // sample t as it lies in memory (sc16: the packed word; the zero word is the zero sample)
@@ -234,10 +229,10 @@ __global__ __launch_bounds__(256) void arbitrary_kernel(RsInT<FMT> in, float2 *o
             // (sc16: a pair is 8 bytes, and what has to line up is the pair's own address -- a buffer that is only 4-byte aligned takes
             //  this path whenever tb falls on an odd sample of it)
             bool whole = tb >= in.cur_base && tb + 2 * (long long)nq <= in.end;
-            if constexpr (FMT == RS_IN_SC16) whole = whole && ((reinterpret_cast<size_t>(in.cur + (tb - in.cur_base)) & 7) == 0);
+            if constexpr (FMT == IQ_SC16) whole = whole && ((reinterpret_cast<size_t>(in.cur + (tb - in.cur_base)) & 7) == 0);
             else whole = whole && (((tb - in.cur_base) & 1) == 0) && ((reinterpret_cast<size_t>(in.cur) & 15) == 0);
             if (whole) {
-                if constexpr (FMT == RS_IN_SC16) {
+                if constexpr (FMT == IQ_SC16) {
                     const uint2 *src = reinterpret_cast<const uint2 *>(in.cur + (tb - in.cur_base));
 #pragma unroll
                     for (int i = 0; i < RS_PER; i++) {
@@ -388,14 +383,12 @@ struct msresamp_hip_s {
     long long out_count = 0;        // outputs of the arbitrary stage produced so far (j), less the whole periods taken off by rs_rebase
     long long per_in = 1, per_out = 1;      // one period of the phase: step / g inputs, 2^24 / g outputs of the arbitrary stage
     hipStream_t stream = nullptr;
-    unsigned in_fmt = RS_IN_CF32;   // format of the caller's samples and of in[0], their retained tail (msresamp_hip_set_input_format)
+    unsigned in_fmt = IQ_CF32;   // format of the caller's samples and of in[0], their retained tail (msresamp_hip_set_input_format)
     // The caller's output (msresamp_hip_set_output_format, _set_output_gain): read at every call and nowhere retained -- no stage buffer
     // is an output buffer -- so both may change between any two calls.
-    unsigned out_fmt = RS_OUT_CF32;
+    unsigned out_fmt = IQ_CF32;
     float out_gain = 1.0f;
-    unsigned long long *d_clip = nullptr;               // clipped samples since sc16 output was first selected (device, 64 bits)
-    unsigned long long clip_base = 0;                   // ... of them, already reported and reset (msresamp_hip_clipped)
-    hipEvent_t clip_ev = nullptr; bool clip_pending = false;    // recorded behind the last sc16-output call's kernels
+    Sc16ClipCount clip;         // allocated when sc16 output is first selected; marked behind the last sc16-output call's kernels
     hipEvent_t ev_first[2] = { nullptr, nullptr };      // msresamp_hip_time_first_stage: around the launch that reads the caller's samples
     bool time_first = false, timed_first = false;
 };
@@ -416,7 +409,7 @@ static int stage_reserve(msresamp_hip_t q, StageBuf &b, size_t extra, hipStream_
     if (keep + extra <= b.cap) {                        // slide the tail to the front (stream ordered, no allocation)
         if (keep) {
             const RsIn me = { nullptr, 0, b.d, b.base, b.end };
-            hipLaunchKernelGGL(tail_save_kernel<RS_IN_CF32>, dim3(1), dim3(RS_KEEP), 0, st, me, b.d, b.end - (long long)keep);
+            hipLaunchKernelGGL(tail_save_kernel<IQ_CF32>, dim3(1), dim3(RS_KEEP), 0, st, me, b.d, b.end - (long long)keep);
             RSCHK(hipGetLastError());
         }
         b.base = b.end - (long long)keep;
@@ -509,8 +502,7 @@ extern "C" int msresamp_hip_destroy(msresamp_hip_t q)
     (void)hipFree(q->d_h1); (void)hipFree(q->d_hpfb);
     if (q->stream) (void)hipStreamDestroy(q->stream);
     for (hipEvent_t e : q->ev_first) if (e) (void)hipEventDestroy(e);
-    if (q->d_clip) (void)hipFree(q->d_clip);
-    if (q->clip_ev) (void)hipEventDestroy(q->clip_ev);
+    q->clip.release();
     delete q;
     return MCRX_OK;
 }
@@ -552,7 +544,7 @@ extern "C" size_t msresamp_hip_max_output(msresamp_hip_t q, size_t nin)
 extern "C" int msresamp_hip_set_input_format(msresamp_hip_t q, unsigned format)
 {
     if (!q) { g_rs_err = "null argument"; return MCRX_EINVAL; }
-    if (format != RS_IN_CF32 && format != RS_IN_SC16) { g_rs_err = "msresamp: input format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
+    if (format != IQ_CF32 && format != IQ_SC16) { g_rs_err = "msresamp: input format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
     if (q->in[0].end > q->in[0].base) { g_rs_err = "msresamp: the input format cannot change while the handle holds input history (reset first)"; return MCRX_EBUSY; }
     q->in_fmt = format;
     return MCRX_OK;
@@ -567,16 +559,8 @@ extern "C" int msresamp_hip_set_output_format(msresamp_hip_t q, unsigned format)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_rs_err = "null argument"; return MCRX_EINVAL; }
-    if (format != RS_OUT_CF32 && format != RS_OUT_SC16) { g_rs_err = "msresamp: output format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
-    if (format == RS_OUT_SC16 && !q->d_clip) {
-        unsigned long long *d = nullptr;
-        RSCHK(hipMalloc((void **)&d, sizeof(unsigned long long)));
-        if (hipMemset(d, 0, sizeof(unsigned long long)) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipEventCreateWithFlags(&q->clip_ev, hipEventDisableTiming) != hipSuccess) {
-            (void)hipFree(d); g_rs_err = "device allocation failed"; return MCRX_EHIP;
-        }
-        q->d_clip = d;
-    }
+    if (format != IQ_CF32 && format != IQ_SC16) { g_rs_err = "msresamp: output format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
+    if (format == IQ_SC16) RSCHK(q->clip.ensure());
     q->out_fmt = format;
     return MCRX_OK;
 }
@@ -600,13 +584,7 @@ extern "C" int msresamp_hip_clipped(msresamp_hip_t q, uint64_t *samples, int res
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_rs_err = "null argument"; return MCRX_EINVAL; }
     uint64_t n = 0;
-    if (q->d_clip) {
-        if (q->clip_pending) { RSCHK(hipEventSynchronize(q->clip_ev)); q->clip_pending = false; }
-        unsigned long long seen = 0;
-        RSCHK(hipMemcpy(&seen, q->d_clip, sizeof(seen), hipMemcpyDeviceToHost));
-        n = seen - q->clip_base;
-        if (reset) q->clip_base = seen;
-    }
+    RSCHK(q->clip.read(&n, reset != 0));        // (whatever the format is now)
     if (samples) *samples = n;
     return MCRX_OK;
 }
@@ -640,7 +618,7 @@ static int rs_execute(msresamp_hip_t q, const void *d_in, size_t nin, void *d_ou
     DevScope dev_scope_(q ? q->device : -1);
     if (!q || !nout || (!d_in && nin) || !d_out) { g_rs_err = "null argument"; return MCRX_EINVAL; }
     if (q->in_fmt != (unsigned)FMT) {       // (before anything is counted: the call consumes nothing)
-        g_rs_err = FMT == RS_IN_SC16 ? "msresamp: input format mismatch, an sc16 call on a cf32 handle (msresamp_hip_set_input_format)"
+        g_rs_err = FMT == IQ_SC16 ? "msresamp: input format mismatch, an sc16 call on a cf32 handle (msresamp_hip_set_input_format)"
                                      : "msresamp: input format mismatch, a cf32 call on an sc16 handle (msresamp_hip_execute_device_sc16)";
         return MCRX_EINVAL;
     }
@@ -650,13 +628,11 @@ static int rs_execute(msresamp_hip_t q, const void *d_in, size_t nin, void *d_ou
     hipStream_t st = (hipStream_t)stream;
     *nout = 0;
     // the last stage's store: the handle's format and gain as they are now (sc16: any 4-byte-aligned d_out)
-    const bool sc16_out = q->out_fmt == RS_OUT_SC16;
+    const bool sc16_out = q->out_fmt == IQ_SC16;
     if (sc16_out && (reinterpret_cast<uintptr_t>(d_out) & 3u)) { g_rs_err = "sc16 output must be 4-byte aligned"; return MCRX_EINVAL; }
-    const RsOut caller = { d_out, q->out_gain, sc16_out ? q->d_clip : nullptr };
+    const RsOut caller = { d_out, q->out_gain, sc16_out ? q->clip.device() : nullptr };
     auto clip_mark = [&]() -> int {         // behind the launch that wrote the caller's sc16 samples: what msresamp_hip_clipped waits for
-        if (!sc16_out) return MCRX_OK;
-        RSCHK(hipEventRecord(q->clip_ev, st));
-        q->clip_pending = true;
+        if (sc16_out) RSCHK(q->clip.mark(st));
         return MCRX_OK;
     };
     rs_rebase(q);
@@ -740,7 +716,7 @@ static int rs_execute(msresamp_hip_t q, const void *d_in, size_t nin, void *d_ou
             if ((rc = stage_reserve(q, bo, (size_t)(k1 - k0), st))) return rc;
             const unsigned n = (unsigned)(k1 - k0);
             float2 *o = bo.d + (bo.end - bo.base);
-            if (s) hipLaunchKernelGGL(halfband_kernel<RS_IN_CF32>, dim3((n + OB - 1) / OB), dim3(256), 0, st, stage_in(q->in[s]), o, k0, k1, q->d_h1);
+            if (s) hipLaunchKernelGGL(halfband_kernel<IQ_CF32>, dim3((n + OB - 1) / OB), dim3(256), 0, st, stage_in(q->in[s]), o, k0, k1, q->d_h1);
             else { FirstStageTimer timer(q, st); hipLaunchKernelGGL(halfband_kernel<FMT>, dim3((n + OB - 1) / OB), dim3(256), 0, st, src0, o, k0, k1, q->d_h1); }
             RSCHK(hipGetLastError());
             bo.end = k1;
@@ -773,11 +749,11 @@ static int rs_execute(msresamp_hip_t q, const void *d_in, size_t nin, void *d_ou
 
 extern "C" int msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out,
                                            size_t out_cap, size_t *nout, void *stream)
-{ return rs_execute<RS_IN_CF32>(q, d_in, nin, d_out, out_cap, nout, stream); }
+{ return rs_execute<IQ_CF32>(q, d_in, nin, d_out, out_cap, nout, stream); }
 
 // the same for a handle whose input format is sc16: nin samples = 2 * nin int16 (any 4-byte-aligned d_in)
 extern "C" int msresamp_hip_execute_device_sc16(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out,
                                                 size_t out_cap, size_t *nout, void *stream)
-{ return rs_execute<RS_IN_SC16>(q, d_in, nin, d_out, out_cap, nout, stream); }
+{ return rs_execute<IQ_SC16>(q, d_in, nin, d_out, out_cap, nout, stream); }
 
 extern "C" const char *msresamp_hip_last_error(void) { return g_rs_err.c_str(); }

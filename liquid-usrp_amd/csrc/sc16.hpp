@@ -1,5 +1,6 @@
-// sc16_out.hpp -- the transmitter's 16-bit integer output format (mctx_hip_set_output_format(q, 1)), defined once.
-//
+// sc16.hpp -- 16-bit integer IQ (sc16), defined once.  A sample is one 32-bit word: int16 re in the low half, im in the high half.
+// Input (sc16_unpack): the word means (re, im) * 2^-15; conversion to fp32 and scaling are both exact for every int16.
+// Output (transmitter, resampler, channel emulator):
 // Let v be the fp32 value a cf32 transmitter stores for one component (behind the oscillator and the gain).  An sc16 transmitter stores
 //   Q(v) = clamp(r, -32768, 32767),  r = rint(v * 32768.0f)      round half to even, in fp32; the multiply is exact
 // so Q is a function of the cf32 output alone.  NaN stores 0, infinities saturate.  A SAMPLE is clipped when r lies outside
@@ -11,11 +12,17 @@
 // saturating pack v_cvt_pk_i16_i32.  The clip test works on the int32s: r + 32768 as an unsigned number is > 65535 exactly outside the
 // range, the saturated infinities included.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace mcrx {
 
-enum { TX_CF32 = 0, TX_SC16 = 1 };      // mctx_hip_set_output_format
+enum { IQ_CF32 = 0, IQ_SC16 = 1 };      // input or output
+
+__device__ __forceinline__ float2 sc16_unpack(uint32_t w)
+{
+    return make_float2((float)(int16_t)(w & 0xffffu) * 0x1p-15f, (float)((int32_t)w >> 16) * 0x1p-15f);
+}
 
 __device__ __forceinline__ int sc16_round(float v)
 {
@@ -43,5 +50,46 @@ __device__ __forceinline__ void sc16_clip_commit(unsigned long long *counter, ui
     for (int o = 32; o >= 1; o >>= 1) nclip += (uint32_t)__shfl_xor((int)nclip, o, 64);
     if ((threadIdx.x & 63u) == 0u) atomicAdd(counter, (unsigned long long)nclip);
 }
+
+// Host side of the count.  Kernels add to *device(); read() waits for the last mark() only.
+struct Sc16ClipCount {
+    unsigned long long *d_clip = nullptr, clip_base = 0;        // clip_base: already reported and reset
+    hipEvent_t clip_ev = nullptr; bool clip_pending = false;
+
+    unsigned long long *device() const { return d_clip; }
+    hipError_t ensure()         // all or nothing; no-op once the counter exists
+    {
+        if (d_clip) return hipSuccess;
+        unsigned long long *d = nullptr; hipEvent_t ev = nullptr;
+        hipError_t e = hipMalloc((void **)&d, sizeof(*d));
+        if (e == hipSuccess) e = hipMemset(d, 0, sizeof(*d));
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e == hipSuccess) { d_clip = d; clip_ev = ev; } else (void)hipFree(d);
+        return e;
+    }
+    hipError_t mark(hipStream_t st)     // behind the launch that stored sc16
+    {
+        const hipError_t e = hipEventRecord(clip_ev, st);
+        clip_pending = clip_pending || e == hipSuccess;
+        return e;
+    }
+    hipError_t read(uint64_t *n, bool reset)    // 0, device untouched, if ensure() never ran
+    {
+        unsigned long long seen = clip_base;
+        hipError_t e = hipSuccess;
+        if (clip_pending && (e = hipEventSynchronize(clip_ev)) == hipSuccess) clip_pending = false;
+        if (d_clip && e == hipSuccess) e = hipMemcpy(&seen, d_clip, sizeof(seen), hipMemcpyDeviceToHost);
+        *n = seen - clip_base;
+        if (reset) clip_base = seen;
+        return e;
+    }
+    void release()
+    {
+        if (d_clip) (void)hipFree(d_clip);
+        if (clip_ev) (void)hipEventDestroy(clip_ev);
+        *this = Sc16ClipCount();
+    }
+};
 
 }  // namespace mcrx

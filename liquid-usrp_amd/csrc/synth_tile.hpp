@@ -120,9 +120,9 @@ __host__ __device__ inline bool syn_aligned(const TxSynthArgs &a)
 {
     return !a.tiles && !a.ft0 && (a.L % 8) == 0 && (a.cp % 8) == 0 && (a.M % 8) == 0 && a.taper >= 0 && a.taper <= 4;
 }
-// FMT: what is stored -- TX_CF32 one float4 of two samples per lane and block, TX_SC16 the same two samples through sc16_sample
-// (sc16_out.hpp) as one 8-byte store, the clipped ones counted in a register and committed once per wave behind the last round
-template <int K, int R, int IN, int FMT = TX_CF32>
+// FMT: what is stored -- IQ_CF32 one float4 of two samples per lane and block, IQ_SC16 the same two samples through sc16_sample
+// (sc16.hpp) as one 8-byte store, the clipped ones counted in a register and committed once per wave behind the last round
+template <int K, int R, int IN, int FMT = IQ_CF32>
 __global__ __launch_bounds__(K / 2) void synth_kernel(TxSynthArgs a, uint32_t slab_blocks)
 {
     constexpr int T = K / 2, N = K / 2, C = 2;
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(K / 2) void synth_kernel(TxSynthArgs a, uint32_t sl
 #pragma unroll
         for (int c = 0; c < C; c++) s[i][c] = make_float2(0.f, 0.f);
     char *outb = reinterpret_cast<char *>(a.out);
-    constexpr size_t OSZ = FMT == TX_SC16 ? sizeof(uint32_t) : sizeof(float2);      // bytes of a stored sample
+    constexpr size_t OSZ = FMT == IQ_SC16 ? sizeof(uint32_t) : sizeof(float2);      // bytes of a stored sample
     const uint32_t ooff = (uint32_t)n0 * (uint32_t)OSZ;
     uint32_t nclip = 0;                                             // (sc16) clipped samples of this lane
     // Oscillator e^{+j t dtheta}: exact 32-bit phase through v_sin / v_cos at the first column of every group of 8 blocks
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(K / 2) void synth_kernel(TxSynthArgs a, uint32_t sl
                     const float s1 = fmaf(osn, cd1, ocs * sd1), c1 = fmaf(ocs, cd1, -(osn * sd1));            // the second column
                     const float2 y0 = make_float2(fmaf(acc[r][0].x, ocs, -(acc[r][0].y * osn)), fmaf(acc[r][0].y, ocs, acc[r][0].x * osn));
                     const float2 y1 = make_float2(fmaf(acc[r][1].x, c1, -(acc[r][1].y * s1)), fmaf(acc[r][1].y, c1, acc[r][1].x * s1));
-                    if constexpr (FMT == TX_SC16) {
+                    if constexpr (FMT == IQ_SC16) {
                         *reinterpret_cast<uint2 *>(uniform_ptr(outb + (size_t)(b - (long long)a.out_first) * K * OSZ) + ooff) =
                             make_uint2(sc16_sample(y0.x * a.gain, y0.y * a.gain, nclip), sc16_sample(y1.x * a.gain, y1.y * a.gain, nclip));
                     } else {
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(K / 2) void synth_kernel(TxSynthArgs a, uint32_t sl
         }
         lds_barrier();
     }
-    if constexpr (FMT == TX_SC16) sc16_clip_commit(a.clip, nclip);
+    if constexpr (FMT == IQ_SC16) sc16_clip_commit(a.clip, nclip);
 }
 
 }  // namespace syn

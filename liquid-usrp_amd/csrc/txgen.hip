@@ -19,7 +19,7 @@
 #include "devmath.h"
 #include "txcode.hpp"
 #include "devscope.hpp"
-#include "sc16_out.hpp"
+#include "sc16.hpp"
 #include <random>
 #include <string>
 #include <vector>
@@ -361,7 +361,7 @@ struct TxSynthArgs {
     uint32_t out_first = 0;       // blocks in front of this one only feed the filter: out holds blocks >= out_first
     // ragged traffic: symkind[ch][S] (TXK_*), frames = 1, S = symbols of the whole axis
     const uint8_t *symkind = nullptr;
-    // sc16 output (sc16_out.hpp): `out` then holds 4-byte samples, and the clipped ones are added to *clip
+    // sc16 output (sc16.hpp): `out` then holds 4-byte samples, and the clipped ones are added to *clip
     unsigned long long *clip = nullptr;
 };
 
@@ -583,7 +583,7 @@ using namespace mcrx;
 
 static thread_local std::string g_tx_err;
 // the host paths that produce a block or a frame at a time have no gain to put the full scale against: they stay cf32
-#define TX_SC16_UNSUPP "sc16 output covers mctx_hip_generate, _generate_ragged and _synthesize_tiles; the streaming interface and mctx_hip_frame are cf32 only"
+#define TX_NO_SC16 "sc16 output covers mctx_hip_generate, _generate_ragged and _synthesize_tiles; the streaming interface and mctx_hip_frame are cf32 only"
 #define TXCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_tx_err = std::string(#x) + ": " + hipGetErrorString(e_); return MCRX_EHIP; } } while (0)
 
 struct mctx_hip_s {
@@ -609,11 +609,9 @@ struct mctx_hip_s {
     long long period = 0, blocks_out = 0; unsigned out_pos = 0;
     hipStream_t sst = nullptr;
     float2 *d_synv = nullptr; size_t syn_cap = 0;       // sharded synthesis: inverse-FFT outputs of one slab (+ lead)
-    // ---- output format (mctx_hip_set_output_format): TX_CF32, or TX_SC16 with its count of clipped samples
-    unsigned out_fmt = TX_CF32;
-    unsigned long long *d_clip = nullptr;               // clipped samples since the handle was made (device, 64 bits)
-    unsigned long long clip_base = 0;                   // ... of them, already reported and reset (mctx_hip_clipped)
-    hipEvent_t clip_ev = nullptr; bool clip_pending = false;    // recorded behind the last sample-producing launch
+    // ---- output format (mctx_hip_set_output_format): IQ_CF32, or IQ_SC16 with its count of clipped samples
+    unsigned out_fmt = IQ_CF32;
+    Sc16ClipCount clip;         // allocated when sc16 is first selected; marked behind the last sample-producing launch (mctx_hip_clipped)
     template <class T> int up(const T **dst, const T *src, size_t n)
     {
         T *p = nullptr;
@@ -676,8 +674,7 @@ extern "C" int mctx_hip_destroy(mctx_hip_t q)
     for (void *p : { (void *)q->d_shdr, (void *)q->d_spay, (void *)q->d_sxsym, (void *)q->d_ft0, (void *)q->d_fS,
                      (void *)q->d_sv[0], (void *)q->d_sv[1], (void *)q->d_sout, (void *)q->d_synv }) if (p) (void)hipFree(p);
     if (q->h_sout) (void)hipHostFree(q->h_sout);
-    if (q->d_clip) (void)hipFree(q->d_clip);
-    if (q->clip_ev) (void)hipEventDestroy(q->clip_ev);
+    q->clip.release();
     if (q->sst) (void)hipStreamDestroy(q->sst);
     delete q;
     return MCRX_OK;
@@ -1062,9 +1059,9 @@ template <int KK, int R, int IN>
 static int tx_launch_fused_in(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t st)
 {
     if constexpr (KK < 512 || R == 8) {     // (sc16 has no rounds of 4 at K >= 512 -- a development switch of the cf32 kernels: tx_synthesize_fmt)
-        if (ya.clip) return tx_launch_fused_fmt<KK, R, IN, TX_SC16>(q, ya, st);
+        if (ya.clip) return tx_launch_fused_fmt<KK, R, IN, IQ_SC16>(q, ya, st);
     }
-    return tx_launch_fused_fmt<KK, R, IN, TX_CF32>(q, ya, st);
+    return tx_launch_fused_fmt<KK, R, IN, IQ_CF32>(q, ya, st);
 }
 // the input side of the kernel is a compile-time choice (three loaders in one body spilled the window): exchanged granules,
 // the aligned symbol loader (rounds of 8 blocks only), or the block-by-block walk
@@ -1100,13 +1097,12 @@ static int tx_synthesize_fmt(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t st
 // stream is what mctx_hip_clipped waits for.
 static int tx_synthesize(mctx_hip_t q, const TxSynthArgs &ya, hipStream_t st)
 {
-    if (q->out_fmt != TX_SC16) return tx_synthesize_fmt(q, ya, st);
+    if (q->out_fmt != IQ_SC16) return tx_synthesize_fmt(q, ya, st);
     if (reinterpret_cast<uintptr_t>(ya.out) & 7u) { g_tx_err = "sc16 output must be 8-byte aligned"; return MCRX_EINVAL; }
     TxSynthArgs yi = ya;
-    yi.clip = q->d_clip;
+    yi.clip = q->clip.device();
     { int rc = tx_synthesize_fmt(q, yi, st); if (rc) return rc; }
-    TXCHK(hipEventRecord(q->clip_ev, st));
-    q->clip_pending = true;
+    TXCHK(q->clip.mark(st));
     return MCRX_OK;
 }
 
@@ -1114,14 +1110,9 @@ extern "C" int mctx_hip_set_output_format(mctx_hip_t q, unsigned format)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_tx_err = "null handle"; return MCRX_EINVAL; }
-    if (format != TX_CF32 && format != TX_SC16) { g_tx_err = "output format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
+    if (format != IQ_CF32 && format != IQ_SC16) { g_tx_err = "output format must be 0 (cf32) or 1 (sc16)"; return MCRX_EINVAL; }
     if (q->st_on) { g_tx_err = "the output format cannot change once the streaming interface has started"; return MCRX_EBUSY; }
-    if (format == TX_SC16 && !q->d_clip) {
-        TXCHK(hipMalloc((void **)&q->d_clip, sizeof(unsigned long long)));
-        TXCHK(hipMemset(q->d_clip, 0, sizeof(unsigned long long)));
-        TXCHK(hipDeviceSynchronize());
-        TXCHK(hipEventCreateWithFlags(&q->clip_ev, hipEventDisableTiming));
-    }
+    if (format == IQ_SC16) TXCHK(q->clip.ensure());
     q->out_fmt = format;
     return MCRX_OK;
 }
@@ -1133,13 +1124,7 @@ extern "C" int mctx_hip_clipped(mctx_hip_t q, uint64_t *samples, int reset)
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_tx_err = "null handle"; return MCRX_EINVAL; }
     uint64_t n = 0;
-    if (q->out_fmt == TX_SC16) {
-        if (q->clip_pending) { TXCHK(hipEventSynchronize(q->clip_ev)); q->clip_pending = false; }
-        unsigned long long seen = 0;
-        TXCHK(hipMemcpy(&seen, q->d_clip, sizeof(seen), hipMemcpyDeviceToHost));
-        n = seen - q->clip_base;
-        if (reset) q->clip_base = seen;
-    }
+    if (q->out_fmt == IQ_SC16) TXCHK(q->clip.read(&n, reset != 0));      // (a cf32 handle reports 0; what sc16 calls counted stays)
     if (samples) *samples = n;
     return MCRX_OK;
 }
@@ -1190,7 +1175,7 @@ extern "C" int mctx_hip_stream_begin(mctx_hip_t q, unsigned max_payload_len)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_tx_err = "null handle"; return MCRX_EINVAL; }
-    if (q->out_fmt == TX_SC16) { g_tx_err = TX_SC16_UNSUPP; return MCRX_EUNSUPP; }
+    if (q->out_fmt == IQ_SC16) { g_tx_err = TX_NO_SC16; return MCRX_EUNSUPP; }
     const unsigned N = q->N, M = q->M, K = q->K, L = M + q->cp, Md = q->od.M_data;
     // slots for the longest frame a payload of this size can make: BPSK behind two rate-1/2 codes
     unsigned Sh, Sp, S; frame_geometry(q, max_payload_len, 39, 7, 7, Sh, Sp, S);
@@ -1240,7 +1225,7 @@ extern "C" int mctx_hip_stream_update(mctx_hip_t q, unsigned ch, const uint8_t *
                                       int mod, int fec0, int fec1)
 {
     DevScope dev_scope_(q ? q->device : -1);
-    if (q && q->out_fmt == TX_SC16) { g_tx_err = TX_SC16_UNSUPP; return MCRX_EUNSUPP; }
+    if (q && q->out_fmt == IQ_SC16) { g_tx_err = TX_NO_SC16; return MCRX_EUNSUPP; }
     if (!q || !q->st_on || !header8 || (!payload && payload_len)) { g_tx_err = "bad argument"; return MCRX_EINVAL; }
     if (ch >= q->N) { g_tx_err = "error: multichanneltx::UpdateData(), invalid channel id"; return MCRX_EINVAL; }
     if (!mod_bps(mod)) { g_tx_err = "unsupported modulation scheme"; return MCRX_EUNSUPP; }
@@ -1304,7 +1289,7 @@ static int tx_stream_period(mctx_hip_t q)
 extern "C" int mctx_hip_stream_generate(mctx_hip_t q, float *out)
 {
     DevScope dev_scope_(q ? q->device : -1);
-    if (q && q->out_fmt == TX_SC16) { g_tx_err = TX_SC16_UNSUPP; return MCRX_EUNSUPP; }
+    if (q && q->out_fmt == IQ_SC16) { g_tx_err = TX_NO_SC16; return MCRX_EUNSUPP; }
     if (!q || !q->st_on || !out) { g_tx_err = "bad argument"; return MCRX_EINVAL; }
     const unsigned L = q->M + q->cp;
     if (q->out_pos >= L) { int rc = tx_stream_period(q); if (rc) return rc; }
@@ -1329,7 +1314,7 @@ extern "C" int mctx_hip_frame(mctx_hip_t q, const uint8_t *header8, const uint8_
                               int mod, int fec0, int fec1, float gain, float *out, size_t out_cap)
 {
     DevScope dev_scope_(q ? q->device : -1);
-    if (q && q->out_fmt == TX_SC16) { g_tx_err = TX_SC16_UNSUPP; return MCRX_EUNSUPP; }
+    if (q && q->out_fmt == IQ_SC16) { g_tx_err = TX_NO_SC16; return MCRX_EUNSUPP; }
     if (!q || !header8 || (!payload && payload_len) || !out) { g_tx_err = "bad argument"; return MCRX_EINVAL; }
     if (!mod_bps(mod)) { g_tx_err = "unsupported modulation scheme"; return MCRX_EUNSUPP; }
     if (!fec_supported(fec0) || !fec_supported(fec1)) { g_tx_err = "unsupported fec scheme"; return MCRX_EUNSUPP; }

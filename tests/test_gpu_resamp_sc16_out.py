@@ -276,6 +276,34 @@ def test_clipping(product, rate):
     rs.close()
 
 
+def test_clip_count_across_a_format_switch(product):
+    """The resampler's read-out rule: clipped() reports the count whatever the handle's format is now (the transmitter's reports 0
+    while it is cf32: tests/test_gpu_tx_sc16.py), and only sc16 calls add to it."""
+    rate = CLIP_RATES[0]
+    x = ref(product, rate).d_x[:3001]
+    rs_f = product.msresamp(rate)
+    mag = np.abs(rs_f.execute(x).cpu().numpy().view(np.float32))
+    g_clip = float(np.float32(1.0 / np.quantile(mag, 0.9)))
+    rs_f.gain = g_clip
+    rs_f.reset()
+    want = model.clipped_samples(rs_f.execute(x).cpu().numpy())
+    rs_f.close()
+    assert want > 0
+    rs = product.msresamp(rate, output_format="sc16", gain=g_clip)
+    rs.execute(x)
+    assert rs.clipped() == want
+    rs.output_format = "cf32"
+    assert rs.output_format == 0 and rs.clipped() == want
+    rs.reset()
+    rs.execute(x)                                                              # a cf32 call adds nothing
+    assert rs.clipped() == want
+    rs.output_format = "sc16"
+    rs.reset()
+    rs.execute(x)
+    assert rs.clipped() == 2 * want
+    rs.close()
+
+
 # ---------------------------------------------------------------------------------------------- 6. NaN and infinities
 def test_nan_and_infinities(product):
     torch = _torch()

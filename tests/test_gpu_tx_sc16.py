@@ -146,6 +146,29 @@ def test_clipping_is_the_clamp_and_is_counted(product, N):
     tx_f.close(); tx_i.close()
 
 
+def test_clip_count_across_a_format_switch(product):
+    """The transmitter's read-out rule: clipped() is 0 while the handle's format is cf32, and what the sc16 calls counted is still
+    there when the handle is sc16 again (the resampler's rule differs: tests/test_gpu_resamp_sc16_out.py)."""
+    L = product.lib()
+    tx_f, tx_i = pair(product, 8, 64, 8, 4)
+    gain0 = 1.0 / 8
+    x0 = tx_f.generate(1, 20, gain=gain0, seed=31)[0].cpu().numpy()
+    p = float(np.percentile(np.abs(x0.view(np.float32)), 99.0))
+    assert p > 0
+    gain = gain0 / p
+    want = model.clipped_samples(tx_f.generate(1, 20, gain=gain, seed=31)[0].cpu().numpy())
+    assert want > 0
+    tx_i.generate(1, 20, gain=gain, seed=31)
+    assert tx_i.clipped() == want
+    assert L.mctx_hip_set_output_format(tx_i._h, 0) == product.MCRX_OK and tx_i.output_format == 0
+    assert tx_i.clipped() == 0
+    assert L.mctx_hip_set_output_format(tx_i._h, 1) == product.MCRX_OK and tx_i.output_format == 1
+    assert tx_i.clipped() == want
+    assert tx_i.clipped(reset=True) == want
+    assert tx_i.clipped() == 0
+    tx_f.close(); tx_i.close()
+
+
 # ---------------------------------------------------------------------------------------------- 3. the quantiser itself
 def test_selftest_quantise_reaches_ties_and_edges(product):
     _torch()
