@@ -105,6 +105,40 @@ __device__ __forceinline__ int dif_pos(int k)
     return pos + k;
 }
 
+// devmath.h's sincos_u32 with its roundings pinned: the twiddles and oscillator steps below are part of the output's bits, and the
+// polynomials of the plain version are contracted by the compiler as it sees fit per build (as scalars they came out as the Horner
+// chains written here; next to packed consumers two of their fused multiply-adds became a multiply and an add, and a fraction of
+// the K = 1024 outputs moved by an ulp of an intermediate).  Same octant reduction, same coefficients.
+// SEMI: the one exception the released builds contain, kept so that their output bits stay: in the radix-8 plans (K = 512, 1024) the
+// first twiddle of each LDS stage was evaluated with only the innermost step of either polynomial fused (the two evaluations had been
+// vectorised as a pair); polys_semi spells that out with contraction off.
+__device__ __forceinline__ void polys_semi(float a, float a2, float p1, float q1, float &sp, float &cp)
+{
+#pragma clang fp contract(off)
+    const float ps = -1.6666654611e-1f + a2 * p1, pc = 4.166664568298827e-2f + a2 * q1;
+    const float ts = (a * a2) * ps, tc = (a2 * a2) * pc;
+    sp = a + ts;
+    cp = tc + fmaf(a2, -0.5f, 1.0f);
+}
+template <bool SEMI = false>
+__device__ __forceinline__ void sincos_u32_fx(uint32_t th, float &s, float &c)
+{
+    const uint32_t t = th + 0x20000000u, q = t >> 30;
+    const int32_t r = (int32_t)(t & 0x3FFFFFFFu) - 0x20000000;
+    const float a = (float)r * 1.4629180792671596e-09f;          // (pi/2) / 2^30
+    const float a2 = a * a;
+    const float p1 = fmaf(a2, -1.9515295891e-4f, 8.3321608736e-3f), q1 = fmaf(a2, 2.443315711809948e-5f, -1.388731625493765e-3f);
+    float sp, cp;
+    if constexpr (SEMI) polys_semi(a, a2, p1, q1, sp, cp);
+    else {
+        sp = fmaf(a * a2, fmaf(a2, p1, -1.6666654611e-1f), a);
+        cp = fmaf(a2 * a2, fmaf(a2, q1, 4.166664568298827e-2f), fmaf(a2, -0.5f, 1.0f));
+    }
+    const float ss = (q & 1) ? cp : sp, cc = (q & 1) ? sp : cp;
+    s = (q & 2) ? -ss : ss;
+    c = ((q + 1) & 2) ? -cc : cc;
+}
+
 // exp(-j 2 pi k / 16), k = 0..7
 __device__ __forceinline__ float2 w16(int k)
 {
@@ -132,7 +166,7 @@ __device__ __forceinline__ void fft_reg(float2 (&v)[F])
                 const int tk = (i & (h - 1)) * (8 / h);       // W_{2h}^{i mod h} as a power of W_16
                 if (tk == 0) v[i + h] = d;
                 else if (tk == 4) v[i + h] = cmulnj(d);
-                else v[i + h] = cmul_fx(d, w16(tk));
+                else v[i + h] = cmul_fx_pk(d, w16(tk));
             }
         }
     }
@@ -163,6 +197,9 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
     constexpr int N = K / 2;
     constexpr int H = P - 1;                // history blocks
     constexpr int TL = Geo<K, C, T, P>::TL, TG = P - TL;     // taps per column in LDS / fetched per round
+    // Complex products as two packed instructions each (devmath.h: cmul_fx_pk, rot_fx_pk -- the scalar forms' bits): everywhere but in the
+    // mixer and oscillator of the two builds that spill (28 taps, K >= 512), which spill 5-13 registers more with them and 3-7 fewer without
+    constexpr bool PKM = !(P > CH_P_REF && K >= 512);
     constexpr int S = Plan<K>::S, F = Plan<K>::F, ROWP = Plan<K>::ROWP, R = Plan<K>::R, LR = Plan<K>::LR;
     static_assert(TPS * C == K && NS * TPS == T && NS >= 1, "bad channelizer geometry");
     static_assert(TL >= 1 && TG >= 0 && TG <= 8, "tap split");
@@ -177,6 +214,13 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
     // fetched into registers for the FIR of each round only: across the FFT stages the registers
     // hold the sliding window plus the next round's blocks that are already in flight.
     float *ltap = reinterpret_cast<float *>(tile + NS * CH_R * ROWP);
+    // a.hist_out: the stream's last H blocks, as they came, for the next launch -- a grid-stride copy whose first element travels with
+    // the taps' round trip (requested in front of them, stored behind their barrier; clamped, not branched: see load_raw)
+    constexpr uint32_t NH = (uint32_t)H * K;
+    const bool carry_hist = a.hist_out != nullptr;
+    const Raw *const hsrc = static_cast<const Raw *>(a.x) + (carry_hist ? (size_t)(a.nblocks - H) * K : 0);
+    uint32_t hidx = blockIdx.x * T + tid;
+    Raw hval = hsrc[carry_hist ? (hidx < NH ? hidx : NH - 1) : 0];
     {
         constexpr int NT = TL * K;                  // all requests first, then the LDS writes: one round trip
         constexpr int PER = (NT + T - 1) / T;
@@ -187,6 +231,14 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
         for (int i = 0; i < PER; i++) { const int idx = tid + i * T; if (idx < NT) ltap[idx] = tv[i]; }
     }
     __syncthreads();
+    if (carry_hist) {
+        Raw *const hdst = static_cast<Raw *>(a.hist_out);
+        while (hidx < NH) {
+            hdst[hidx] = hval;
+            hidx += gridDim.x * T;
+            if (hidx < NH) hval = hsrc[hidx];
+        }
+    }
     // radix-R stage twiddles W_L^{r*pos}, r = 1..R-1: pos = q % (L/R) does not depend on the
     // loop trip because L/R divides the workgroup size
     float2 tw[S > 0 ? S : 1][R - 1];
@@ -196,14 +248,17 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
         const int pos = tid % q4;
 #pragma unroll
         for (int r = 1; r < R; r++) {
-            float sn, cs; sincos_u32((uint32_t)(r * pos) * (uint32_t)(4294967296.0 / L), sn, cs);
+            float sn, cs;
+            if (R == 8 && r == 1) sincos_u32_fx<true>((uint32_t)(r * pos) * (uint32_t)(4294967296.0 / L), sn, cs);
+            else sincos_u32_fx((uint32_t)(r * pos) * (uint32_t)(4294967296.0 / L), sn, cs);
             tw[st][r - 1] = make_float2(cs, -sn);
         }
     }
 
     const uint32_t dth = a.dtheta;
-    float sd1, cd1; sincos_u32(dth, sd1, cd1);                  // e^{j dtheta}: column n+1 from column n
-    float sk8, ck8; sincos_u32((uint32_t)K * dth, sk8, ck8);    // e^{j K dtheta}: block b+1 from block b
+    // (oscillator values travel as (sin, cos) in a register pair: every turn below is two packed instructions, devmath.h: rot_fx_pk)
+    float2 od1; sincos_u32_fx(dth, od1.x, od1.y);                  // e^{j dtheta}: column n+1 from column n
+    float2 ok8; sincos_u32_fx((uint32_t)K * dth, ok8.x, ok8.y);    // e^{j K dtheta}: block b+1 from block b
     const uint32_t t0 = a.first_sample_lo;
 
     // raw samples of block b (relative to a.x), columns n0..n0+C-1; zeros outside the stream
@@ -247,28 +302,27 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
     // the launch-constant per-block step K*dtheta, the neighbouring column by the per-sample step.  Every value is
     // a fixed function of (group start, position in the group, column), so a stream cut into several calls on
     // tile boundaries reproduces the single-call result bit for bit (explicit fma shapes, no reassociation).
-    auto osc_start = [&](long long g, float &sn, float &cs) {
-        sincos_u32_hw((t0 + (uint32_t)(g * K + n0)) * dth, sn, cs);
+    auto osc_start = [&](long long g, float2 &o) {
+        sincos_u32_hw((t0 + (uint32_t)(g * K + n0)) * dth, o.x, o.y);
+        if constexpr (PKM) o = trans_settle(o);         // (its readers are packed instructions in assembly text)
     };
-    auto osc_next_block = [&](float &sn, float &cs) {
-        const float s2 = fmaf(sn, ck8, cs * sk8), c2 = fmaf(cs, ck8, -(sn * sk8)); sn = s2; cs = c2;
-    };
+    auto osc_next_block = [&](float2 &o) { o = PKM ? rot_fx_pk(o, ok8) : rot_fx(o, ok8); };
     // src -> dst; cf32 mixes in place (src and dst are the same window entry), sc16 unpacks the word here, where it is first used
-    auto mix_with = [&](long long b, float sn, float cs, const Raw (&src)[C], float2 (&dst)[C]) {
+    auto mix_with = [&](long long b, float2 o, const Raw (&src)[C], float2 (&dst)[C]) {
         // blocks outside the stream become zeros: a zeroed oscillator (by value; the caller's copy keeps turning)
         // zeroes both columns, two selects per block instead of four.  (Clamped loads return finite samples.)
         if constexpr (EDGE) {
             const bool valid = (b >= 0 && b < (long long)a.nblocks) || (b < 0 && a.halo != nullptr);
-            sn = valid ? sn : 0.f; cs = valid ? cs : 0.f;
+            o.x = valid ? o.x : 0.f; o.y = valid ? o.y : 0.f;
         }
 #pragma unroll
         for (int c = 0; c < C; c++) {
-            if (c > 0) { const float s2 = fmaf(sn, cd1, cs * sd1), c2 = fmaf(cs, cd1, -(sn * sd1)); sn = s2; cs = c2; }
+            if (c > 0) o = PKM ? rot_fx_pk(o, od1) : rot_fx(o, od1);
             float x, y;
             // sc16_unpack's expression spelled out: through the call this kernel's registers are allocated differently
             if constexpr (SC16) { x = (float)(int16_t)(src[c] & 0xffffu) * 0x1p-15f; y = (float)((int32_t)src[c] >> 16) * 0x1p-15f; }
             else { x = src[c].x; y = src[c].y; }
-            dst[c] = make_float2(fmaf(x, cs, y * sn), fmaf(y, cs, -(x * sn)));
+            dst[c] = PKM ? rot_fx_pk(make_float2(x, y), o) : rot_fx(make_float2(x, y), o);
         }
     };
 
@@ -290,12 +344,12 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
         int i = 0;
 #pragma unroll
         for (int g = 0; g < HG; g++) {
-            float sn, cs;
-            osc_start(bs - (long long)CH_R * (HG - g), sn, cs);
+            float2 o;
+            osc_start(bs - (long long)CH_R * (HG - g), o);
 #pragma unroll
             for (int k = 0; k < CH_R; k++) {
-                if (g > 0 || k >= HSKIP) { mix_with(bs - H + i, sn, cs, raw(i), s[i]); i++; }
-                osc_next_block(sn, cs);
+                if (g > 0 || k >= HSKIP) { mix_with(bs - H + i, o, raw(i), s[i]); i++; }
+                osc_next_block(o);
             }
         }
     }
@@ -339,6 +393,7 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
     }
     const uint32_t tile_step = a.cg * (MCRX_TILE_S / 2);     // 16-byte units between consecutive tiles of a channel group
     float4 *out4 = reinterpret_cast<float4 *>(a.out);
+    const uint32_t wg_tile_end = (uint32_t)((((long long)blockIdx.x * NS + NS - 1) * (long long)a.slab_blocks) / MCRX_TILE_S) + 1u;      // one past the first tile of my last slab
     int wcol[C];                                        // where my columns' FIR outputs go in a tile row (padded index)
 #pragma unroll
     for (int c = 0; c < C; c++) wcol[c] = pad<K>(SHIFT ? (int)((n0 + c + a.col_shift) & (K - 1)) : n0 + c);
@@ -358,10 +413,10 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
 #pragma unroll
                 for (int c = 0; c < C; c++) tap[j][c] = ltap[j * K + n0 + c];
             {
-                float sn, cs;
-                osc_start(b0, sn, cs);
+                float2 o;
+                osc_start(b0, o);
 #pragma unroll
-                for (int r = 0; r < CH_R; r++) { mix_with(b0 + r, sn, cs, raw(H + r), s[H + r]); osc_next_block(sn, cs); }
+                for (int r = 0; r < CH_R; r++) { mix_with(b0 + r, o, raw(H + r), s[H + r]); osc_next_block(o); }
             }
 #pragma unroll
             for (int r = 0; r < CH_R; r++) {
@@ -390,10 +445,10 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
             // many taps: the eight outputs of the round accumulate side by side, one tap (from LDS, or of the fetched ones) at a time,
             // oldest first -- the taps never sit in registers all at once
             {
-                float sn, cs;
-                osc_start(b0, sn, cs);
+                float2 o;
+                osc_start(b0, o);
 #pragma unroll
-                for (int r = 0; r < CH_R; r++) { mix_with(b0 + r, sn, cs, raw(H + r), s[H + r]); osc_next_block(sn, cs); }
+                for (int r = 0; r < CH_R; r++) { mix_with(b0 + r, o, raw(H + r), s[H + r]); osc_next_block(o); }
             }
             // (CH_RH outputs per pass: the accumulators of all eight at once cost 16 more registers than the kernel has)
 #pragma unroll
@@ -455,15 +510,15 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
                         fft_reg<8>(v);                  // v[m] = X[bitrev(m)]
                         p[0] = v[0];
 #pragma unroll
-                        for (int r = 1; r < 8; r++) p[r * D] = cmul_fx(v[bitrev_c(r, 3)], tw[st][r - 1]);
+                        for (int r = 1; r < 8; r++) p[r * D] = cmul_fx_pk(v[bitrev_c(r, 3)], tw[st][r - 1]);
                         continue;
                     }
                     const float2 x0 = p[0], x1 = p[D], x2 = p[2 * D], x3 = p[3 * D];
                     const float2 a0 = cadd(x0, x2), a1 = csub(x0, x2), a2 = cadd(x1, x3), a3 = cmulnj(csub(x1, x3));
                     p[0] = cadd(a0, a2);
-                    p[D] = cmul_fx(cadd(a1, a3), tw[st][0]);
-                    p[2 * D] = cmul_fx(csub(a0, a2), tw[st][1]);
-                    p[3 * D] = cmul_fx(csub(a1, a3), tw[st][2]);
+                    p[D] = cmul_fx_pk(cadd(a1, a3), tw[st][0]);
+                    p[2 * D] = cmul_fx_pk(csub(a0, a2), tw[st][1]);
+                    p[3 * D] = cmul_fx_pk(csub(a1, a3), tw[st][2]);
                 }
                 lds_barrier();
             }
@@ -500,6 +555,22 @@ __device__ __forceinline__ void channelizer_rounds(const ChanArgs &a, float2 *ti
 #endif
             }
         }
+        // a.out2: the granules of the stream's last tiles once more, where the next launch's synchronizers look for their history.  Decided
+        // per workgroup and round on scalars -- does my last slab reach those tiles yet? -- so that every other round pays one compare
+        if (__builtin_expect(a.out2 != nullptr && (wg_tile_end + ((uint32_t)rd >> 1)) * tile_step > a.out2_first, 0)) {
+            float4 *out24 = reinterpret_cast<float4 *>(a.out2);
+#pragma unroll
+            for (int k = 0; k < OTRIPS; k++) {
+                const uint32_t dst = sdst[k] + ((uint32_t)rd >> 1) * tile_step + ((uint32_t)rd & 1u) * (CH_R / 2);
+                bool ok = dst >= a.out2_first;
+                if constexpr (EDGE) ok = ok && rd * CH_R < srem[k];
+                if (ok) {
+                    const float2 *src = tile + ssrc[k];
+                    const float2 v0 = src[0], v1 = src[ROWP];
+                    out24[(size_t)(dst - a.out2_first)] = make_float4(v0.x, v0.y, v1.x, v1.y);
+                }
+            }
+        }
         lds_barrier();
     }
 }
@@ -523,6 +594,7 @@ static hipError_t launch_one(const ChanArgs &a, hipStream_t st)
     long long nslabs = ((long long)a.nblocks + a.slab_blocks - 1) / a.slab_blocks;
     unsigned grid = (unsigned)((nslabs + NS - 1) / NS);
     if (grid == 0) return hipSuccess;
+    if (a.hist_out != nullptr && a.nblocks < (uint32_t)(P - 1)) return hipErrorInvalidValue;
     // granule stores are addressed by 32-bit offsets in 16-byte units: 64 GB of output per launch
     if ((unsigned long long)(K / 2) * ((unsigned long long)a.ntiles + (unsigned long long)NS * a.slab_blocks / MCRX_TILE_S + 1ull) * (MCRX_TILE_S / 2) >= (1ull << 32))
         return hipErrorInvalidValue;
@@ -613,6 +685,7 @@ __global__ __launch_bounds__(CG_T) void channelizer_generic_kernel(ChanArgs a, u
 }
 
 static bool pow2_fast(unsigned K) { return K >= 2 && K <= 1024 && (K & (K - 1)) == 0; }
+int channelizer_carries(unsigned K) { return pow2_fast(K) ? 1 : 0; }
 int channelizer_supported(unsigned K)
 { return (pow2_fast(K) || (K >= 2 && K % 2 == 0 && K <= 2048)) ? 1 : 0; }
 
@@ -652,6 +725,7 @@ static hipError_t launch_format(unsigned K, unsigned P, const ChanArgs &a, hipSt
     }
     if (P != CH_P_REF) return hipErrorInvalidValue;
     if (!pow2_fast(K)) {
+        if (a.out2 != nullptr || a.hist_out != nullptr) return hipErrorInvalidValue;       // (channelizer_carries)
         if (a.nblocks == 0) return hipSuccess;
         const size_t lds = (size_t)(CH_R + 1) * K * sizeof(float2);
         static PerDeviceOnce gen_done;

@@ -38,6 +38,39 @@ __device__ __forceinline__ cfd csub_nj(cfd a, cfd b)
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(av), "v"(bv));
     return make_float2(r.x, r.y);
 }
+// cmul_fx in two packed instructions, the same bits: a packed multiply forms (-(a.y b.y), a.y b.x) -- the sign sits on an operand
+// (neg_lo), and (-p) q == -(p q) exactly -- and a packed fma adds a.x (b.x, b.y) to it: the scalar form's two multiplies and two
+// fused multiply-adds, each with the same operands and the same single rounding.
+__device__ __forceinline__ cfd cmul_fx_pk(cfd a, cfd b)
+{
+    devmath_v2f t, r; const devmath_v2f av = { a.x, a.y }, bv = { b.x, b.y };
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0] neg_lo:[1,0]" : "=v"(t) : "v"(av), "v"(bv));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(r) : "v"(av), "v"(bv), "v"(t));
+    return make_float2(r.x, r.y);
+}
+// v turned back by the oscillator value o = (sin, cos), roundings pinned: mix_down_hw's shape, and, with v itself an oscillator
+// value (sin, cos), one oscillator step by the angle of o
+__device__ __forceinline__ cfd rot_fx(cfd v, cfd o)
+{ return make_float2(fmaf(v.x, o.y, v.y * o.x), fmaf(v.y, o.y, -(v.x * o.x))); }
+// ... in two packed instructions with the roundings of the four scalar ones (the sign of the second product is neg_hi on its operand)
+__device__ __forceinline__ cfd rot_fx_pk(cfd v, cfd o)
+{
+    devmath_v2f t, r; const devmath_v2f vv = { v.x, v.y }, ov = { o.x, o.y };
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[0,0] neg_hi:[1,0]" : "=v"(t) : "v"(vv), "v"(ov));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(vv), "v"(ov), "v"(t));
+    return make_float2(r.x, r.y);
+}
+
+// A value fresh from the transcendental unit (v_sin_f32, v_cos_f32, ...) on its way into inline assembly.  Another VALU instruction may
+// read such a result one wait state later at the earliest; the compiler keeps that distance between its own instructions but does not
+// look into assembly text, and a packed multiply placed right behind the v_cos_f32 read the register's old value (seen on the MI355X:
+// the 28-tap K = 128 build, whose schedule happened to put them back to back).  This is that wait state, tied to the value.
+__device__ __forceinline__ cfd trans_settle(cfd v)
+{
+    devmath_v2f vv = { v.x, v.y };
+    asm("s_nop 0" : "+v"(vv));
+    return make_float2(vv.x, vv.y);
+}
 
 // sin/cos of a 32-bit phase (theta * 2 pi / 2^32): octant-centred reduction is exact in
 // integers, then degree-7/8 minimax polynomials on [-pi/4, pi/4] (abs error ~1e-7).

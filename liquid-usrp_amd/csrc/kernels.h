@@ -26,8 +26,13 @@ struct ChanArgs {
     uint32_t ntiles;            // tiles per group in `out`
     uint32_t cg;                // channels per group
     uint32_t col_shift;         // P = 28 (oversampled front end): column n's FIR output is transform input (n + col_shift) mod K
+    // What the next launch of a stream needs of this one, written by this launch itself (channelizer_carries(K) only; NULL: not wanted):
+    float2 *out2;               // a second copy of the granules from 16-byte unit `out2_first` of `out` on: the last tiles of a one-group launch,
+    uint32_t out2_first;        //   which the next launch's synchronizers read as history in front of their own tiles
+    void *hist_out;             // the last P - 1 blocks of x, in x's format: the next launch's halo (needs nblocks >= P - 1)
 };
 int channelizer_supported(unsigned K);
+int channelizer_carries(unsigned K);     // 1: the kernel of this K serves ChanArgs::out2 / hist_out (the power-of-two kernel; not the generic one)
 // blocks per workgroup slab such that the grid is a whole number of waves over `ncu` compute units
 uint32_t channelizer_auto_slab(unsigned K, size_t nblocks, unsigned ncu);
 // P = taps per column: 14 = the reference's bank (any even K <= 2048), 28 = the oversampled front end's composite bank (power-of-two K <= 1024);

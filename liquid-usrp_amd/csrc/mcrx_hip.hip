@@ -190,6 +190,7 @@ struct mcrx_hip_s {
 
     hipEvent_t ev_ready[MCRX_SLOTS] = {}, ev_scout[MCRX_SLOTS] = {}, ev_done[MCRX_SLOTS] = {}, ev_in = nullptr, ev_consumed = nullptr, ev_tmp[4] = {};
     int last_slot = -1; size_t last_ntiles = 0;     // where the synchronizer history (tail of the previous launch) sits
+    bool carried = false; uint64_t carried_seq = 0; // ... and whether that launch's channelizer already wrote it into the front of launch carried_seq's slot (ChanArgs::out2)
     uint32_t spec_stride = MCRX_SPEC_MAX;           // slots per channel in d_spec (grows when a push holds more frames per channel: launch_sync)
     SpecSlot *d_spec = nullptr; float2 *d_spec_R = nullptr; int64_t *d_anchor = nullptr, *d_seekst = nullptr;
     bool spec = false;
@@ -543,7 +544,7 @@ static int restart_async(mcrx_hip_t q, hipStream_t st, bool from_zero)
     if (from_zero) { q->total_samples = 0; q->chan_samples = 0; }
     q->stage_fill = 0; q->stage_first = q->total_samples;
     q->hist_cur = 0;
-    q->last_slot = -1; q->last_ntiles = 0;
+    q->last_slot = -1; q->last_ntiles = 0; q->carried = false;
     q->pf_in_valid = 0; q->pf_steps = 0; q->pf_have_last = false;
     monitor_restart(q);
     RC(join_into(q, st));
@@ -859,8 +860,10 @@ extern "C" int mcrx_hip_get_taps(mcrx_hip_t q, float *h, size_t n)
 }
 
 // ---------------------------------------------------------------- stage level
+// out2 / out2_first_tile, hist_out: ChanArgs' carries for the next launch of a stream (kernels.h; NULL: none)
 static int launch_channelizer(mcrx_hip_t q, const void *x, size_t nblocks, uint64_t first_sample,
-                              const void *halo, float2 *out, unsigned groups, size_t ntiles_stride, hipStream_t st)
+                              const void *halo, float2 *out, unsigned groups, size_t ntiles_stride, hipStream_t st,
+                              float2 *out2 = nullptr, size_t out2_first_tile = 0, void *hist_out = nullptr)
 {
     if (nblocks == 0) return MCRX_OK;
     if (nblocks % MCRX_TILE) return fail(MCRX_EINVAL, "nblocks must be a multiple of MCRX_TILE (16)");
@@ -871,6 +874,8 @@ static int launch_channelizer(mcrx_hip_t q, const void *x, size_t nblocks, uint6
     a.slab_blocks = q->slab_blocks ? q->slab_blocks : channelizer_auto_slab(q->K, nblocks, q->ncu);
     a.first_sample_lo = (uint32_t)first_sample; a.dtheta = q->dtheta;
     a.ntiles = (uint32_t)ntiles_stride; a.cg = q->N / groups; a.col_shift = q->col_shift;
+    if (out2 && groups != 1) return fail(MCRX_EINVAL, "a second copy of the last tiles needs a one-group launch");
+    a.out2 = out2; a.out2_first = (uint32_t)(out2_first_tile * a.cg * (MCRX_TILE / 2)); a.hist_out = hist_out;      // (16-byte units; channelizer_launch checks that they fit 32 bits)
     RC(q->ev_begin(0, st));
     HIPCHK(channelizer_launch(q->K, q->chan_P, q->in_fmt, a, st));
     RC(q->ev_end(0, st));
@@ -1163,6 +1168,7 @@ static int ensure_chan(mcrx_hip_t q, size_t tiles)
                          (size_t)q->hist_tiles * tile_elems * sizeof(float2), hipMemcpyDeviceToDevice));
     for (int i = 0; i < MCRX_SLOTS; i++) { if (q->d_chan[i]) (void)hipFree(q->d_chan[i]); q->d_chan[i] = nb[i]; }
     q->chan_cap_tiles = tiles;
+    q->carried = false;                          // (the copy a channelizer made into the old buffers is gone with them)
     return MCRX_OK;
 }
 
@@ -1235,7 +1241,17 @@ static int run_blocks(mcrx_hip_t q, const void *x, size_t nblocks, uint64_t firs
         if (st != sc) { HIPCHK(hipEventRecord(q->ev_in, st)); HIPCHK(hipStreamWaitEvent(sc, q->ev_in, 0)); }
         if (q->seq >= q->nslots) HIPCHK(hipStreamWaitEvent(sc, q->ev_done[slot], 0));
     }
-    if (q->last_slot >= 0)
+    // What the next push needs of this one -- the synchronizers' history tiles in front of its slot, the bank's last blocks -- the
+    // channelizer writes itself where it can (kernels.h: ChanArgs::out2, hist_out) instead of a copy in front of the next launch and a
+    // kernel behind this one: two packets fewer per push that would each wait for a place on a full chip.  The tiles: pipelined handles
+    // with slots enough that the next slot's last reader (launch seq + 1 - nslots) is long done -- its end is waited for here, a push
+    // earlier than the acquisition (launch_acquisition) would -- and pushes that hold all hist_tiles themselves.
+    const bool direct = !q->bypass && !q->oversampled && channelizer_carries(q->K);
+    const unsigned next = (unsigned)((q->seq + 1) % q->nslots);
+    const bool carry_tiles = direct && q->pipelined && q->nslots >= 4 && ntiles >= q->hist_tiles;
+    const bool carry_hist = direct && nblocks >= q->hist_blocks;
+    if (carry_tiles && q->seq + 1 >= q->nslots) HIPCHK(hipStreamWaitEvent(sc, q->ev_done[next], 0));
+    if (q->last_slot >= 0 && !(q->carried && q->carried_seq == q->seq))
         HIPCHK(hipMemcpyAsync(buf, q->d_chan[q->last_slot] + q->last_ntiles * tile_elems,
                               (size_t)q->hist_tiles * tile_elems * sizeof(float2), hipMemcpyDeviceToDevice, sc));
     if (q->bypass)      // the input already is the channel's sample stream (one channel: its tiles are contiguous)
@@ -1243,9 +1259,12 @@ static int run_blocks(mcrx_hip_t q, const void *x, size_t nblocks, uint64_t firs
     else if (q->oversampled)
         RC(run_oversampled(q, static_cast<const float2 *>(x), nblocks, first_abs, buf + q->hist_tiles * tile_elems, sc));      // (cf32 handles only: create)
     else
-        RC(launch_channelizer(q, x, nblocks, first_abs, q->d_hist[q->hist_cur], buf + q->hist_tiles * tile_elems, 1, ntiles, sc));
+        RC(launch_channelizer(q, x, nblocks, first_abs, q->d_hist[q->hist_cur], buf + q->hist_tiles * tile_elems, 1, ntiles, sc,
+                              carry_tiles ? q->d_chan[next] : nullptr, ntiles - (carry_tiles ? q->hist_tiles : 0), carry_hist ? q->d_hist[1 - q->hist_cur] : nullptr));
+    q->carried = carry_tiles; q->carried_seq = q->seq + 1;
     // FIR history: the last 13 (27) blocks of (history, x)
-    if (!q->bypass && !q->oversampled) {
+    if (carry_hist) q->hist_cur ^= 1;
+    else if (!q->bypass && !q->oversampled) {      // (a push shorter than the history, the generic kernel: blocks of the old history stay)
         const uint64_t nh = (uint64_t)q->hist_blocks * q->K;
         const dim3 hg((unsigned)((nh + 255) / 256));
         if (q->in_fmt == IQ_SC16)
