@@ -506,7 +506,8 @@ const char *mctx_hip_last_error(void);
  * w[n] = sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2) -- unit variance per component.  The integers of an sc16 handle are Q of a cf32
  * handle's output exactly, and a stream cut anywhere gives the one-shot output bit for bit.
  * The handle keeps the 64-bit position of the next input sample and the last max d_i input samples (device memory); successive calls
- * must be ordered on the device (one stream, or events of the caller's).  In-place use is refused: the taps read behind the write front. */
+ * must be ordered on the device (one stream, or events of the caller's).  In-place use is refused: the taps read behind the write front.
+ * The rays are constants unless fading is switched on (mcrx_hip_chanfade_set, at the end of this block): then a_i becomes g_i(n) a_i. */
 #define MCRX_CHANEMU_MAX_TAPS  8
 #define MCRX_CHANEMU_MAX_DELAY 65535
 typedef struct mcrx_hip_chanemu_s *mcrx_hip_chanemu_t;
@@ -538,6 +539,49 @@ int      mcrx_hip_chanemu_clipped(mcrx_hip_chanemu_t q, uint64_t *samples, int r
 /* host: the two Philox words sample `position` draws under `seed` (the same code the kernel compiles; needs no GPU) */
 int      mcrx_hip_chanemu_selftest_words(uint64_t seed, uint64_t position, uint32_t out[2]);
 const char *mcrx_hip_chanemu_last_error(void);
+
+/* ---- channel emulator: fading rays (Rayleigh / Rician with Doppler) ----
+ * With fading on, ray i of the emulator is multiplied by a complex gain g_i(n) -- still a function of the ABSOLUTE output index n alone,
+ * so a stream cut anywhere stays bit-identical to one call and the sc16 integers stay Q of the cf32 output.  With fading off (the state
+ * of a new handle, and after a NULL) the emulator is the one described above, word for word.
+ *   B = 2^log2_block wideband samples is the update interval of the gains; b = n >> log2_block the grid row, n_b = (b << log2_block)
+ *   mod 2^64; e(p) of a 64-bit phase p is (cos, sin)(2 pi (p >> 32) / 2^32).  Per ray i, with S = num_sinusoids scattered sinusoids:
+ *     G_i[b] = c_los_i e((psi_i << 32) + Lambda_i n_b) + c_sc_i sum_{k<S} e((Phi_ik << 32) + N_ik n_b)        phases mod 2^64
+ *     g_i(n) = G_i[b] + f (G_i[b+1] - G_i[b]),   f = (n & (B - 1)) 2^-log2_block                               linear, by definition
+ *     s[n]   = sum_{i<T} (g_i(n) a_i) x[n - d_i]                                                               table order
+ *   The gain is indexed by the output time n, not by n - d_i.  Rotation, gain, noise and quantiser behind s[n] are unchanged.
+ * The integers are made on the host from `seed`: the Philox4x32-10 words of counter (k, i, 1, 0) and key (lo32(seed), hi32(seed)) give the
+ * stratified arrival angle alpha_ik = 2 pi (k + w0 2^-32) / S and the phase Phi_ik = w1; N_ik = rint(doppler_i cos(alpha_ik) 2^64),
+ * Lambda_i = rint(los_doppler_i 2^64), psi_i = los_phase_i; c_los_i = sqrt(K_i / (K_i + 1)), c_sc_i = sqrt(1 / ((K_i + 1) S)) with
+ * K_i = rice_k[i] the linear Rice factor, so that E|g_i|^2 = 1: K = 0 is Rayleigh (Jakes' spectrum of width doppler_i), a large K a
+ * specular ray with a Doppler shift.  Linear interpolation between grid rows is part of the definition: against the sample-exact sum of
+ * sinusoids it deviates by about (pi f_d B)^2 / 2 (1.2e-3 at f_d B = 1/64), so choose log2_block for the Doppler at hand.
+ * The handle keeps a table of gains in device memory (64 bytes a row), grown to what a call needs up to table_rows rows (0: 2^18 rows,
+ * 16 MB); a call that needs more is processed in consecutive spans on the caller's stream, which changes no bit of the output.
+ * (These three functions do not carry the emulator's prefix: its set of entry points is closed.  Errors are read with
+ * the emulator's last_error function.) */
+#define MCRX_CHANEMU_MAX_SINUSOIDS 16
+typedef struct {
+    uint32_t struct_size, log2_block, num_sinusoids, table_rows;   /* sizeof(mcrx_hip_chanemu_fading); 1 .. 24; 1 .. 16; 0 = default, else >= 2 */
+    double   doppler[MCRX_CHANEMU_MAX_TAPS];       /* f_d >= 0, cycles per wideband sample */
+    double   los_doppler[MCRX_CHANEMU_MAX_TAPS];   /* signed, cycles per wideband sample */
+    float    rice_k[MCRX_CHANEMU_MAX_TAPS];        /* linear, >= 0, finite */
+    uint32_t los_phase[MCRX_CHANEMU_MAX_TAPS];     /* 2^32 * cycles */
+    uint64_t seed;
+} mcrx_hip_chanemu_fading;
+/* f == NULL: fading off.  Holds no stream state: it may be called between any two execute calls, needs no synchronisation with calls in
+ * flight, and entries beyond the handle's num_taps are ignored.  MCRX_EINVAL, before any device work: a null handle, a wrong struct_size,
+ * log2_block outside 1 .. 24, num_sinusoids outside 1 .. 16, table_rows == 1, a Doppler that is not finite, a negative doppler,
+ * doppler * B > 1/8 or |los_doppler| * B > 1/8 (the grid must sample the gain), a rice_k that is negative or not finite. */
+int      mcrx_hip_chanfade_set(mcrx_hip_chanemu_t q, const mcrx_hip_chanemu_fading *f);
+int      mcrx_hip_chanfade_on(mcrx_hip_chanemu_t q);                                 /* 1 with fading on; 0 for a null handle */
+/* host, no GPU: the integers and coefficients ray `ray` (< MCRX_CHANEMU_MAX_TAPS) gets -- steps[0] / phases[0] the line-of-sight term,
+ * then the num_sinusoids scattered ones (1 + num_sinusoids entries each); coef = { c_los, c_sc }.  Checks `f` as set does, for that ray. */
+int      mcrx_hip_chanfade_selftest(const mcrx_hip_chanemu_fading *f, unsigned ray, int64_t *steps, uint32_t *phases, float coef[2]);
+
+/* The gain kernel on its own, for tests and measurements: G_i[first_row + r], r < rows, of the handle's rays as float2 [rows][MCRX_CHANEMU_MAX_TAPS]
+ * (entries of rays >= num_taps are not written) into the caller's device buffer, asynchronously on `stream`.  MCRX_EINVAL with fading off. */
+int      mcrx_hip_chanfade_gains(mcrx_hip_chanemu_t q, uint64_t first_row, uint32_t rows, void *d_table, void *stream);
 
 #ifdef __cplusplus
 }

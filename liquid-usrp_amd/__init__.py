@@ -178,6 +178,10 @@ _EXPORTS = {
     "mcrx_hip_chanemu_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
     "mcrx_hip_chanemu_selftest_words": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
     "mcrx_hip_chanemu_last_error": (C.c_char_p, []),
+    "mcrx_hip_chanfade_set": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mcrx_hip_chanfade_on": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_chanfade_gains": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_chanfade_selftest": (C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
 }
 
 _lib = None
@@ -704,6 +708,54 @@ class ChanemuConfig(C.Structure):
                 ("seed", C.c_uint64), ("output_format", C.c_uint32)]
 
 
+CHANEMU_MAX_SINUSOIDS = 16                          # MCRX_CHANEMU_MAX_SINUSOIDS
+
+
+class ChanemuFading(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("log2_block", C.c_uint32), ("num_sinusoids", C.c_uint32), ("table_rows", C.c_uint32),
+                ("doppler", C.c_double * CHANEMU_MAX_TAPS), ("los_doppler", C.c_double * CHANEMU_MAX_TAPS),
+                ("rice_k", C.c_float * CHANEMU_MAX_TAPS), ("los_phase", C.c_uint32 * CHANEMU_MAX_TAPS), ("seed", C.c_uint64)]
+
+
+_FADING_KEYS = ("doppler", "rice_k", "los_doppler", "los_phase", "sinusoids", "log2_block", "seed", "table_rows")
+
+
+def chanemu_fading(num_taps, doppler=0.0, rice_k=0.0, los_doppler=0.0, los_phase=0, sinusoids=16, log2_block=10, seed=0, table_rows=0):
+    """The mcrx_hip_chanemu_fading structure of a fading description for `num_taps` rays; per-ray entries are scalars (every ray gets
+    them) or sequences of num_taps values.  Raises ValueError for what the library would refuse."""
+    def per_ray(v, name, conv):
+        vals = [conv(x) for x in v] if hasattr(v, "__len__") else [conv(v)] * num_taps
+        if len(vals) != num_taps:
+            raise ValueError("fading: %s has %d entries for %d rays" % (name, len(vals), num_taps))
+        return vals
+    for v, name, lo, hi in ((log2_block, "log2_block", 1, 24), (sinusoids, "sinusoids", 1, CHANEMU_MAX_SINUSOIDS)):
+        if int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError("fading: %s must be %d .. %d" % (name, lo, hi))
+    if int(table_rows) != table_rows or int(table_rows) == 1 or not 0 <= int(table_rows) < (1 << 32):
+        raise ValueError("fading: table_rows must be 0 (default) or 2 .. 2^32 - 1")
+    f = ChanemuFading()
+    f.struct_size, f.log2_block, f.num_sinusoids, f.table_rows = C.sizeof(ChanemuFading), int(log2_block), int(sinusoids), int(table_rows)
+    B = float(1 << int(log2_block))
+    fd, fl = per_ray(doppler, "doppler", float), per_ray(los_doppler, "los_doppler", float)
+    rk, ph = per_ray(rice_k, "rice_k", float), per_ray(los_phase, "los_phase", int)
+    for i in range(num_taps):
+        if not (math.isfinite(fd[i]) and math.isfinite(fl[i])):
+            raise ValueError("fading: a Doppler is not finite")
+        if fd[i] < 0.0 or fd[i] * B > 0.125 or abs(fl[i]) * B > 0.125:
+            raise ValueError("fading: 0 <= doppler and doppler * 2^log2_block <= 1/8 (|los_doppler| likewise): the grid must sample the gain")
+        if not (math.isfinite(rk[i]) and rk[i] >= 0.0 and math.isfinite(C.c_float(rk[i]).value)):
+            raise ValueError("fading: rice_k must be finite and not negative")
+        f.doppler[i], f.los_doppler[i], f.rice_k[i], f.los_phase[i] = fd[i], fl[i], rk[i], ph[i] % (1 << 32)
+    f.seed = int(seed) % (1 << 64)
+    return f
+
+
+def chanemu_doppler(cycles_per_ofdm_symbol, M, cp, num_channels):
+    """The chanemu Doppler (cycles per wideband sample) of a gain that turns `cycles_per_ofdm_symbol` cycles in one OFDM symbol of a
+    user channel: a symbol is M + cp channel-rate samples, each 2 * num_channels wideband samples."""
+    return float(cycles_per_ofdm_symbol) / ((M + cp) * 2 * num_channels)
+
+
 def chanemu_cfo_step(spacings, M, num_channels):
     """The chanemu cfo_step (2^32 * cycles per wideband sample, mod 2^32) of a carrier offset of `spacings` subcarrier spacings as
     every channel's synchronizer sees it: a channel-rate sample is 2 * num_channels wideband samples, a spacing 1 / M cycles of those."""
@@ -719,9 +771,14 @@ class chanemu(object):
     noise_std is per component.  Everything is a function of the absolute sample index, so a stream may be cut into execute calls
     anywhere.  execute(x) takes a torch complex64 CUDA tensor and returns complex64, or with output_format="sc16" a contiguous int16
     tensor of shape (n, 2) -- the transmitter's quantiser applied to what a cf32 emulator returns; clipped() counts the samples that
-    left the int16 range."""
+    left the int16 range.
 
-    def __init__(self, taps=((0, 1.0),), cfo_step=0, phase0=0, gain=1.0, noise_std=0.0, seed=0, output_format="cf32"):
+    fading=dict(doppler=..., rice_k=..., los_doppler=..., los_phase=..., sinusoids=16, log2_block=10, seed=0, table_rows=0) turns every
+    ray into a Rayleigh (rice_k = 0) or Rician fading one: Doppler in cycles per wideband sample (chanemu_doppler), per ray or one
+    value for all; the gains are updated every 2^log2_block samples and interpolated linearly between.  set_fading(None | dict) changes
+    it between any two execute calls; it holds no stream state."""
+
+    def __init__(self, taps=((0, 1.0),), cfo_step=0, phase0=0, gain=1.0, noise_std=0.0, seed=0, output_format="cf32", fading=None):
         self._h = C.c_void_p()
         output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
         taps = list(taps)
@@ -735,11 +792,42 @@ class chanemu(object):
             c.delay[i], c.tap_re[i], c.tap_im[i] = int(d), complex(a).real, complex(a).imag
         c.cfo_step, c.phase0 = int(cfo_step) % (1 << 32), int(phase0) % (1 << 32)
         c.gain, c.noise_std, c.seed, c.output_format = float(gain), float(noise_std), int(seed) % (1 << 64), output_format
+        fading = self._fading_struct(len(taps), fading)
         rc = lib().mcrx_hip_chanemu_create(C.byref(self._h), C.addressof(c))
         if rc != MCRX_OK:
             self._h = C.c_void_p()
             self._chk(rc, "mcrx_hip_chanemu_create")
         self.taps, self.output_format = [(int(d), complex(a)) for d, a in taps], output_format
+        if fading is not None:
+            self._chk(lib().mcrx_hip_chanfade_set(self._h, C.addressof(fading)), "mcrx_hip_chanfade_set")
+
+    @staticmethod
+    def _fading_struct(num_taps, fading):
+        if fading is None:
+            return None
+        if not isinstance(fading, dict) or any(k not in _FADING_KEYS for k in fading):
+            raise ValueError("fading is None or a dict with keys of %s" % (_FADING_KEYS,))
+        return chanemu_fading(num_taps, **fading)
+
+    def set_fading(self, fading):
+        """None: fading off (the emulator of constant rays); a dict as at construction: fading on with these parameters.  The gains
+        are a function of the absolute sample index, so this may be called between any two execute calls."""
+        f = self._fading_struct(len(self.taps), fading)
+        self._chk(lib().mcrx_hip_chanfade_set(self._h, C.addressof(f) if f is not None else None), "mcrx_hip_chanfade_set")
+
+    def fading_on(self):
+        return bool(lib().mcrx_hip_chanfade_on(self._h))
+
+    def gains(self, first_row, rows, stream=None):
+        """The gain table's rows first_row .. first_row + rows - 1 (grid row b = n >> log2_block) as a complex64 CUDA tensor
+        [rows, num_taps]: what the execute calls interpolate between.  For tests and measurements."""
+        import torch
+        out = torch.zeros((int(rows), CHANEMU_MAX_TAPS), dtype=torch.complex64, device="cuda")
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device)
+        self._chk(lib().mcrx_hip_chanfade_gains(self._h, int(first_row) % (1 << 64), int(rows), _dptr(out), _stream_ptr(stream)),
+                  "mcrx_hip_chanfade_gains")
+        return out[:, :len(self.taps)]
 
     @staticmethod
     def _chk(rc, name):

@@ -8,7 +8,17 @@
 //   out  = v[n] (cf32)  or  Q(v[n]) (sc16: sc16.hpp, the shared quantiser as it stands)
 // w[n]: Box-Muller on the words Philox4x32-10 gives for counter (n >> 1, 0, 0) and key seed; sample n takes words 2 (n & 1), 2 (n & 1) + 1.
 //
-// chanemu_kernel<ROT, NOISE, FMT>: streaming, no LDS.  A lane owns the index-aligned pair (2k, 2k + 1): one Philox evaluation serves
+// With fading on (mcrx_hip_chanfade_*) the constant a_i becomes g_i(n) a_i, where g_i is a sum of sinusoids sampled
+// on the grid n = b 2^L and interpolated linearly between its rows -- a function of n again:
+//   G_i[b] = c_los_i e((psi_i << 32) + Lambda_i n_b) + c_sc_i sum_{k<S} e((Phi_ik << 32) + N_ik n_b)      n_b = b << L, phases mod 2^64,
+//                                                       e(p) = sincos_u32(p >> 32); LOS first, then k ascending, one fmaf per term
+//   g_i(n) = fmaf(f, G_i[b+1] - G_i[b], G_i[b])          b = n >> L, f = (n & (2^L - 1)) 2^-L (exact), per component
+//   s[n]   = sum_i (g_i(n) a_i) x[n - d_i]               the product in cmul_fx's shape, then the two fmaf per component as above
+// chanemu_gain_kernel writes the rows a span of samples needs into the handle's table (float2 [row][MCRX_CHANEMU_MAX_TAPS]), a lane per
+// (row, ray); chanemu_kernel<..., FADE = true> reads two rows per ray.  The integers (steps, phases) are made on the host from the
+// fading seed (fading_ray) and travel as kernel arguments.
+//
+// chanemu_kernel<ROT, NOISE, FMT, FADE>: streaming, no LDS.  A lane owns the index-aligned pair (2k, 2k + 1): one Philox evaluation serves
 // it, and its accesses are 16 bytes where the address allows (a uniform choice per tap: all lanes' pairs have the same parity).  A tap's
 // reads are the input shifted by d_i -- coalesced, re-reading lines the neighbouring lanes and workgroups fetch anyway.  Reads in
 // front of the call's first sample come from the handle's history (the last D = max d_i inputs), of which hist_len are valid; the rest
@@ -61,7 +71,34 @@ struct ChanemuArgs {
     uint32_t cfo_step, phase0;
     float gain, nstd;
     uint64_t seed;
+    // FADE builds only: the gain table of this span, its row 0 = grid row row0 = pos >> L; rows = rows it holds; finv = 2^-L
+    const float2 *gtab; uint64_t row0; uint32_t L, rows; float finv;
 };
+
+// The sinusoids of the fading gains: per ray the line-of-sight term [0] and S scattered ones [1 .. S]
+struct FadeTables {
+    int64_t step[MCRX_CHANEMU_MAX_TAPS][MCRX_CHANEMU_MAX_SINUSOIDS + 1];      // 2^64 * cycles per wideband sample
+    uint32_t phase[MCRX_CHANEMU_MAX_TAPS][MCRX_CHANEMU_MAX_SINUSOIDS + 1];    // 2^32 * cycles
+    float c_los[MCRX_CHANEMU_MAX_TAPS], c_sc[MCRX_CHANEMU_MAX_TAPS];
+    uint32_t S;
+};
+
+// table[row][ray] = G_ray[row0 + row], row < rows: blockIdx.y is the ray (its integers are scalar loads), a lane per row
+__global__ __launch_bounds__(256) void chanemu_gain_kernel(FadeTables t, float2 *table, uint64_t row0, uint32_t rows, uint32_t L)
+{
+    const uint32_t row = blockIdx.x * 256u + threadIdx.x, ray = blockIdx.y;
+    if (row >= rows) return;
+    const uint64_t nb = (row0 + row) << L;                              // the grid index wraps with the 64-bit position
+    float sn, cs;
+    sincos_u32((uint32_t)((((uint64_t)t.phase[ray][0] << 32) + (uint64_t)t.step[ray][0] * nb) >> 32), sn, cs);
+    float2 G = make_float2(t.c_los[ray] * cs, t.c_los[ray] * sn);
+    const float c = t.c_sc[ray];
+    for (uint32_t k = 1; k <= t.S; k++) {
+        sincos_u32((uint32_t)((((uint64_t)t.phase[ray][k] << 32) + (uint64_t)t.step[ray][k] * nb) >> 32), sn, cs);
+        G.x = fmaf(c, cs, G.x); G.y = fmaf(c, sn, G.y);
+    }
+    table[(size_t)row * MCRX_CHANEMU_MAX_TAPS + ray] = G;
+}
 
 // x[pos + r] for one sample: the input, the history, or a zero in front of the last reset (and for the masked half of an edge pair)
 __device__ __forceinline__ float2 chanemu_fetch(const ChanemuArgs &a, long long r)
@@ -102,7 +139,7 @@ __device__ __forceinline__ float2 chanemu_sample(const ChanemuArgs &a, float2 s,
     return v;
 }
 
-template <bool ROT, bool NOISE, int FMT>
+template <bool ROT, bool NOISE, int FMT, bool FADE>
 __global__ __launch_bounds__(256) void chanemu_kernel(ChanemuArgs a)
 {
     // lane g owns absolute samples base + 2 g, + 1 with base = pos & ~1: relative to in[0] that is m0 = 2 g - (pos & 1), m0 + 1
@@ -116,15 +153,32 @@ __global__ __launch_bounds__(256) void chanemu_kernel(ChanemuArgs a)
 #pragma unroll
         for (int i = 0; i < MCRX_CHANEMU_MAX_TAPS; i++)                 // every tap's loads first: T pairs in flight
             if (i < (int)a.T) chanemu_fetch_pair(a, m0 - (long long)a.delay[i], x0[i], x1[i]);
+        const uint64_t nabs = (a.pos - odd) + 2 * g;                    // even; wraps with the 64-bit position
         float2 s0 = make_float2(0.f, 0.f), s1 = s0;
+        // FADE: the pair's grid row (2^L is even: a pair never straddles one) relative to the table's first, and its two fractions
+        const float2 *grow = nullptr;
+        float f0 = 0.f, f1 = 0.f;
+        if (FADE) {
+            const uint64_t row = ((nabs >> a.L) - a.row0) & (~(uint64_t)0 >> a.L);
+            grow = a.gtab + (size_t)(row < a.rows - 1u ? row : a.rows - 2u) * MCRX_CHANEMU_MAX_TAPS;     // (row + 1 < rows for every pair of the span)
+            const uint32_t frac = (uint32_t)nabs & ((1u << a.L) - 1u);
+            f0 = (float)frac * a.finv; f1 = (float)(frac + 1u) * a.finv;
+        }
 #pragma unroll
         for (int i = 0; i < MCRX_CHANEMU_MAX_TAPS; i++)
-            if (i < (int)a.T) {
+            if (i < (int)a.T && FADE) {
+                const float2 G0 = grow[i], G1 = grow[MCRX_CHANEMU_MAX_TAPS + i];
+                const float dx = G1.x - G0.x, dy = G1.y - G0.y;
+                const float2 av = make_float2(a.are[i], a.aim[i]);
+                const float2 h0 = cmul_fx(make_float2(fmaf(f0, dx, G0.x), fmaf(f0, dy, G0.y)), av);
+                const float2 h1 = cmul_fx(make_float2(fmaf(f1, dx, G0.x), fmaf(f1, dy, G0.y)), av);
+                s0.x = fmaf(h0.x, x0[i].x, fmaf(-h0.y, x0[i].y, s0.x)); s0.y = fmaf(h0.x, x0[i].y, fmaf(h0.y, x0[i].x, s0.y));
+                s1.x = fmaf(h1.x, x1[i].x, fmaf(-h1.y, x1[i].y, s1.x)); s1.y = fmaf(h1.x, x1[i].y, fmaf(h1.y, x1[i].x, s1.y));
+            } else if (i < (int)a.T) {
                 const float ar = a.are[i], ai = a.aim[i];
                 s0.x = fmaf(ar, x0[i].x, fmaf(-ai, x0[i].y, s0.x)); s0.y = fmaf(ar, x0[i].y, fmaf(ai, x0[i].x, s0.y));
                 s1.x = fmaf(ar, x1[i].x, fmaf(-ai, x1[i].y, s1.x)); s1.y = fmaf(ar, x1[i].y, fmaf(ai, x1[i].x, s1.y));
             }
-        const uint64_t nabs = (a.pos - odd) + 2 * g;                    // even; wraps with the 64-bit position
         Philox4 w = {};
         if (NOISE) w = chanemu_pair_words(a.seed, nabs);
         const float2 v0 = chanemu_sample<ROT, NOISE>(a, s0, nabs, w.w[0], w.w[1]);
@@ -168,7 +222,77 @@ struct mcrx_hip_chanemu_s {
     uint32_t hist_len = 0;      // valid samples at the end of hist[cur] (the rest: zeros in front of the last reset)
     float2 *hist[2] = { nullptr, nullptr }; int cur = 0;
     Sc16ClipCount clip;         // sc16 handles only (allocated at creation): clipped samples since the handle was made
+    bool fade = false;          // fading on: ft holds the sinusoids of rays 0 .. num_taps - 1
+    FadeTables ft = {};
+    uint32_t fade_L = 0, fade_cap = 0;              // log2 of the update interval; the most rows of the table a span may use
+    float2 *gtab = nullptr; uint32_t gtab_rows = 0; // the gain table and the rows allocated (grown on demand, never shrunk)
 };
+
+// 2^18 rows = 16 MB at most, and only what a call needs: at L = 10 that is one span for 2.7e8 samples (the 512-channel slab is 2.1e8),
+// at L = 6 a span of 1.7e7 samples = 0.27 GB of traffic, against which three launches are nothing; a larger table buys no speed
+static const uint32_t FADE_DEFAULT_ROWS = 1u << 18;
+
+static const char *fading_check(const mcrx_hip_chanemu_fading *f, unsigned ray0, unsigned ray1)
+{
+    if (f->struct_size != sizeof(mcrx_hip_chanemu_fading)) return "mcrx_hip_chanemu_fading: wrong struct_size";
+    if (f->log2_block < 1 || f->log2_block > 24) return "log2_block must be 1 .. 24";
+    if (f->num_sinusoids < 1 || f->num_sinusoids > MCRX_CHANEMU_MAX_SINUSOIDS) return "num_sinusoids must be 1 .. 16";
+    if (f->table_rows == 1) return "table_rows must be 0 (default) or at least 2";
+    const double B = (double)(1u << f->log2_block);
+    for (unsigned i = ray0; i < ray1; i++) {
+        if (!std::isfinite(f->doppler[i]) || !std::isfinite(f->los_doppler[i])) return "a Doppler is not finite";
+        if (f->doppler[i] < 0.0) return "doppler must not be negative";
+        if (f->doppler[i] * B > 0.125 || std::fabs(f->los_doppler[i]) * B > 0.125) return "a Doppler times the update interval exceeds 1/8: the grid does not sample the gain";
+        if (!std::isfinite(f->rice_k[i]) || f->rice_k[i] < 0.f) return "rice_k must be finite and not negative";
+    }
+    return nullptr;
+}
+
+// the integers and coefficients of one ray (a checked configuration): entry 0 the line-of-sight term, then the S scattered sinusoids
+static void fading_ray(const mcrx_hip_chanemu_fading *f, unsigned i, int64_t *steps, uint32_t *phases, float coef[2])
+{
+    const uint32_t S = f->num_sinusoids;
+    steps[0] = (int64_t)std::rint(f->los_doppler[i] * 18446744073709551616.0);
+    phases[0] = f->los_phase[i];
+    for (uint32_t k = 0; k < S; k++) {
+        const Philox4 w = philox4x32_10(k, i, 1u, 0u, (uint32_t)f->seed, (uint32_t)(f->seed >> 32));
+        const double alpha = 2.0 * 3.14159265358979323846 * ((double)k + (double)w.w[0] * 2.3283064365386963e-10) / (double)S;
+        steps[1 + k] = (int64_t)std::rint(f->doppler[i] * std::cos(alpha) * 18446744073709551616.0);
+        phases[1 + k] = w.w[1];
+    }
+    const double K = (double)f->rice_k[i];
+    coef[0] = (float)std::sqrt(K / (K + 1.0));
+    coef[1] = (float)std::sqrt(1.0 / ((K + 1.0) * (double)S));
+}
+
+extern "C" int mcrx_hip_chanfade_selftest(const mcrx_hip_chanemu_fading *f, unsigned ray, int64_t *steps, uint32_t *phases, float coef[2])
+{
+    if (!f || !steps || !phases || !coef) { g_ce_err = "null pointer"; return MCRX_EINVAL; }
+    if (ray >= MCRX_CHANEMU_MAX_TAPS) { g_ce_err = "ray must be 0 .. 7"; return MCRX_EINVAL; }
+    if (const char *bad = fading_check(f, ray, ray + 1)) { g_ce_err = bad; return MCRX_EINVAL; }
+    fading_ray(f, ray, steps, phases, coef);
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_chanfade_set(mcrx_hip_chanemu_t q, const mcrx_hip_chanemu_fading *f)
+{
+    if (!q) { g_ce_err = "null handle"; return MCRX_EINVAL; }
+    if (!f) { q->fade = false; return MCRX_OK; }
+    if (const char *bad = fading_check(f, 0, q->cfg.num_taps)) { g_ce_err = bad; return MCRX_EINVAL; }
+    FadeTables &t = q->ft;
+    t = FadeTables();
+    t.S = f->num_sinusoids;
+    for (uint32_t i = 0; i < q->cfg.num_taps; i++) {
+        float coef[2];
+        fading_ray(f, i, t.step[i], t.phase[i], coef);
+        t.c_los[i] = coef[0]; t.c_sc[i] = coef[1];
+    }
+    q->fade_L = f->log2_block;
+    q->fade_cap = f->table_rows ? f->table_rows : FADE_DEFAULT_ROWS;
+    q->fade = true;
+    return MCRX_OK;
+}
+extern "C" int mcrx_hip_chanfade_on(mcrx_hip_chanemu_t q) { return q && q->fade ? 1 : 0; }
 
 extern "C" const char *mcrx_hip_chanemu_last_error(void) { return g_ce_err.c_str(); }
 
@@ -219,6 +343,7 @@ extern "C" int mcrx_hip_chanemu_destroy(mcrx_hip_chanemu_t q)
     if (!q) return MCRX_OK;
     (void)hipDeviceSynchronize();
     for (float2 *p : q->hist) if (p) (void)hipFree(p);
+    if (q->gtab) (void)hipFree(q->gtab);
     q->clip.release();
     delete q;
     return MCRX_OK;
@@ -235,14 +360,17 @@ extern "C" int mcrx_hip_chanemu_reset(mcrx_hip_chanemu_t q) { return mcrx_hip_ch
 extern "C" uint64_t mcrx_hip_chanemu_position(mcrx_hip_chanemu_t q) { return q ? q->pos : 0; }
 extern "C" unsigned mcrx_hip_chanemu_output_format(mcrx_hip_chanemu_t q) { return q ? q->cfg.output_format : 0u; }
 
-template <int FMT>
+template <int FMT, bool FADE>
 static void chanemu_launch(const ChanemuArgs &a, bool rot, bool noise, dim3 grid, hipStream_t st)
 {
-    if (rot) { if (noise) hipLaunchKernelGGL((chanemu_kernel<true, true, FMT>), grid, dim3(256), 0, st, a);
-               else       hipLaunchKernelGGL((chanemu_kernel<true, false, FMT>), grid, dim3(256), 0, st, a); }
-    else     { if (noise) hipLaunchKernelGGL((chanemu_kernel<false, true, FMT>), grid, dim3(256), 0, st, a);
-               else       hipLaunchKernelGGL((chanemu_kernel<false, false, FMT>), grid, dim3(256), 0, st, a); }
+    if (rot) { if (noise) hipLaunchKernelGGL((chanemu_kernel<true, true, FMT, FADE>), grid, dim3(256), 0, st, a);
+               else       hipLaunchKernelGGL((chanemu_kernel<true, false, FMT, FADE>), grid, dim3(256), 0, st, a); }
+    else     { if (noise) hipLaunchKernelGGL((chanemu_kernel<false, true, FMT, FADE>), grid, dim3(256), 0, st, a);
+               else       hipLaunchKernelGGL((chanemu_kernel<false, false, FMT, FADE>), grid, dim3(256), 0, st, a); }
 }
+
+// rows of the gain table the samples pos .. pos + n - 1 read (n >= 1): their own grid rows and the one behind the last
+static uint64_t fade_rows(uint64_t pos, uint64_t n, uint32_t L) { return (((pos & (((uint64_t)1 << L) - 1)) + n - 1) >> L) + 2; }
 
 extern "C" int mcrx_hip_chanemu_execute_device(mcrx_hip_chanemu_t q, const void *d_in, size_t n, void *d_out, void *stream)
 {
@@ -259,24 +387,68 @@ extern "C" int mcrx_hip_chanemu_execute_device(mcrx_hip_chanemu_t q, const void 
     if (n == 0) return MCRX_OK;
     hipStream_t st = (hipStream_t)stream;
     const mcrx_hip_chanemu_config &c = q->cfg;
+    const bool fade = q->fade;
+    uint32_t cap = 0;                                                   // fading: the rows of the table a span may use
+    if (fade) {
+        const uint64_t want = fade_rows(q->pos, n, q->fade_L);
+        cap = (uint32_t)(want < q->fade_cap ? want : q->fade_cap);
+        if (cap > q->gtab_rows) {                                       // grow (hipFree waits for the calls in flight); steady state: never
+            const uint64_t twice = 2ull * q->gtab_rows < q->fade_cap ? 2ull * q->gtab_rows : q->fade_cap;
+            const uint32_t rows = (uint32_t)(twice > cap ? twice : cap);
+            if (q->gtab) { CECHK(hipFree(q->gtab)); q->gtab = nullptr; q->gtab_rows = 0; }
+            CECHK(hipMalloc((void **)&q->gtab, (size_t)rows * MCRX_CHANEMU_MAX_TAPS * sizeof(float2)));
+            q->gtab_rows = rows;
+        }
+    }
     ChanemuArgs a = {};
-    a.in = static_cast<const float2 *>(d_in); a.out = d_out; a.hist = q->hist[q->cur]; a.clip = q->clip.device();
-    a.pos = q->pos; a.n = n; a.D = q->D; a.hist_len = q->hist_len; a.T = c.num_taps;
+    a.clip = q->clip.device(); a.D = q->D; a.T = c.num_taps;
     for (uint32_t i = 0; i < c.num_taps; i++) { a.delay[i] = c.delay[i]; a.are[i] = c.tap_re[i]; a.aim[i] = c.tap_im[i]; }
     a.cfo_step = c.cfo_step; a.phase0 = c.phase0; a.gain = c.gain; a.nstd = c.noise_std; a.seed = c.seed;
-    const uint64_t pairs = ((q->pos & 1u) + n + 1) >> 1;
-    const dim3 grid((unsigned)((pairs + 255) / 256));
     const bool rot = c.cfo_step != 0 || c.phase0 != 0, noise = c.noise_std != 0.f;
-    if (sc16) chanemu_launch<IQ_SC16>(a, rot, noise, grid, st); else chanemu_launch<IQ_CF32>(a, rot, noise, grid, st);
-    CECHK(hipGetLastError());
-    if (q->D) {
-        hipLaunchKernelGGL(chanemu_history_kernel, dim3((q->D + 255) / 256), dim3(256), 0, st, a, q->hist[q->cur ^ 1]);
+    // without fading one span; with it, spans of at most cap - 1 grid intervals: gain kernel -> main kernel -> history kernel each.
+    // The operator is cut-invariant, so the spans are invisible in the output.
+    for (size_t off = 0; off < n; ) {
+        size_t m = n - off;
+        if (fade) {
+            const uint64_t avail = ((uint64_t)(cap - 1) << q->fade_L) - (q->pos & (((uint64_t)1 << q->fade_L) - 1));
+            m = m < avail ? m : (size_t)avail;
+            a.L = q->fade_L; a.row0 = q->pos >> q->fade_L; a.rows = (uint32_t)fade_rows(q->pos, m, q->fade_L); a.gtab = q->gtab;
+            a.finv = std::ldexp(1.0f, -(int)q->fade_L);
+            hipLaunchKernelGGL(chanemu_gain_kernel, dim3((a.rows + 255) / 256, c.num_taps), dim3(256), 0, st, q->ft, q->gtab, a.row0, a.rows, a.L);
+            CECHK(hipGetLastError());
+        }
+        a.in = static_cast<const float2 *>(d_in) + off;
+        a.out = sc16 ? static_cast<void *>(static_cast<uint32_t *>(d_out) + off) : static_cast<void *>(static_cast<float2 *>(d_out) + off);
+        a.hist = q->hist[q->cur]; a.pos = q->pos; a.n = m; a.hist_len = q->hist_len;
+        const uint64_t pairs = ((q->pos & 1u) + m + 1) >> 1;
+        const dim3 grid((unsigned)((pairs + 255) / 256));
+        if (fade) { if (sc16) chanemu_launch<IQ_SC16, true>(a, rot, noise, grid, st); else chanemu_launch<IQ_CF32, true>(a, rot, noise, grid, st); }
+        else      { if (sc16) chanemu_launch<IQ_SC16, false>(a, rot, noise, grid, st); else chanemu_launch<IQ_CF32, false>(a, rot, noise, grid, st); }
         CECHK(hipGetLastError());
-        q->cur ^= 1;
-        q->hist_len = (uint32_t)((uint64_t)q->hist_len + n < q->D ? q->hist_len + n : q->D);
+        if (q->D) {
+            hipLaunchKernelGGL(chanemu_history_kernel, dim3((q->D + 255) / 256), dim3(256), 0, st, a, q->hist[q->cur ^ 1]);
+            CECHK(hipGetLastError());
+            q->cur ^= 1;
+            q->hist_len = (uint32_t)((uint64_t)q->hist_len + m < q->D ? q->hist_len + m : q->D);
+        }
+        q->pos += m;
+        off += m;
     }
-    q->pos += n;
     if (sc16) CECHK(q->clip.mark(st));
+    return MCRX_OK;
+}
+
+// the gain kernel on its own, into the caller's buffer: what execute_device computes for itself, for tests and measurements
+extern "C" int mcrx_hip_chanfade_gains(mcrx_hip_chanemu_t q, uint64_t first_row, uint32_t rows, void *d_table, void *stream)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_ce_err = "null handle"; return MCRX_EINVAL; }
+    if (!q->fade) { g_ce_err = "fading is off"; return MCRX_EINVAL; }
+    if (!d_table || (reinterpret_cast<uintptr_t>(d_table) & 7u)) { g_ce_err = "d_table must be an 8-byte aligned device buffer"; return MCRX_EINVAL; }
+    if (rows == 0) return MCRX_OK;
+    hipLaunchKernelGGL(chanemu_gain_kernel, dim3((rows + 255) / 256, q->cfg.num_taps), dim3(256), 0, (hipStream_t)stream, q->ft,
+                       static_cast<float2 *>(d_table), first_row, rows, q->fade_L);
+    CECHK(hipGetLastError());
     return MCRX_OK;
 }
 
