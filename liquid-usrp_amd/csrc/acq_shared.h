@@ -1,11 +1,16 @@
-// acq_shared.h -- what the kernels and the host's acquisition planner (acq_plan.hpp) both read: the limits of the segment-parallel
-// acquisition and the layout of the host-mapped hint block.  No HIP types: kernels.h includes it, and so do programs built by the
-// host compiler alone.
+// acq_shared.h -- what the kernels and the host's planners (acq_plan.hpp, rx_plan.hpp) both read: the limits of the segment-parallel
+// acquisition, the layout of the host-mapped hint block and the K = 7 decoder's row count.  No HIP types: kernels.h includes it, and
+// so do programs built by the host compiler alone.
 #pragma once
 #include <stdint.h>
 
 #define MCRX_SPEC_MAX 256        // slots per channel the scouts hold in registers at a time (kernels.h: SpecSlot)
 #define MCRX_SEG_MAX 128         // most segment waves per channel
+#ifdef __HIPCC__
+#define MCRX_HD __host__ __device__
+#else
+#define MCRX_HD
+#endif
 
 namespace mcrx {
 
@@ -32,5 +37,13 @@ enum HintWord {
     HINT_WORDS = 12
 };
 enum { HINT_WALK_BASE = HINT_WALKED, HINT_LIST_BASE = HINT_LIST_QAM };     // where walk_hint / list_hint point
+
+// the K = 7 decoder's geometry (csrc/viterbi_frames.hpp): T trellis steps in at most 64 blocks of a multiple of 24 steps, each run W steps
+// early and W steps long; a wave keeps B + 2 W decision rows of 512 bytes
+namespace vf {
+constexpr unsigned W = 48;
+MCRX_HD constexpr unsigned block_steps(unsigned T) { return 24u * ((T + 1535u) / 1536u); }
+MCRX_HD constexpr unsigned rows_for(unsigned T) { return block_steps(T) + 2u * W; }
+}
 
 }  // namespace mcrx

@@ -260,13 +260,7 @@ struct SyncArgs {
     int payload_fr, payload_lean, payload_xb;      // which build of the M = 64 workers (MCRX_PAYLOAD_FR / _LEAN / _XB at creation; defaults 1, 1, 63): the parity tests compare them
     uint32_t vit_off;          // byte offset of the convolutional decoder's 8 KB block scratch in the launch's dynamic LDS (0: none; set by the launchers)
 };
-// the K = 7 decoder's geometry (csrc/viterbi_frames.hpp): T trellis steps in at most 64 blocks of a multiple of 24 steps, each run W steps
-// early and W steps long; a wave keeps B + 2 W decision rows of 512 bytes
-namespace vf {
-constexpr unsigned W = 48;
-__host__ __device__ constexpr unsigned block_steps(unsigned T) { return 24u * ((T + 1535u) / 1536u); }
-__host__ __device__ constexpr unsigned rows_for(unsigned T) { return block_steps(T) + 2u * W; }
-}
+// (the K = 7 decoder's geometry, vf::W / block_steps / rows_for: acq_shared.h -- the host-only sizing plan reads it too)
 hipError_t sync_launch(const SyncArgs &a, hipStream_t st);           // full state machine, one wave per channel (general configurations; tail kernel)
 hipError_t sync_launch_tail(const SyncArgs &a, hipStream_t st);      // lean configurations: payloads in progress, to the frame's end (a.tail_only = 1)
 // fill `map` for the `nlen` coded lengths lens[k] at coded-byte offsets offs[k]; lo / hi: scratch of the map's size in bytes / 2 each

@@ -9,6 +9,7 @@
 #include "devmath.h"
 #include "devscope.hpp"
 #include "kernels.h"
+#include "rx_plan.hpp"
 #include "sc16.hpp"
 #include "txcode.hpp"
 
@@ -23,7 +24,6 @@
 
 using namespace mcrx;
 
-#define MCRX_SLOTS 8        /* most per-launch buffer sets (channel tiles, job list, per-job scratch); launch k uses slot k % nslots */
 #define MCRX_GENS 4         /* result generations (records + arenas), a ring: one fills while older ones are harvested or dropped */
 
 static thread_local std::string g_err;
@@ -140,22 +140,19 @@ struct HostArena {
     void release() { if (p) (void)hipHostFree(p); p = nullptr; size = cap = 0; }
 };
 
-struct mcrx_hip_s {
+// (the sizes and build selectors it lives by: its base, rx_plan.hpp -- q->max_enc, q->nch, q->nslots, ...)
+struct mcrx_hip_s : RxPlan {
     int device = -1;            // the HIP device the handle was created on: every entry point runs with it current (devscope.hpp)
-    unsigned N = 0, K = 0, M = 0, cp = 0, taper = 0;
-    bool bypass = false;                    // one synchronizer fed channel-rate samples, no channelizer (ofdmtxrx)
+    unsigned N = 0, M = 0, cp = 0, taper = 0;
     OfdmDesign od;
     mcrx_hip_config cfg{};
     std::vector<float> taps;
-    uint32_t dtheta = 0, slab_blocks = 0, ncu = 256;
+    uint32_t dtheta = 0, ncu = 256;
     const float *d_taps = nullptr;
     SyncConsts sc{};
-    std::vector<void *> owned;              // device allocations freed at destroy
+    // what the handle owns until it is destroyed: device allocations, events, streams (alloc / new_event / new_stream below)
+    std::vector<void *> owned; std::vector<hipEvent_t> owned_events; std::vector<hipStream_t> owned_streams;
     // synchronizer bank
-    unsigned ch_first = 0, nch = 0;
-    uint32_t max_payload = 0, max_enc = 0, max_syms = 0, max_rec = 0;
-    uint32_t max_jobs = 0;                  // job list entries per launch: the frames (max_rec) + the entries the segment waves fill for nothing (two per segment) + void reservations
-    uint64_t arena_cap = 0;
     ChanState *d_st = nullptr; uint8_t *d_hbits = nullptr; float2 *d_R = nullptr;
     uint8_t *d_soft = nullptr, *d_tmpa = nullptr, *d_tmpb = nullptr; float2 *d_syms = nullptr;
     // results: two generations.  Launches write into generation `gen`; a harvest closes it (new launches go to
@@ -163,27 +160,19 @@ struct mcrx_hip_s {
     FrameRec *d_rec[MCRX_GENS] = {}; uint8_t *d_arena[MCRX_GENS] = {}, *d_sarena[MCRX_GENS] = {};
     uint32_t *d_nrec[MCRX_GENS] = {}; unsigned long long *d_arena_used[MCRX_GENS] = {};
     int gen = 0; bool gen_used[MCRX_GENS] = {}, gen_closed[MCRX_GENS] = {}, gen_abandoned[MCRX_GENS] = {};
-    uint32_t round_lds_pad = 0;      // the same cap outside walk mode (MCRX_PAYLOAD_LDS_PAD)
-    uint32_t walk_lds_pad = 13312;   // walk mode: unused LDS per payload worker = at most three of them per SIMD, the fourth slot is the walking scouts' (95 -> 110 Gsample/s on ragged traffic)
-    int payload_fr = 1, payload_lean = 1, payload_xb = 63;      // MCRX_PAYLOAD_FR / _LEAN / _XB: which build of the M = 64 payload workers (tests)
-    int debug = 0, no_fast = 0, seek_burst = 1, acq_mode = 0; bool free_run = false;      // MCRX_DEBUG (trace bits), MCRX_NO_FAST, MCRX_FREE_RUN: read once, at creation
+    int debug = 0, no_fast = 0, seek_burst = 1; bool free_run = false;      // MCRX_DEBUG (trace bits), MCRX_NO_FAST, MCRX_FREE_RUN: read once, at creation
     hipStream_t acq_stream = nullptr;        // the stream the last launch's acquisition / placement kernels ran on (they write the generation's counters)
     uint64_t gen_close_seq[MCRX_GENS] = {}, close_counter = 0;      // order in which generations were closed (= delivery order)
     hipEvent_t ev_gen[MCRX_GENS] = {};       // recorded behind the last launch that wrote into the generation
     hipEvent_t ev_clean[MCRX_GENS] = {};     // recorded behind the zeroing of a collected generation's counters: the next launch into it starts behind that
     bool clean_pending[MCRX_GENS] = {};
-    uint64_t sarena_cap = 0;
     // per-launch slots
     PayloadJob *d_jobs[MCRX_SLOTS] = {}; uint32_t *d_njobs = nullptr; float2 *d_jR[MCRX_SLOTS] = {};
     uint32_t *d_gen[MCRX_SLOTS] = {}, *d_qam[MCRX_SLOTS] = {}, *d_live[MCRX_SLOTS] = {};
-    uint2 *d_vit_scratch = nullptr; uint32_t vit_rows = 0, vit_waves = 0, vit_mode = 0; uint32_t *d_vit_passes = nullptr;      // the K = 7 decoder's decision rows (kernels.h: vit_scratch)
+    uint2 *d_vit_scratch = nullptr; uint32_t *d_vit_passes = nullptr;      // the K = 7 decoder's decision rows (kernels.h: vit_scratch)
     uint64_t seq = 0;                       // synchronizer launches so far (slot = seq % nslots)
-    unsigned nslots = 5;                    // buffer sets in use: the channelizer and the acquisition chain of up to nslots - 1 pushes run ahead of the payload workers
     uint32_t *d_stats = nullptr;            // speculation statistics (SyncArgs::stats)
-    // internal streams: channelizer | acquisition (speculative waves, scouts, placement) | payload workers + decode.
-    // Launch k+1's acquisition -- a chain of dependent events per channel, a few waves per CU -- runs under launch
-    // k's payload/decode kernels, and launch k+1's channelizer as soon as CUs free up.
-    bool pipelined = true;
+    // internal streams (RxPlan::pipelined)
     hipStream_t s_scout = nullptr, s_work = nullptr, s_copy = nullptr;
     // the launches that normally find nothing to do (kernels.h, split_rest), while that is what they have been finding
     hipStream_t s_side = nullptr; hipEvent_t ev_side[MCRX_SLOTS] = {}, ev_side_last = nullptr; bool side_last = false;
@@ -193,43 +182,29 @@ struct mcrx_hip_s {
     bool carried = false; uint64_t carried_seq = 0; // ... and whether that launch's channelizer already wrote it into the front of launch carried_seq's slot (ChanArgs::out2)
     uint32_t spec_stride = MCRX_SPEC_MAX;           // slots per channel in d_spec (grows when a push holds more frames per channel: launch_sync)
     SpecSlot *d_spec = nullptr; float2 *d_spec_R = nullptr; int64_t *d_anchor = nullptr, *d_seekst = nullptr;
-    bool spec = false;
     uint32_t *h_hint = nullptr, *d_hint = nullptr;     // pinned, device-mapped: the hint block (acq_shared.h: HintWord)
     uint8_t *d_jsoft[MCRX_SLOTS] = {}, *d_jtmp[MCRX_SLOTS] = {};
-    bool scout = true, scout_tables = true, il_tried = false;
+    bool scout_tables = true, il_tried = false;
     bool acq_prio = true;                   // the acquisition stream is created with the highest priority (MCRX_NO_PRIO: not)
     AcqPolicy acq;                          // what the acquisition schedule remembers from launch to launch (acq_plan.hpp)
-    // scouts of the acquisition rounds: 1 = the lean scout's unbudgeted build (sync_walk_kernel: 256 + 40 registers, no spills), 0 = the
-    // 168-register build (293 spilled) that round 2 made to fit beside four 80-register payload workers.  With eight 56-register
-    // workers per SIMD neither fits beside them any more, and a scout that adopts 100 frames of a channel pays for every spill:
-    // 8 channels 54.7 -> 64.8 Gsample/s, 512 channels 166.4 -> 169.9 (same box, same run; MCRX_LEAN_BUILD)
-    int lean_build = 1;
-    int seg_walker = 1;                     // 1: the segment waves are the general state machine's kernel (default); mcrx_hip_config::scout_build = 2: acq_lean.hpp's
     // streaming state
     uint64_t total_samples = 0;             // wideband samples accepted since creation (NCO phase)
     uint64_t stage_first = 0;               // absolute index of h_stage[0]
     int64_t chan_samples = 0;               // channel-rate samples produced since creation
-    // the handle's wideband input format (mcrx_hip_config::input_format == sc16.hpp: IQ_*) and its bytes per sample.  The raw-sample
-    // history, both stagings and the bulk path's device buffers hold samples in that format: bytes, indexed in samples * ss
-    uint32_t in_fmt = IQ_CF32; size_t ss = sizeof(float2);
+    // (samples in the handle's input format, RxPlan::in_fmt: bytes, indexed in samples * ss)
     char *d_hist[2] = { nullptr, nullptr }; int hist_cur = 0;
     char *d_in = nullptr;                   // device staging (stage_cap samples)
-    char *h_stage = nullptr; size_t stage_cap = 0, stage_fill = 0;     // pinned host staging (samples)
+    char *h_stage = nullptr; size_t stage_fill = 0;     // pinned host staging (samples)
     float2 *d_chan[MCRX_SLOTS] = {}; size_t chan_cap_tiles = 0;
-    unsigned hist_tiles = 0; uint64_t defer = 0;
-    // taps per column of the bank channelizer_kernel runs and the blocks of FIR history it needs in front of every push: 14 / 13 = the
-    // reference's firpfbch (m = 7), 28 / 27 = the oversampled front end folded into one bank (cfg.front_end = 1; channelizer.hip)
-    unsigned chan_P = 14, hist_blocks = 13, col_shift = 0;
-    // oversampled front end stage by stage (cfg.front_end = 2, the form the oracle runs; kept as the cross-check of front_end = 1): the bank, its input (28 N samples of history in front) and output (32
+    // oversampled front end stage by stage (cfg.front_end = 2): the bank, its input (28 N samples of history in front) and output (32
     // steps of history in front), both double buffered so that a push's history comes from the other buffer
-    bool oversampled = false; mcrx_hip_pfb2_t pfb2 = nullptr; const float *d_h1 = nullptr;
+    mcrx_hip_pfb2_t pfb2 = nullptr; const float *d_h1 = nullptr;
     float2 *d_pfin[2] = { nullptr, nullptr }, *d_pfout[2] = { nullptr, nullptr }; size_t pf_cap_blocks = 0; int pf_cur = 0;
     uint64_t pf_in_valid = 0, pf_steps = 0; size_t pf_last_blocks = 0; bool pf_have_last = false;
     hipStream_t stream = nullptr;
     // large host buffers skip the staging copy: chunks go from the caller's memory to one of two device buffers
     char *d_direct[2] = { nullptr, nullptr }; size_t direct_cap = 0; int direct_idx = 0; bool direct_used[2] = { false, false };
     hipStream_t copy_stream = nullptr; hipEvent_t ev_dcopy[2] = { nullptr, nullptr }, ev_ddone[2] = { nullptr, nullptr };
-    uint64_t min_frame = 1;                 // channel-rate samples of the shortest possible frame
     uint64_t pending_bound = 0;             // upper bound of frame records produced since the last harvest
     uint64_t drain_touch = 0;
     double t_copy = 0, t_harvest = 0, t_run = 0, t_wait = 0, t_d2h = 0, b_d2h = 0, t_grow = 0, t_cnt = 0, t_post = 0;   // MCRX_DEBUG=8: host seconds spent per phase of the bulk path
@@ -245,7 +220,7 @@ struct mcrx_hip_s {
     int ev_begin(int which, hipStream_t st)
     {
         if (!ev_on) return MCRX_OK;
-        if (ev_dump && !ev_base) { HIPCHK(hipEventCreate(&ev_base)); HIPCHK(hipEventRecord(ev_base, st)); }
+        if (ev_dump && !ev_base) { RC(new_event(&ev_base, hipEventDefault)); HIPCHK(hipEventRecord(ev_base, st)); }
         // ring full: fold the older half (long finished in a running stream, so the host does not stall on it)
         if (ev_used[which] + 2 > evring[which].size()) RC(ev_resolve(which, evring[which].size() / 2));
         HIPCHK(hipEventRecord(evring[which][ev_used[which]], st));
@@ -311,6 +286,19 @@ struct mcrx_hip_s {
         HIPCHK(hipMalloc((void **)dst, std::max<size_t>(n, 1) * sizeof(T)));
         HIPCHK(hipMemset(*dst, 0, std::max<size_t>(n, 1) * sizeof(T)));
         owned.push_back(*dst);
+        return MCRX_OK;
+    }
+    int new_event(hipEvent_t *e, unsigned flags)
+    {
+        HIPCHK(hipEventCreateWithFlags(e, flags));
+        owned_events.push_back(*e);
+        return MCRX_OK;
+    }
+    // a blocking stream of default priority unless told otherwise (prio: as hipDeviceGetStreamPriorityRange counts; nullptr: the default)
+    int new_stream(hipStream_t *st, unsigned flags = hipStreamDefault, const int *prio = nullptr)
+    {
+        HIPCHK(prio ? hipStreamCreateWithPriority(st, flags, *prio) : flags ? hipStreamCreateWithFlags(st, flags) : hipStreamCreate(st));
+        owned_streams.push_back(*st);
         return MCRX_OK;
     }
 };
@@ -535,9 +523,6 @@ static int launch_monitor(mcrx_hip_t q, const float2 *chan, unsigned stride, uns
     return MCRX_OK;
 }
 
-// the raw-sample history of one buffer, rounded up to whole 16-byte units (what sync_reset_launch clears: an even number of cf32)
-static size_t hist_bytes(mcrx_hip_t q) { return ((size_t)q->hist_blocks * q->K * q->ss + 15) & ~(size_t)15; }
-
 // synchronizers back to SEEK, channelizer history cleared, undelivered device frames dropped
 static int restart_async(mcrx_hip_t q, hipStream_t st, bool from_zero)
 {
@@ -552,7 +537,7 @@ static int restart_async(mcrx_hip_t q, hipStream_t st, bool from_zero)
     for (int g = 0; g < MCRX_GENS; g++) {
         HIPCHK(sync_reset_launch(q->d_st, q->nch, q->chan_samples, g == 0 ? reinterpret_cast<float2 *>(q->d_hist[0]) : nullptr,
                                  g == 0 ? reinterpret_cast<float2 *>(q->d_hist[1]) : nullptr,
-                                 hist_bytes(q) / sizeof(float2), q->d_nrec[g], q->d_arena_used[g],
+                                 q->hist_bytes / sizeof(float2), q->d_nrec[g], q->d_arena_used[g],
                                  nullptr, st));
         q->gen_used[g] = false; q->gen_closed[g] = false; q->gen_abandoned[g] = false;
     }
@@ -562,30 +547,132 @@ static int restart_async(mcrx_hip_t q, hipStream_t st, bool from_zero)
     return MCRX_OK;
 }
 
-// The experiment switches of development builds (devel.h: constant nullptr in a release build), read once, behind the configuration's
-// fields and over them.  MCRX_DEBUG is the one variable a release build reads.
-static void read_devel_env(mcrx_hip_t q)
+// The experiment switches of development builds (devel.h: constant nullptr in a release build), read once: those that change a planned
+// value go to the plan, which applies them behind the configuration's fields and over them (rx_plan.hpp: RxDevel); the others set
+// flags of the handle.  MCRX_DEBUG is the one variable a release build reads.
+static void read_devel_env(mcrx_hip_t q, RxDevel *d)
 {
     q->debug = getenv("MCRX_DEBUG") ? atoi(getenv("MCRX_DEBUG")) : 0;
-    if (devel_env("MCRX_SERIAL")) q->pipelined = false;
-    q->scout = devel_env("MCRX_NO_SCOUT") == nullptr;
-    if (!q->scout || devel_env("MCRX_NO_SPEC")) q->spec = false;        // (speculation hands off through the scouts' job list)
+    d->serial = devel_env("MCRX_SERIAL"); d->slots = devel_env("MCRX_SLOTS");
+    d->no_scout = devel_env("MCRX_NO_SCOUT"); d->no_spec = devel_env("MCRX_NO_SPEC");
+    d->payload_fr = devel_env("MCRX_PAYLOAD_FR"); d->payload_lean = devel_env("MCRX_PAYLOAD_LEAN"); d->payload_xb = devel_env("MCRX_PAYLOAD_XB");
+    d->acq_mode = devel_env("MCRX_ACQ_MODE"); d->lean_build = devel_env("MCRX_LEAN_BUILD");
+    d->walk_lds_pad = devel_env("MCRX_WALK_LDS_PAD"); d->payload_lds_pad = devel_env("MCRX_PAYLOAD_LDS_PAD");
     if (devel_env("MCRX_NO_PRIO")) q->acq_prio = false;
     q->no_fast = devel_env_int("MCRX_NO_FAST", 0);
     q->free_run = devel_env("MCRX_FREE_RUN") != nullptr;
-    q->payload_fr = devel_env_int("MCRX_PAYLOAD_FR", q->payload_fr);
-    q->payload_lean = devel_env_int("MCRX_PAYLOAD_LEAN", q->payload_lean) != 0;
-    q->payload_xb = devel_env_int("MCRX_PAYLOAD_XB", q->payload_xb);
     q->seek_burst = devel_env_int("MCRX_SEEK_BURST", q->seek_burst);
-    q->acq_mode = devel_env_int("MCRX_ACQ_MODE", q->acq_mode);
-    q->lean_build = devel_env_int("MCRX_LEAN_BUILD", q->lean_build);
-    q->walk_lds_pad = (uint32_t)devel_env_int("MCRX_WALK_LDS_PAD", (int)q->walk_lds_pad);
-    q->round_lds_pad = (uint32_t)devel_env_int("MCRX_PAYLOAD_LDS_PAD", (int)q->round_lds_pad);
     if (devel_env("MCRX_EVT")) q->ev_on = true;
     if (devel_env("MCRX_EVT_DUMP")) { q->ev_on = true; q->ev_dump = true; }
-    if (devel_env("MCRX_SLOTS")) q->nslots = (unsigned)std::max(2, std::min(MCRX_SLOTS, atoi(devel_env("MCRX_SLOTS"))));
     if (devel_env("MCRX_NSEG")) q->acq.nseg_fixed = (uint32_t)std::max(1, std::min(MCRX_SEG_MAX, atoi(devel_env("MCRX_NSEG"))));         // segments per channel, fixed
     if (devel_env("MCRX_SEG_FRAMES")) q->acq.seg_frames = (uint32_t)std::max(1, std::min(64, atoi(devel_env("MCRX_SEG_FRAMES"))));         // ... or frames per segment aimed at
+}
+
+// ---- mcrx_hip_create in parts, in the order things are allocated: tables, buffers, streams and events (the sizes: rx_plan.hpp)
+static int create_tables(mcrx_hip_t q)
+{
+    q->taps = q->bypass ? std::vector<float>(14, 0.f) : pfb_prototype(q->K, 7, 60.0f);
+    q->dtheta = q->bypass ? 0u : channel_center_step(q->N);
+    // the channelizer's column tap table (kernels.h: ChanArgs::taps)
+    const std::vector<float> ct = q->chan_P == 28 ? pfb2_composite_taps(pfb2_prototype(q->K, 7, 60.0f), halfband_branch_taps(7, 60.0f), q->K)
+                                : q->bypass ? q->taps : pfb_column_taps(q->taps, q->K);
+    RC(q->upload(&q->d_taps, ct.data(), ct.size()));
+    RC(build_tables(q));
+    if (q->oversampled) {
+        if (mcrx_hip_pfb2_create(&q->pfb2, q->K, 7, 60.0f) != MCRX_OK) return fail(MCRX_EHIP, mcrx_hip_pfb2_last_error());
+        const std::vector<float> h1 = halfband_branch_taps(7, 60.0f);
+        RC(q->upload(&q->d_h1, h1.data(), h1.size()));
+    }
+    return MCRX_OK;
+}
+
+static int create_buffers(mcrx_hip_t q)
+{
+    const size_t nch = q->nch, M = q->M;
+    RC(q->alloc(&q->d_st, nch));
+    RC(q->alloc(&q->d_seekst, nch * 2));
+    RC(q->alloc(&q->d_hbits, nch * MCRX_HDR_SYMS));
+    RC(q->alloc(&q->d_R, nch * M));
+    RC(q->alloc(&q->d_soft, nch * 8 * q->max_enc));
+    RC(q->alloc(&q->d_tmpa, nch * (q->max_enc + 16)));
+    RC(q->alloc(&q->d_tmpb, nch * (q->max_enc + 16)));
+    RC(q->alloc(&q->d_syms, nch * q->max_syms));
+    for (int g = 0; g < MCRX_GENS; g++) {
+        RC(q->alloc(&q->d_rec[g], q->max_rec));
+        RC(q->alloc(&q->d_arena[g], q->arena_cap));
+        RC(q->alloc(&q->d_sarena[g], q->sarena_cap));
+        // (one 32-byte block per generation -- records, dropped | pad | payload bytes, symbol bytes -- so that a poll reads it with one
+        //  small copy and clears it with one fill: each of those waits ~0.1 ms for a slot on the full chip)
+        RC(q->alloc(&q->d_nrec[g], 8));
+        q->d_arena_used[g] = reinterpret_cast<unsigned long long *>(q->d_nrec[g] + 4);
+    }
+    RC(q->alloc(&q->d_njobs, MCRX_SLOTS));       // one counter per slot: a launch's placement kernel zeroes the next slot's
+    RC(q->alloc(&q->d_stats, 8));
+    // (coherent: with hipHostMallocMapped alone the allocation is non-coherent and a free-running host -- one that never
+    //  synchronizes with the device -- does not see the kernels' updates at all)
+    if (hipHostMalloc((void **)&q->h_hint, HINT_WORDS * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
+        for (int i = 0; i < HINT_WORDS; i++) q->h_hint[i] = 0;          // (the words: acq_shared.h, HintWord)
+        if (hipHostGetDevicePointer((void **)&q->d_hint, q->h_hint, 0) != hipSuccess) q->d_hint = nullptr;
+    }
+    q->spec = q->spec && q->d_hint;
+    if (q->scout) {
+        const size_t max_jobs = q->max_jobs;
+        for (unsigned sl = 0; sl < q->nslots; sl++) {
+            RC(q->alloc(&q->d_jobs[sl], max_jobs));
+            RC(q->alloc(&q->d_gen[sl], max_jobs + 1));
+            RC(q->alloc(&q->d_qam[sl], max_jobs + 1));
+            RC(q->alloc(&q->d_live[sl], max_jobs + 1));
+            RC(q->alloc(&q->d_jR[sl], max_jobs * M));
+            RC(q->alloc(&q->d_jsoft[sl], max_jobs * 8 * q->max_enc));
+            RC(q->alloc(&q->d_jtmp[sl], max_jobs * 2 * (q->max_enc + 16)));
+        }
+        if (q->vit_rows) {          // (the K = 7 decoder's scratch: at once only with cfg.conv_scratch = 1, else sync_lazy_allocs)
+            RC(q->alloc(&q->d_vit_passes, 8));
+            if (q->vit_mode == 1) RC(q->alloc_raw(&q->d_vit_scratch, (size_t)q->vit_waves * q->vit_rows * 64));
+        }
+        if (q->spec) {              // speculative acquisition (lean path only): slots, their equalisers, the anchors
+            RC(q->alloc(&q->d_spec, nch * MCRX_SPEC_MAX));
+            RC(q->alloc(&q->d_spec_R, nch * MCRX_SEG_MAX * M));
+            RC(q->alloc(&q->d_anchor, nch));
+        }
+    }
+    RC(q->alloc(&q->d_hist[0], q->hist_bytes));
+    RC(q->alloc(&q->d_hist[1], q->hist_bytes));
+    // host staging for Execute()
+    if (hipHostMalloc((void **)&q->h_stage, q->stage_cap * q->ss, hipHostMallocDefault) != hipSuccess)
+        return fail(MCRX_ENOMEM, "pinned staging allocation failed");
+    RC(q->alloc(&q->d_in, q->stage_cap * q->ss));
+    return MCRX_OK;
+}
+
+// Streams are mapped onto the hardware queues in the order they are created: that order is part of the measured design.
+static int create_streams_and_events(mcrx_hip_t q)
+{
+    // (blocking streams: work a caller puts on the legacy default stream -- e.g. a torch copy of a result buffer --
+    //  still orders against them, as it did when everything ran on one stream)
+    RC(q->new_stream(&q->stream));
+    {   // the acquisition stream carries the serial per-channel chains every payload launch waits for: highest priority
+        int least = 0, greatest = 0;
+        const bool prio = q->acq_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least;
+        RC(q->new_stream(&q->s_scout, hipStreamDefault, prio ? &greatest : nullptr));
+    }
+    RC(q->new_stream(&q->s_work));
+    // (With the others: a stream created in mid-stream shifts the queue mapping.  Only for receivers of few channels: their pushes are
+    //  chains of launch gaps, and three launches less in the work stream's chain are worth 15-18 % (8 channels: 65 -> 77 Gsample/s, with
+    //  the K = 7 code 41 -> 47); a receiver that fills the chip gains nothing from it, and the stream's mere existence cost 1 % of the
+    //  headline and 10 % of the pipeline leg in alternating runs -- scratch/r5/split_ab.sh.)
+    if (q->side_stream) RC(q->new_stream(&q->s_side));
+    RC(q->new_stream(&q->s_copy, hipStreamNonBlocking));
+    for (int g = 0; g < MCRX_GENS; g++) for (hipEvent_t *e : { &q->ev_gen[g], &q->ev_clean[g] }) RC(q->new_event(e, hipEventDisableTiming));
+    for (hipEvent_t *e : { &q->ev_in, &q->ev_consumed, &q->ev_tmp[0], &q->ev_tmp[1], &q->ev_tmp[2], &q->ev_tmp[3], &q->ev_side_last })
+        RC(q->new_event(e, hipEventDisableTiming));
+    for (int sl = 0; sl < MCRX_SLOTS; sl++)
+        for (hipEvent_t *e : { &q->ev_ready[sl], &q->ev_scout[sl], &q->ev_done[sl], &q->ev_side[sl] }) RC(q->new_event(e, hipEventDisableTiming));
+    for (int w = 0; w < MCRX_NKERNELS; w++) {
+        q->evring[w].resize(2048, nullptr);
+        for (auto &e : q->evring[w]) RC(q->new_event(&e, hipEventDefault));
+    }
+    return MCRX_OK;
 }
 
 extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned cp, unsigned taper,
@@ -615,185 +702,24 @@ extern "C" int mcrx_hip_create(mcrx_hip_t *out, unsigned N, unsigned M, unsigned
 
     mcrx_hip_t q = new mcrx_hip_s();
     q->device = current_device();
-    q->N = N; q->K = bypass ? 1 : 2 * N; q->M = M; q->cp = cp; q->taper = taper; q->bypass = bypass;
-    q->in_fmt = in_fmt; q->ss = in_fmt == IQ_SC16 ? 2 * sizeof(int16_t) : sizeof(float2);
+    q->N = N; q->M = M; q->cp = cp; q->taper = taper; q->cfg = ec;
     if (q->od.init(M, cp, taper, p) != 0) { delete q; return fail(MCRX_EINVAL, "invalid subcarrier allocation"); }
-    q->cfg = ec;
-    q->max_payload = q->cfg.max_payload_len ? q->cfg.max_payload_len : 2048;
-    q->max_enc = 4 * (q->max_payload + 4) + 16;
-    // floor: the per-frame scratch rows (max_enc + 16 bytes) also hold the soft Viterbi decoder's checkpoints, 128 bytes
-    // per 960 trellis steps = 128 * ceil((8 e0 + 6) / 960) <= 0.54 max_enc + 128 bytes for a frame that fits (e0 <= max_enc / 2
-    // behind the rate-1/2 code): covered from max_enc = 256 on (smaller rows were overrun by 128 bytes)
-    if (q->max_enc < 256) q->max_enc = 256;
-    q->max_enc = (q->max_enc + 15) & ~15u;
-    q->max_syms = 8 * q->max_enc;
-    q->ch_first = q->cfg.channel_first;
-    if (q->ch_first >= N || (uint64_t)q->ch_first + q->cfg.channel_count > N) { delete q; return fail(MCRX_EINVAL, "channel shard outside [0, N)"); }
-    q->nch = q->cfg.channel_count ? q->cfg.channel_count : N - q->ch_first;
-    q->max_rec = q->cfg.max_frames ? q->cfg.max_frames : 16 * q->nch + 64;
-    q->min_frame = (uint64_t)(3 + (288 + q->od.M_data - 1) / q->od.M_data + 2) * (M + cp);
-    if (!q->cfg.max_frames) {
-        // ... and never fewer than one host batch (Execute() harvests per batch) can hold: the shortest frame is
-        // S0a, S0b, S1, the header symbols, one payload symbol and the tail
-        const uint64_t batch = q->cfg.batch_samples ? q->cfg.batch_samples : ((uint64_t)1 << 20);
-        const uint64_t min_frame = q->min_frame;
-        const uint64_t per_ch = (batch / q->K + 8) / min_frame + 2;
-        q->max_rec = (uint32_t)std::max<uint64_t>(q->max_rec, std::min<uint64_t>(per_ch * q->nch, 1u << 22));
-        // ... and enough for bulk Execute() calls to run in chunks of up to 16 Mi samples between harvests, within
-        // about 2 GB of per-record buffers (arena share, soft bits, scratch, equaliser)
-        const uint64_t per_rec = ((((uint64_t)q->max_payload + 15) & ~15ull) + 64ull * (2ull * (q->max_payload + 4) + 8)) +
-                                 10ull * q->max_enc + 32 + 8ull * M;
-        const uint64_t bulk = std::min<uint64_t>((((uint64_t)16 << 20) / q->K + 8) / min_frame + 3, ((uint64_t)2 << 30) / per_rec / q->nch);
-        q->max_rec = (uint32_t)std::max<uint64_t>(q->max_rec, bulk * q->nch);
+    {   // every size, and the checks that are left: nothing is allocated for a configuration that is refused
+        RxInputs in{ N, M, cp, taper, ec, q->od.M_data, q->od.M_pilot, RxDevel() };
+        read_devel_env(q, &in.devel);
+        const char *why = "";
+        const int refused = rx_plan(in, q, &why);
+        if (refused) { delete q; return fail(refused, why); }
     }
-    // frame arenas (per result generation): payload bytes | equalised symbols, the latter reserved for BPSK
-    // behind one rate-1/2 code (longer frames still fit while the total stays below the cap; overflow is counted)
-    q->arena_cap = (uint64_t)q->max_rec * (((uint64_t)q->max_payload + 15) & ~15ull);
-    q->sarena_cap = (uint64_t)q->max_rec * (8ull * 8ull * (2ull * (q->max_payload + 4) + 8));
-    if (q->sarena_cap > (8ull << 30)) q->sarena_cap = 8ull << 30;
-    q->pipelined = !q->cfg.serial;
-    q->slab_blocks = q->cfg.slab_blocks ? ((q->cfg.slab_blocks + MCRX_TILE - 1) & ~(uint32_t)(MCRX_TILE - 1)) : 0;      // 0: sized per launch; slabs are whole tiles
     { int dev = 0, n = 0;
       if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
           q->ncu = (uint32_t)n; }
-    const uint32_t front_end = bypass ? 0 : q->cfg.front_end;
-    if (front_end > 2) { delete q; return fail(MCRX_EINVAL, "front_end must be 0, 1 or 2"); }
-    q->oversampled = front_end == 2;
-    if (front_end && ((q->K & (q->K - 1)) || q->K > 1024 || q->K < 2)) { delete q; return fail(MCRX_EUNSUPP, "the oversampled front end needs a power-of-two channel count <= 512"); }
-    if (front_end == 1) { q->chan_P = 28; q->hist_blocks = 27; q->col_shift = q->K / 2 + 1; }
-    q->taps = bypass ? std::vector<float>(14, 0.f) : pfb_prototype(q->K, 7, 60.0f);
-    q->dtheta = bypass ? 0u : channel_center_step(N);
-    // channel-rate history in front of every push's tiles: a symbol window, plus -- if frames straddling two pushes are
-    // to be deferred rather than walked serially -- the longest frame start-to-push-end distance to be covered
-    q->defer = q->cfg.defer_samples;
-    q->hist_tiles = (unsigned)((q->defer + M + cp + 8 + MCRX_TILE - 1) / MCRX_TILE + 1);
-
-    auto bail = [&](int rc) { mcrx_hip_destroy(q); return rc; };
     int rc;
-    {   // the channelizer's column tap table (kernels.h: ChanArgs::taps)
-        std::vector<float> ct = q->chan_P == 28 ? pfb2_composite_taps(pfb2_prototype(q->K, 7, 60.0f), halfband_branch_taps(7, 60.0f), q->K)
-                              : bypass ? q->taps : pfb_column_taps(q->taps, q->K);
-        if ((rc = q->upload(&q->d_taps, ct.data(), ct.size()))) return bail(rc);
+    if ((rc = create_tables(q)) || (rc = create_buffers(q)) || (rc = create_streams_and_events(q)) || (rc = restart_async(q, q->stream, true)) ||
+        (hipStreamSynchronize(q->stream) != hipSuccess && (rc = fail(MCRX_EHIP, "stream sync failed")))) {
+        mcrx_hip_destroy(q);
+        return rc;
     }
-    if ((rc = build_tables(q))) return bail(rc);
-    if (q->oversampled) {
-        if (mcrx_hip_pfb2_create(&q->pfb2, q->K, 7, 60.0f) != MCRX_OK) return bail(fail(MCRX_EHIP, mcrx_hip_pfb2_last_error()));
-        std::vector<float> h1 = halfband_branch_taps(7, 60.0f);
-        if ((rc = q->upload(&q->d_h1, h1.data(), h1.size()))) return bail(rc);
-    }
-    if ((rc = q->alloc(&q->d_st, q->nch))) return bail(rc);
-    if ((rc = q->alloc(&q->d_seekst, (size_t)q->nch * 2))) return bail(rc);
-    if ((rc = q->alloc(&q->d_hbits, (size_t)q->nch * MCRX_HDR_SYMS))) return bail(rc);
-    if ((rc = q->alloc(&q->d_R, (size_t)q->nch * M))) return bail(rc);
-    if ((rc = q->alloc(&q->d_soft, (size_t)q->nch * 8 * q->max_enc))) return bail(rc);
-    if ((rc = q->alloc(&q->d_tmpa, (size_t)q->nch * (q->max_enc + 16)))) return bail(rc);
-    if ((rc = q->alloc(&q->d_tmpb, (size_t)q->nch * (q->max_enc + 16)))) return bail(rc);
-    if ((rc = q->alloc(&q->d_syms, (size_t)q->nch * q->max_syms))) return bail(rc);
-    for (int g = 0; g < MCRX_GENS; g++) {
-        if ((rc = q->alloc(&q->d_rec[g], q->max_rec))) return bail(rc);
-        if ((rc = q->alloc(&q->d_arena[g], q->arena_cap))) return bail(rc);
-        if ((rc = q->alloc(&q->d_sarena[g], q->sarena_cap))) return bail(rc);
-        // (one 32-byte block per generation -- records, dropped | pad | payload bytes, symbol bytes -- so that a poll reads it with one
-        //  small copy and clears it with one fill: each of those waits ~0.1 ms for a slot on the full chip)
-        if ((rc = q->alloc(&q->d_nrec[g], 8))) return bail(rc);
-        q->d_arena_used[g] = reinterpret_cast<unsigned long long *>(q->d_nrec[g] + 4);
-        if (hipEventCreateWithFlags(&q->ev_gen[g], hipEventDisableTiming) != hipSuccess) return bail(fail(MCRX_EHIP, "hipEventCreate failed"));
-        if (hipEventCreateWithFlags(&q->ev_clean[g], hipEventDisableTiming) != hipSuccess) return bail(fail(MCRX_EHIP, "hipEventCreate failed"));
-    }
-    {   // mcrx_hip_config::worker_build / acquisition / scout_build
-        const uint32_t wb = q->cfg.worker_build, aq = q->cfg.acquisition, sb = q->cfg.scout_build;
-        if (wb > 5 || aq > 5) return bail(fail(MCRX_EINVAL, "worker_build / acquisition out of range"));
-        if (wb == 1) q->payload_xb = 0;
-        if (wb >= 2) { q->payload_lean = 0; q->payload_fr = wb == 2 ? 1 : wb == 3 ? 2 : wb == 4 ? 4 : 0; }
-        if ((aq >= 1 && aq <= 3) || aq == 5) q->acq_mode = (int)aq;
-        q->spec = aq != 4;                      // (wanted; whether the design and the device allow it: below)
-        if (sb > 2) return bail(fail(MCRX_EINVAL, "scout_build out of range"));
-        if (sb == 1) q->lean_build = 0;
-        if (sb == 2) q->seg_walker = 0;
-    }
-    read_devel_env(q);
-    if (!q->pipelined) q->nslots = 2;
-    if ((rc = q->alloc(&q->d_njobs, MCRX_SLOTS))) return bail(rc);      // one counter per slot: a launch's placement kernel zeroes the next slot's
-    if ((rc = q->alloc(&q->d_stats, 8))) return bail(rc);
-    // (coherent: with hipHostMallocMapped alone the allocation is non-coherent and a free-running host -- one that never
-    //  synchronizes with the device -- does not see the kernels' updates at all)
-    if (hipHostMalloc((void **)&q->h_hint, HINT_WORDS * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
-        for (int i = 0; i < HINT_WORDS; i++) q->h_hint[i] = 0;          // (the words: acq_shared.h, HintWord)
-        if (hipHostGetDevicePointer((void **)&q->d_hint, q->h_hint, 0) != hipSuccess) q->d_hint = nullptr;
-    }
-    if (q->scout) {
-        q->max_jobs = 2 * q->max_rec + 4 * q->nch + 1024;
-        for (unsigned sl = 0; sl < q->nslots; sl++) {
-            if ((rc = q->alloc(&q->d_jobs[sl], q->max_jobs))) return bail(rc);
-            if ((rc = q->alloc(&q->d_gen[sl], (size_t)q->max_jobs + 1))) return bail(rc);
-            if ((rc = q->alloc(&q->d_qam[sl], (size_t)q->max_jobs + 1))) return bail(rc);
-            if ((rc = q->alloc(&q->d_live[sl], (size_t)q->max_jobs + 1))) return bail(rc);
-            if ((rc = q->alloc(&q->d_jR[sl], (size_t)q->max_jobs * M))) return bail(rc);
-            if ((rc = q->alloc(&q->d_jsoft[sl], (size_t)q->max_jobs * 8 * q->max_enc))) return bail(rc);
-            if ((rc = q->alloc(&q->d_jtmp[sl], (size_t)q->max_jobs * 2 * (q->max_enc + 16)))) return bail(rc);
-        }
-        if (q->sc.payload_soft) {
-            // The K = 7 decoder (decode_general_kernel, viterbi_frames.hpp) takes a frame per wave and keeps 512 bytes of decisions per trellis
-            // step of a block in HBM: one region per workgroup, as many workgroups as a launch can have frames (at most 2 per SIMD: it is
-            // arithmetic).  Its launches follow each other on the work stream, so one set serves every slot.  ~200 KB per workgroup at 1200-byte
-            // payloads = 0.4 GB: allocated when the first frame with the code has been seen (cfg.conv_scratch), launch_sync.
-            q->vit_rows = vf::rows_for(4u * q->max_enc + 6u);
-            q->vit_waves = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(q->max_rec, 2048));
-            q->vit_mode = q->cfg.conv_scratch;
-            if (q->vit_mode > 2) return bail(fail(MCRX_EINVAL, "conv_scratch must be 0, 1 or 2"));
-            if ((rc = q->alloc(&q->d_vit_passes, 8))) return bail(rc);
-            if (q->vit_mode == 1 && (rc = q->alloc_raw(&q->d_vit_scratch, (size_t)q->vit_waves * q->vit_rows * 64))) return bail(rc);
-        }
-        // speculative acquisition (lean path only): slots, their equalisers, the anchors
-        const bool lean = (q->sc.log2M >= 6 && q->sc.M == 64 * q->sc.E && q->sc.M_pilot <= 64) ||
-                          (q->sc.M == 48 && q->sc.E == 1 && q->sc.M_pilot <= 64);        // (48 = 3 x 16: the reference applications' default, round 5)
-        q->spec = q->spec && lean && q->d_hint;
-        if (q->spec) {
-            if ((rc = q->alloc(&q->d_spec, (size_t)q->nch * MCRX_SPEC_MAX))) return bail(rc);
-            if ((rc = q->alloc(&q->d_spec_R, (size_t)q->nch * MCRX_SEG_MAX * M))) return bail(rc);
-            if ((rc = q->alloc(&q->d_anchor, q->nch))) return bail(rc);
-        }
-    }
-    if ((rc = q->alloc(&q->d_hist[0], hist_bytes(q)))) return bail(rc);
-    if ((rc = q->alloc(&q->d_hist[1], hist_bytes(q)))) return bail(rc);
-    // host staging for Execute(): whole tiles of MCRX_TILE blocks
-    size_t tile_samples = (size_t)MCRX_TILE * q->K;
-    size_t want = q->cfg.batch_samples ? q->cfg.batch_samples : ((size_t)1 << 20);
-    q->stage_cap = std::max<size_t>(1, (want + tile_samples - 1) / tile_samples) * tile_samples;
-    if (hipHostMalloc((void **)&q->h_stage, q->stage_cap * q->ss, hipHostMallocDefault) != hipSuccess)
-        return bail(fail(MCRX_ENOMEM, "pinned staging allocation failed"));
-    if ((rc = q->alloc(&q->d_in, q->stage_cap * q->ss))) return bail(rc);
-    // (blocking streams: work a caller puts on the legacy default stream -- e.g. a torch copy of a result buffer --
-    //  still orders against them, as it did when everything ran on one stream)
-    if (hipStreamCreate(&q->stream) != hipSuccess) return bail(fail(MCRX_EHIP, "hipStreamCreate failed"));
-    {   // the acquisition stream carries the serial per-channel chains every payload launch waits for: highest priority
-        int least = 0, greatest = 0;
-        const bool prio = q->acq_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least;
-        if ((prio ? hipStreamCreateWithPriority(&q->s_scout, hipStreamDefault, greatest) : hipStreamCreate(&q->s_scout)) != hipSuccess)
-            return bail(fail(MCRX_EHIP, "hipStreamCreate failed"));
-    }
-    if (hipStreamCreate(&q->s_work) != hipSuccess) return bail(fail(MCRX_EHIP, "hipStreamCreate failed"));
-    // (With the others: a stream created in mid-stream shifts the queue mapping.  Only for receivers of few channels: their pushes are
-    //  chains of launch gaps, and three launches less in the work stream's chain are worth 15-18 % (8 channels: 65 -> 77 Gsample/s, with
-    //  the K = 7 code 41 -> 47); a receiver that fills the chip gains nothing from it, and the stream's mere existence cost 1 % of the
-    //  headline and 10 % of the pipeline leg in alternating runs -- scratch/r5/split_ab.sh.)
-    if (q->pipelined && q->nch <= 32 && q->cfg.channel_count == 0 && hipStreamCreate(&q->s_side) != hipSuccess)      // (not a rank's shard behind a pipeline: streams enough there)
-        return bail(fail(MCRX_EHIP, "hipStreamCreate failed"));
-    if (hipStreamCreateWithFlags(&q->s_copy, hipStreamNonBlocking) != hipSuccess) return bail(fail(MCRX_EHIP, "hipStreamCreate failed"));
-    {
-        hipEvent_t *evs[] = { &q->ev_in, &q->ev_consumed, &q->ev_tmp[0], &q->ev_tmp[1], &q->ev_tmp[2], &q->ev_tmp[3], &q->ev_side_last };
-        for (hipEvent_t *e : evs) if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return bail(fail(MCRX_EHIP, "hipEventCreate failed"));
-        for (int sl = 0; sl < MCRX_SLOTS; sl++) {
-            hipEvent_t *ev3[] = { &q->ev_ready[sl], &q->ev_scout[sl], &q->ev_done[sl], &q->ev_side[sl] };
-            for (hipEvent_t *e : ev3) if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return bail(fail(MCRX_EHIP, "hipEventCreate failed"));
-        }
-    }
-    for (int w = 0; w < MCRX_NKERNELS; w++) {
-        q->evring[w].resize(2048, nullptr);
-        for (auto &e : q->evring[w]) if (hipEventCreate(&e) != hipSuccess) return bail(fail(MCRX_EHIP, "hipEventCreate failed"));
-    }
-    if ((rc = restart_async(q, q->stream, true))) return bail(rc);
-    if (hipStreamSynchronize(q->stream) != hipSuccess) return bail(fail(MCRX_EHIP, "stream sync failed"));
     *out = q;
     return MCRX_OK;
 }
@@ -810,40 +736,20 @@ extern "C" int mcrx_hip_destroy(mcrx_hip_t q)
         (void)hipMemcpy(v, q->d_stats, sizeof(v), hipMemcpyDeviceToHost);
         fprintf(stderr, "mcrx stats: walked %u adopted %u last failed crc: key %08x computed %08x\n", v[0], v[1], v[2], v[3]);
     }
+    // Buffers first, while the handle's streams still exist: freed behind the streams' destruction they took twenty times as long
+    // (destroying an 8-channel handle: 330 ms instead of 16, a 512-channel one 470 ms; same box, alternating runs).
     for (void *p : q->owned) (void)hipFree(p);
     il_tables_release(q->sc.il_map);
-    for (int i = 0; i < MCRX_SLOTS; i++) if (q->d_chan[i]) (void)hipFree(q->d_chan[i]);
-    for (int i = 0; i < 2; i++) { if (q->d_pfin[i]) (void)hipFree(q->d_pfin[i]); if (q->d_pfout[i]) (void)hipFree(q->d_pfout[i]); }
+    // ... the buffers that are regrown, so freed when replaced (ensure_chan, run_oversampled, execute_direct) ...
+    for (float2 *p : q->d_chan) if (p) (void)hipFree(p);
+    for (int i = 0; i < 2; i++) for (void *p : { (void *)q->d_pfin[i], (void *)q->d_pfout[i], (void *)q->d_direct[i] }) if (p) (void)hipFree(p);
     if (q->pfb2) (void)mcrx_hip_pfb2_destroy(q->pfb2);
     if (q->h_stage) (void)hipHostFree(q->h_stage);
-    q->arena_host.release(); q->sarena_host.release();
-    {
-        hipEvent_t evs[] = { q->ev_in, q->ev_consumed, q->ev_tmp[0], q->ev_tmp[1], q->ev_tmp[2], q->ev_tmp[3], q->ev_side_last, q->ev_base };
-        for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-        for (int g = 0; g < MCRX_GENS; g++) { if (q->ev_gen[g]) (void)hipEventDestroy(q->ev_gen[g]); if (q->ev_clean[g]) (void)hipEventDestroy(q->ev_clean[g]); }
-        for (int sl = 0; sl < MCRX_SLOTS; sl++) {
-            if (q->ev_ready[sl]) (void)hipEventDestroy(q->ev_ready[sl]);
-            if (q->ev_scout[sl]) (void)hipEventDestroy(q->ev_scout[sl]);
-            if (q->ev_done[sl]) (void)hipEventDestroy(q->ev_done[sl]);
-            if (q->ev_side[sl]) (void)hipEventDestroy(q->ev_side[sl]);
-        }
-        hipStream_t sts[] = { q->s_scout, q->s_work, q->s_copy, q->s_side };
-        for (hipStream_t t : sts) if (t) (void)hipStreamDestroy(t);
-    }
-    for (int i = 0; i < 2; i++) {
-        if (q->d_direct[i]) (void)hipFree(q->d_direct[i]);
-        if (q->ev_dcopy[i]) (void)hipEventDestroy(q->ev_dcopy[i]);
-        if (q->ev_ddone[i]) (void)hipEventDestroy(q->ev_ddone[i]);
-    }
-    if (q->mon.allocated) {
-        for (void *p : { (void *)q->mon.d_carry[0], (void *)q->mon.d_carry[1], (void *)q->mon.d_sums, (void *)q->mon.d_part }) if (p) (void)hipFree(p);
-        for (hipEvent_t e : { q->mon.ev_in, q->mon.ev_out, q->mon.ev_last }) if (e) (void)hipEventDestroy(e);
-        if (q->mon.s_mon) (void)hipStreamDestroy(q->mon.s_mon);
-    }
-    if (q->copy_stream) (void)hipStreamDestroy(q->copy_stream);
     if (q->h_hint) (void)hipHostFree(q->h_hint);
-    for (int w = 0; w < MCRX_NKERNELS; w++) for (auto e : q->evring[w]) if (e) (void)hipEventDestroy(e);
-    if (q->stream) (void)hipStreamDestroy(q->stream);
+    q->arena_host.release(); q->sarena_host.release();
+    // ... then events before streams, and the streams newest first: q->stream, the first one made, goes last
+    for (hipEvent_t e : q->owned_events) (void)hipEventDestroy(e);
+    for (size_t i = q->owned_streams.size(); i-- > 0;) (void)hipStreamDestroy(q->owned_streams[i]);
     delete q;
     return MCRX_OK;
 }
@@ -1319,10 +1225,10 @@ static int execute_direct(mcrx_hip_t q, const char *&src, size_t &nsamples, bool
     size_t chunk = (size_t)std::min<uint64_t>(blocks_cap * q->K, (uint64_t)16 << 20) / tile_samples * tile_samples;
     if (chunk < 64 * tile_samples) return MCRX_OK;
     if (!q->copy_stream) {
-        HIPCHK(hipStreamCreateWithFlags(&q->copy_stream, hipStreamNonBlocking));
+        RC(q->new_stream(&q->copy_stream, hipStreamNonBlocking));
         for (int i = 0; i < 2; i++) {
-            HIPCHK(hipEventCreateWithFlags(&q->ev_dcopy[i], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&q->ev_ddone[i], hipEventDisableTiming));
+            RC(q->new_event(&q->ev_dcopy[i], hipEventDisableTiming));
+            RC(q->new_event(&q->ev_ddone[i], hipEventDisableTiming));
         }
     }
     while (nsamples >= 64 * tile_samples) {
@@ -1727,13 +1633,13 @@ extern "C" int mcrx_hip_monitor_enable(mcrx_hip_t q, const mcrx_hip_monitor_conf
         // sized for every nfft: carries of 256 samples per channel, sums of 256 bins; partial sums for up to 8192 / nch waves per channel
         m.max_split = std::max<uint32_t>(1, std::min<uint32_t>(64, (8192 + q->nch - 1) / q->nch));
         m.sums_bytes = ((size_t)q->nch * 256 + q->nch) * sizeof(double) + (size_t)q->nch * sizeof(float);
-        HIPCHK(hipMalloc((void **)&m.d_carry[0], (size_t)q->nch * 256 * sizeof(float2)));
-        m.allocated = true;                 // (from here on mcrx_hip_destroy frees whatever exists)
-        HIPCHK(hipMalloc((void **)&m.d_carry[1], (size_t)q->nch * 256 * sizeof(float2)));
-        HIPCHK(hipMalloc((void **)&m.d_sums, m.sums_bytes));
-        HIPCHK(hipMalloc((void **)&m.d_part, m.sums_bytes * m.max_split));
-        HIPCHK(hipStreamCreateWithFlags(&m.s_mon, hipStreamNonBlocking));
-        for (hipEvent_t *e : { &m.ev_in, &m.ev_out, &m.ev_last }) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        // (not cleared: the carries are written before they are read, the sums are cleared in stream order -- monitor_restart)
+        for (float2 **c : { &m.d_carry[0], &m.d_carry[1] }) RC(q->alloc_raw(c, (size_t)q->nch * 256));
+        RC(q->alloc_raw(&m.d_sums, (m.sums_bytes + 7) / 8));
+        RC(q->alloc_raw(&m.d_part, (m.sums_bytes * m.max_split + 7) / 8));
+        RC(q->new_stream(&m.s_mon, hipStreamNonBlocking));
+        for (hipEvent_t *e : { &m.ev_in, &m.ev_out, &m.ev_last }) RC(q->new_event(e, hipEventDisableTiming));
+        m.allocated = true;                 // (only now: a call that failed half way is made again from the start, and what it left is the handle's)
     } else if (m.ev_last) HIPCHK(hipEventSynchronize(m.ev_last));      // a monitor that was on: its launches are over before the sums go
     m.nfft = nfft; m.window = window;
     m.wss = 0.0;

@@ -29,7 +29,7 @@
 // (included inside namespace mcrx, after lane_id(): ofdmsync.hip; needs <utility>)
 namespace vf {
 
-// (W, block_steps(T), rows_for(T): kernels.h -- the host sizes the scratch with them)
+// (W, block_steps(T), rows_for(T): acq_shared.h -- the host sizes the scratch with them)
 static_assert(W % 24u == 0u && W >= 48u, "warm-up: whole register-layout periods, whole bytes, and the traceback's prefetch reaches back 48 rows");
 
 __device__ __forceinline__ constexpr unsigned par(unsigned v) { unsigned p = 0; while (v) { p ^= v & 1u; v >>= 1; } return p; }
