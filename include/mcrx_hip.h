@@ -583,6 +583,52 @@ int      mcrx_hip_chanfade_selftest(const mcrx_hip_chanemu_fading *f, unsigned r
  * (entries of rays >= num_taps are not written) into the caller's device buffer, asynchronously on `stream`.  MCRX_EINVAL with fading off. */
 int      mcrx_hip_chanfade_gains(mcrx_hip_chanemu_t q, uint64_t first_row, uint32_t rows, void *d_table, void *stream);
 
+/* ---- per-user channel emulator on the transmitter's channel tiles ----
+ * Sits between mctx_hip_traffic_tiles and mctx_hip_synthesize_tiles: every channel of the bank gets its own multipath, its own
+ * oscillator, its own timing and its own level, at the channel rate, before the synthesis bank -- which is what puts a strong user next
+ * to a weak one through the bank's skirts.  x_c[b] is the channel-rate sample of local channel c at absolute block index b (a signed
+ * 64-bit value; one block = one channel-rate sample per channel).  Channel c has T_c rays (d_ci, a_ci), a gain_c, a 32-bit phase step
+ * cfo_step_c per channel-rate sample and a start phase phase0_c:
+ *   s_c[b] = sum_{i<T_c} a_ci x_c[b - d_ci]                  table order, two fused multiply-adds per ray and component
+ *   r_c[b] = s_c[b] exp(+j 2 pi th / 2^32)                   th = phase0_c + cfo_step_c (uint32_t)(uint64_t)b  mod 2^32
+ *   y_c[b] = gain_c r_c[b]                                   one fp32 multiply per component
+ * Stateless: a pure function of the absolute block index and of the input it is handed; the handle keeps no history, no position and no
+ * device state beyond the parameter table.  The samples behind a call are supplied by the caller, the way synthesize_tiles takes its
+ * lead: d_in holds granules [tile][channel][8] (cf32, traffic_tiles' layout for num_channels channels) of blocks
+ * [first_block - lead_blocks, first_block + nblocks), d_out receives blocks [first_block, first_block + nblocks) in the same layout;
+ * lead_blocks, nblocks and first_block are multiples of 8 and lead_blocks >= mcrx_hip_userchan_lead_blocks().  What the input holds in
+ * front of block 0 is the caller's business (traffic_tiles writes zeros there).  A stream cut into calls anywhere, with any sufficient
+ * lead, gives the one-call output bit for bit.
+ * Rotation: when every channel of the handle has cfo_step == 0 && phase0 == 0 the rotation is not computed at all (s_c goes to the gain
+ * as it is); otherwise EVERY channel of the handle is rotated, those with a zero step and phase by the oscillator value of phase 0.
+ * A user's timing offset is an integer delay added to all of their rays; it has no field of its own.
+ * At most 2^28 granules (tiles * channels) a call. */
+#define MCRX_USERCHAN_MAX_RAYS     4
+#define MCRX_USERCHAN_MAX_DELAY    255      /* channel-rate samples */
+#define MCRX_USERCHAN_MAX_CHANNELS 1024
+typedef struct mcrx_hip_userchan_s *mcrx_hip_userchan_t;
+typedef struct {
+    uint32_t num_rays;                                      /* 1 .. MCRX_USERCHAN_MAX_RAYS */
+    uint32_t delay[MCRX_USERCHAN_MAX_RAYS];                 /* <= MCRX_USERCHAN_MAX_DELAY channel-rate samples */
+    float    tap_re[MCRX_USERCHAN_MAX_RAYS], tap_im[MCRX_USERCHAN_MAX_RAYS];
+    float    gain;
+    uint32_t cfo_step, phase0;      /* 2^32 * cycles per channel-rate sample; start phase */
+} mcrx_hip_userchan_channel;
+/* ch[num_channels], struct_size = sizeof(mcrx_hip_userchan_channel).  MCRX_EINVAL (before a device is looked for): null pointers, a
+ * wrong struct_size, num_channels outside 1 .. 1024, num_rays outside 1 .. 4, a delay above the maximum, a tap or gain that is not
+ * finite (entries beyond a channel's num_rays are not looked at).  The handle belongs to the HIP device current at creation. */
+int         mcrx_hip_userchan_create(mcrx_hip_userchan_t *out, unsigned num_channels, const mcrx_hip_userchan_channel *ch,
+                                     size_t struct_size);
+int         mcrx_hip_userchan_destroy(mcrx_hip_userchan_t q);
+unsigned    mcrx_hip_userchan_num_channels(mcrx_hip_userchan_t q);                   /* 0 for a null handle */
+unsigned    mcrx_hip_userchan_lead_blocks(mcrx_hip_userchan_t q);                    /* largest delay rounded up to 8; 0 for a null handle */
+/* Asynchronous on `stream` (a hipStream_t, NULL = the default stream).  MCRX_EINVAL: a null handle or buffer, a buffer that is not
+ * 16-byte aligned, nblocks, lead_blocks or first_block not a multiple of 8, lead_blocks below mcrx_hip_userchan_lead_blocks(), input
+ * and output ranges that overlap, more than 2^28 granules. */
+int         mcrx_hip_userchan_apply_tiles(mcrx_hip_userchan_t q, const void *d_in, long long first_block, size_t nblocks,
+                                          size_t lead_blocks, void *d_out, void *stream);
+const char *mcrx_hip_userchan_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,12 @@ _EXPORTS = {
     "mcrx_hip_chanfade_on": (C.c_int, [C.c_void_p]),
     "mcrx_hip_chanfade_gains": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mcrx_hip_chanfade_selftest": (C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "mcrx_hip_userchan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p, C.c_size_t]),
+    "mcrx_hip_userchan_destroy": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_userchan_num_channels": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_userchan_lead_blocks": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_userchan_apply_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_userchan_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -876,6 +882,160 @@ class chanemu(object):
     def close(self):
         if self._h:
             lib().mcrx_hip_chanemu_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+USERCHAN_MAX_RAYS, USERCHAN_MAX_DELAY, USERCHAN_MAX_CHANNELS = 4, 255, 1024      # MCRX_USERCHAN_MAX_RAYS, _MAX_DELAY, _MAX_CHANNELS
+USERCHAN_SYNTH_LEAD = 32      # blocks of filter history userchan.generate gives the synthesis bank: >= 25, a multiple of 8
+
+
+class UserchanChannel(C.Structure):
+    _fields_ = [("num_rays", C.c_uint32), ("delay", C.c_uint32 * USERCHAN_MAX_RAYS),
+                ("tap_re", C.c_float * USERCHAN_MAX_RAYS), ("tap_im", C.c_float * USERCHAN_MAX_RAYS),
+                ("gain", C.c_float), ("cfo_step", C.c_uint32), ("phase0", C.c_uint32)]
+
+
+_USERCHAN_KEYS = ("taps", "gain_db", "cfo_step", "phase0", "delay")
+
+
+def userchan_cfo_step(spacings, M):
+    """The userchan cfo_step (2^32 * cycles per channel-rate sample, mod 2^32) of a user's oscillator that is off by `spacings`
+    subcarrier spacings: a spacing is 1 / M cycles per channel-rate sample."""
+    return int(round(float(spacings) / M * 4294967296.0)) % (1 << 32)
+
+
+def userchan_channel(taps=((0, 1.0),), gain_db=0.0, cfo_step=0, phase0=0, delay=0):
+    """The mcrx_hip_userchan_channel structure of one user: rays (delay, a) in channel-rate samples, summed in the order given; `delay`
+    (the user's timing offset) is added to every ray's; gain = float32(10 ** (gain_db / 20)).  ValueError for what the library refuses."""
+    taps = list(taps)
+    if not 1 <= len(taps) <= USERCHAN_MAX_RAYS:
+        raise ValueError("1 .. %d rays a channel" % USERCHAN_MAX_RAYS)
+    if int(delay) != delay or int(delay) < 0:
+        raise ValueError("a timing offset is a whole number of channel-rate samples, not negative")
+    u = UserchanChannel()
+    u.num_rays = len(taps)
+    for i, (d, a) in enumerate(taps):
+        if int(d) != d or not 0 <= int(d) + int(delay) <= USERCHAN_MAX_DELAY:
+            raise ValueError("a delay (with the timing offset) is a whole number of channel-rate samples, 0 .. %d" % USERCHAN_MAX_DELAY)
+        a = np.complex64(complex(a))
+        if not (np.isfinite(a.real) and np.isfinite(a.imag)):
+            raise ValueError("taps must be finite")
+        u.delay[i], u.tap_re[i], u.tap_im[i] = int(d) + int(delay), float(a.real), float(a.imag)
+    try:
+        with np.errstate(over="ignore"):
+            gain = np.float32(10.0 ** (float(gain_db) / 20.0))
+    except OverflowError:
+        gain = np.float32("inf")
+    if not np.isfinite(gain):
+        raise ValueError("gain_db must be finite and its gain must fit fp32")
+    u.gain, u.cfo_step, u.phase0 = float(gain), int(cfo_step) % (1 << 32), int(phase0) % (1 << 32)
+    return u
+
+
+class userchan(object):
+    """Per-user channel emulator on the transmitter's channel tiles, between TxTraffic.tiles and multichanneltx.synthesize
+    (mcrx_hip_userchan_*): every channel has its own multipath, oscillator, timing and level, at the channel rate.
+
+        userchan(channels=[dict(taps=[(delay, a), ...], gain_db=0.0, cfo_step=0, phase0=0, delay=0), ...])
+
+    One entry per local channel (1 .. 1024): 1 .. 4 rays with delays in channel-rate samples (<= 255 with the timing offset `delay`
+    added), cfo_step / phase0 32-bit phases per channel-rate sample (userchan_cfo_step).  The operator keeps no state: apply() is a
+    function of the absolute block index and of the tiles it is handed, which include `lead_blocks` blocks in front of the output's
+    first.  When no channel has a step or a start phase the rotation is not computed; otherwise every channel is rotated."""
+
+    def __init__(self, channels):
+        self._h = C.c_void_p()
+        chans = []
+        for ch in channels:
+            if isinstance(ch, UserchanChannel):
+                chans.append(ch)
+                continue
+            if not isinstance(ch, dict) or any(k not in _USERCHAN_KEYS for k in ch):
+                raise ValueError("a channel is a dict with keys of %s" % (_USERCHAN_KEYS,))
+            chans.append(userchan_channel(**ch))
+        if not 1 <= len(chans) <= USERCHAN_MAX_CHANNELS:
+            raise ValueError("1 .. %d channels a handle" % USERCHAN_MAX_CHANNELS)
+        self._table = (UserchanChannel * len(chans))(*chans)
+        rc = lib().mcrx_hip_userchan_create(C.byref(self._h), len(chans), C.addressof(self._table), C.sizeof(UserchanChannel))
+        if rc != MCRX_OK:
+            self._h = C.c_void_p()
+            self._chk(rc, "mcrx_hip_userchan_create")
+
+    @staticmethod
+    def _chk(rc, name):
+        _raise_rc(rc, name, lib().mcrx_hip_userchan_last_error)
+
+    @property
+    def num_channels(self):
+        return int(lib().mcrx_hip_userchan_num_channels(self._h))
+
+    @property
+    def lead_blocks(self):
+        """blocks apply() needs in front of its output's first: the largest delay rounded up to 8"""
+        return int(lib().mcrx_hip_userchan_lead_blocks(self._h))
+
+    def shard(self, first, count):
+        """A new handle for local channels [first, first + count): what a channel shard of the transmitter (TxTraffic) applies."""
+        if int(first) != first or int(count) != count or not (0 <= first and 1 <= count and first + count <= len(self._table)):
+            raise ValueError("a shard is channels [first, first + count) of this handle's %d" % len(self._table))
+        return userchan([self._table[c] for c in range(int(first), int(first) + int(count))])
+
+    def apply(self, tiles, first_block, nblocks, lead_blocks=None, out=None, stream=None):
+        """tiles: granules [tile][channel][8] of blocks [first_block - lead_blocks, first_block + nblocks), a contiguous torch complex64
+        CUDA tensor (TxTraffic.tiles' layout for this handle's channels); lead_blocks defaults to the handle's.  Returns the granules
+        of blocks [first_block, first_block + nblocks) -- in `out` when given, which must not overlap `tiles`.  Asynchronous on
+        `stream` (default: torch's current stream of the tiles' device)."""
+        import torch
+        C_ = len(self._table)
+        lead = self.lead_blocks if lead_blocks is None else int(lead_blocks)
+        nblocks = int(nblocks)
+        if nblocks < 0 or lead < 0:
+            raise ValueError("block counts are not negative")
+        for t, need, what in ((tiles, (lead + nblocks) * C_, "tiles"), (out, nblocks * C_, "out")):
+            if t is None:
+                continue
+            if t.dtype != torch.complex64:
+                raise TypeError("%s must be complex64, not %s" % (what, t.dtype))
+            if not t.is_cuda or not t.is_contiguous() or int(t.numel()) < need:
+                raise ValueError("%s must be a contiguous CUDA tensor of at least %d samples" % (what, need))
+        if out is None:
+            out = torch.empty(nblocks * C_, dtype=torch.complex64, device=tiles.device)
+        if nblocks:              # (an empty tensor has no address to pass)
+            if stream is None:
+                stream = torch.cuda.current_stream(tiles.device)
+            self._chk(lib().mcrx_hip_userchan_apply_tiles(self._h, _dptr(tiles), int(first_block), nblocks, lead, _dptr(out),
+                                                          _stream_ptr(stream)), "mcrx_hip_userchan_apply_tiles")
+        return out.view(-1)[:nblocks * C_]
+
+    def generate(self, tx, frames_per_channel, payload_len, mod=LIQUID_MODEM_QPSK, fec0=LIQUID_FEC_NONE, fec1=LIQUID_FEC_HAMMING128,
+                 gain=None, seed=0):
+        """multichanneltx.generate with every user behind their own channel, in one call: tx.traffic(0, N, ...) -> tiles of blocks
+        [-(lead_synth + lead_blocks), blocks) -> apply -> tx.synthesize.  -> (iq, sent), `gain` and `sent` as multichanneltx.generate
+        has them; iq holds the blocks generate() returns for the same arguments."""
+        import torch
+        if self.num_channels != tx.N:
+            raise ValueError("this handle has %d channels, the transmitter %d" % (self.num_channels, tx.N))
+        tr = tx.traffic(0, tx.N, frames_per_channel, payload_len, mod, fec0, fec1, seed)
+        try:
+            nb, ls, lu = tr.blocks, USERCHAN_SYNTH_LEAD, self.lead_blocks
+            tiles = torch.empty((ls + lu + nb) * tx.N, dtype=torch.complex64, device="cuda")
+            tr.tiles(-(ls + lu), ls + lu + nb, tiles)
+            mid = self.apply(tiles, -ls, ls + nb, lu)
+            iq = tx.synthesize(mid, 1, 0, nb, ls, 0, gain)
+            sent = tr.sent
+        finally:
+            tr.close()
+        return iq, sent
+
+    def close(self):
+        if self._h:
+            lib().mcrx_hip_userchan_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
