@@ -27,11 +27,7 @@
 // pilots); the tests hold it to the oracle like the default (tests/test_gpu_parity.py, test_gpu_alloc.py).
 
 #include "lean_prims.hpp"
-#ifndef ACQ_LEAN_WAVES
-#define ACQ_LEAN_WAVES 3        /* waves per SIMD the kernel is built for (mcrx_hip.hip sizes the segments by it: acq_lean_waves()).  Three = 168
-                                   registers: the kernel's real pressure is ~165, and at four (128) the 40 spilled registers sit on every event's
-                                   chain -- 136 against 110 us per launch, scratch/r5/acq_ab.sh */
-#endif
+// (ACQ_LEAN_WAVES, the waves per SIMD the kernel is built for: sync_plan.hpp)
 #ifndef ACQ_WIN
 #define ACQ_WIN 768             /* samples of the channel staged in LDS at a time: 6 KB per wave (a 64-subcarrier frame's acquisition spans ~720) */
 #endif

@@ -6,6 +6,7 @@
 
 #define MCRX_SPEC_MAX 256        // slots per channel the scouts hold in registers at a time (kernels.h: SpecSlot)
 #define MCRX_SEG_MAX 128         // most segment waves per channel
+#define MCRX_HDR_SYMS 288        // BPSK header symbols
 #ifdef __HIPCC__
 #define MCRX_HD __host__ __device__
 #else

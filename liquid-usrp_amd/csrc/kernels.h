@@ -2,13 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "acq_shared.h"        // MCRX_SPEC_MAX, MCRX_SEG_MAX, the hint block's words (HintWord): shared with the host-only planner
+#include "acq_shared.h"        // MCRX_SPEC_MAX, MCRX_SEG_MAX, MCRX_HDR_SYMS, the hint block's words (HintWord): shared with the host-only planners
+#include "sync_plan.hpp"       // SY_LDS_BYTES, VIT_B, DK_T, ...: the launch geometry; SyncStage; the design predicates (host only)
 
 namespace mcrx {
 
 #define MCRX_TILE_S 16           // channel-rate samples per (channel, tile) granule = 128 bytes = one cache line (== MCRX_TILE, include/mcrx_hip.h)
 #define MCRX_TILE_SH 4           // log2 of it
-#define MCRX_HDR_SYMS 288        // BPSK header symbols
 #define MCRX_HDR_ENC 36
 #define MCRX_HDR_DEC 14
 
@@ -227,7 +227,7 @@ struct SyncArgs {
     // but an empty launch still waits for a wave slot on a chip full of channelizer and worker waves -- 0.15 + 0.08 ms of the work
     // stream's 0.98 ms per push (profiles/r5_t3_kernel_stats.csv).  While their lists have been empty the host puts them on a stream
     // of their own, with a decoder launch for their frames only, so that the next push's workers do not queue behind them:
-    int split_rest;                      // 1: stage 1 launches the main workers only, stage 4 the launch behind them
+    int split_rest;                      // 1: SYNC_WORKERS launches the main workers only, SYNC_BEHIND the launch behind them
     int dec_phase;                       // decode_kernel: 0 = every live frame, 1 = the main workers' frames only, 2 = the others
     int seg_walker;                      // 1 (default): the segment waves are the Walker's kernel (sync_spec_kernel); 0 (scout_build = 2): acq_lean.hpp's where the design allows
     int seg_phase;                       // 1: first frame from the entry state only (grid = channels); 2: the rest; 0: one launch, no cadence;
@@ -267,12 +267,13 @@ hipError_t sync_launch_tail(const SyncArgs &a, hipStream_t st);      // lean con
 hipError_t ilmap_build_launch(const uint32_t *d_lens, const uint32_t *d_offs, uint32_t nlen, uint8_t *d_lo, uint8_t *d_hi, uint16_t *d_map, hipStream_t st);
 hipError_t sync_launch_walk(const SyncArgs &a, hipStream_t st);      // the lean scout built without a register budget: for streams it has to walk by itself
 hipError_t sync_launch_lean(const SyncArgs &a, hipStream_t st);      // lean scout: acquisition + header + hand-off, one wave per channel
-int acq_lean_waves(const SyncConsts &c);
+int acq_lean_waves(const SyncConsts &c);                             // sync_plan.hpp's sync_lean_waves() of this design
 hipError_t sync_launch_spec(const SyncArgs &a, hipStream_t st);      // segment-parallel acquisition: one wave per (channel, segment)
-// stage 0: record placement (one workgroup), 1: payload workers (one wave per handed-off frame),
-// 2: packet decode (one workgroup per frame; only after the lean workers -- the general ones decode in place)
-hipError_t sync_launch_payload(const SyncArgs &a, int stage, hipStream_t st);
-bool sync_payload_splits(const SyncArgs &a);                         // the payload stage has a launch behind the main workers (SyncArgs::split_rest)
+// SYNC_PLACE: record placement (one workgroup), SYNC_WORKERS: payload workers (one wave per handed-off frame), SYNC_BEHIND: the launch
+// behind the lean workers, SYNC_DECODE / SYNC_DECODE_GENERAL: packet decode (one workgroup per frame; only after the fast workers -- the
+// general ones decode in place).  What each stage launches: sync_plan.hpp, sync_payload_plan()
+hipError_t sync_launch_payload(const SyncArgs &a, SyncStage stage, hipStream_t st);
+bool sync_payload_splits(const SyncArgs &a);                         // the plan's answer: the payload stage has a launch behind the main workers (SyncArgs::split_rest)
 // synchronizers back to SEEK at sample `cur`; optionally also zero two history buffers of hist_n cf32 each (hist_n even)
 // and the result counters -- a whole restart in one launch
 hipError_t sync_reset_launch(ChanState *st, uint32_t nch, int64_t cur, float2 *hist0, float2 *hist1, size_t hist_n,

@@ -906,7 +906,7 @@ static int launch_workers(mcrx_hip_t q, SyncArgs &a, hipStream_t sa, hipStream_t
 {
     const unsigned slot = (unsigned)(q->seq % q->nslots);
     RC(q->ev_begin(2, sa));               // record placement
-    HIPCHK(sync_launch_payload(a, 0, sa));
+    HIPCHK(sync_launch_payload(a, SYNC_PLACE, sa));
     RC(q->ev_end(2, sa));
     if (sw != sa) {
         HIPCHK(hipEventRecord(q->ev_scout[slot], sa));
@@ -935,21 +935,21 @@ static int launch_workers(mcrx_hip_t q, SyncArgs &a, hipStream_t sa, hipStream_t
     else if (gen_side) sd = q->s_side;
     else if (q->side_last) HIPCHK(hipStreamWaitEvent(sw, q->ev_side_last, 0));       // (back in one line: behind what the other stream still holds)
     RC(q->ev_begin(3, sw));
-    HIPCHK(sync_launch_payload(a, 1, sw));
+    HIPCHK(sync_launch_payload(a, SYNC_WORKERS, sw));
     RC(q->ev_end(3, sw));
     RC(q->ev_begin(4, sw));
-    HIPCHK(sync_launch_payload(a, 2, sw));
+    HIPCHK(sync_launch_payload(a, SYNC_DECODE, sw));
     if (split) {
         HIPCHK(hipEventRecord(q->ev_side[slot], sw));
         HIPCHK(hipStreamWaitEvent(sd, q->ev_side[slot], 0));
-        HIPCHK(sync_launch_payload(a, 4, sd));
+        HIPCHK(sync_launch_payload(a, SYNC_BEHIND, sd));
         a.dec_phase = 2;
-        HIPCHK(sync_launch_payload(a, 2, sd));
+        HIPCHK(sync_launch_payload(a, SYNC_DECODE, sd));
     } else if (gen_side) {
         HIPCHK(hipEventRecord(q->ev_side[slot], sw));
         HIPCHK(hipStreamWaitEvent(sd, q->ev_side[slot], 0));
     }
-    HIPCHK(sync_launch_payload(a, 3, sd));
+    HIPCHK(sync_launch_payload(a, SYNC_DECODE_GENERAL, sd));
     RC(q->ev_end(4, sd));
     if (split || gen_side) HIPCHK(hipEventRecord(q->ev_side_last, sd));
     q->side_last = split || gen_side;

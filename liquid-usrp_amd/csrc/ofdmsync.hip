@@ -279,7 +279,7 @@ __device__ unsigned golay_dec_sym(unsigned r)
 // differences between states never exceed 6 x 510), and the traceback walks the blocks from the last to the first,
 // re-running each block's forward pass from its checkpoint into an LDS scratch of VIT_B decision words and then tracing
 // back through it: the same survivors as one pass with all decisions kept, at twice the add-compare-select work.
-#define VIT_B 960u             /* steps per block: a multiple of 64 (traceback chunks own whole bytes) and of 6 (the lane layout's period) */
+// (VIT_B steps per block: sync_plan.hpp)
 struct VitSym {                 // the two soft symbols of a step: from soft bytes, or from packed hard bits (0 / 255)
     const uint8_t *p; bool hard;
     // symbols of step t0 + lane as sa | sb << 8 (steps >= T: anything); one load per 64 steps instead of two per step
@@ -679,7 +679,6 @@ __device__ __forceinline__ unsigned demod_soft(const uint8_t *nbt, unsigned mod,
 
 // ------------------------------------------------------------------ the walker
 // Wave-private LDS scratch, referenced by name so every access is a ds_* instruction.
-#define SY_MAXM 1024
 extern __shared__ __attribute__((aligned(16))) float2 sy_lds[];
 #define sy_w  (sy_lds + lo)                                                     /* this wave's scratch (Walker::lo: 0 in one-wave workgroups) */
 #define ldsc  sy_w                                                            /* complex scratch [M]   */
@@ -691,7 +690,7 @@ extern __shared__ __attribute__((aligned(16))) float2 sy_lds[];
 #define ldshd (reinterpret_cast<uint16_t *>(ldsps + 256 + 3 * MCRX_HDR_SYMS))   /* Golay-decoded 12-bit words [12] */
 #define ldsad (reinterpret_cast<uint32_t *>(ldsps + 256 + 3 * MCRX_HDR_SYMS + 32)) /* job list entries of the adopted frames [MCRX_SPEC_MAX] */
 #define ldsqn (ldsps + 256 + 3 * MCRX_HDR_SYMS + 32 + 4 * MCRX_SPEC_MAX)        /* QAM neighbour table of the frame's modem [256] */
-#define SY_LDS_BYTES(M) ((((size_t)(M) * 8 + (size_t)(M) * 12 + 256 + 3 * MCRX_HDR_SYMS + 32 + 4 * MCRX_SPEC_MAX + 256) + 15) & ~(size_t)15)
+// (their sum: SY_LDS_BYTES(M), sync_plan.hpp)
 
 // One wavefront per workgroup: LDS traffic of a wave is processed in order, so a compiler-level
 // fence is all the hand-off between lanes needs (no s_barrier, and no vmcnt(0) drain of the
@@ -2607,8 +2606,7 @@ __global__ __launch_bounds__(WV, SY_ACQ_WAVES) void sync_lean_kernel(SyncArgs a)
 // four (the walkers on 128 CUs, the other 128 free for the channelizer, whose workgroups otherwise cannot start before the
 // one-per-SIMD walkers spread over every CU have finished): the channelizer does overlap then (1.65 -> 0.99 ms), but the
 // walkers, now sharing their CUs with all the workers the channelizer displaced, take 2.03 ms instead of 1.65 -- 91.8 against
-// 110 Gsample/s on ragged traffic.  One per workgroup it stays.
-#define SY_WALK_WPB 1
+// 110 Gsample/s on ragged traffic.  One per workgroup it stays (sync_plan.hpp).
 template <int E>
 __global__ __launch_bounds__(WV * SY_WALK_WPB) void sync_walk_kernel(SyncArgs a)
 {
@@ -2867,7 +2865,7 @@ __global__ __launch_bounds__(WV) void payload_multi_kernel(SyncArgs a)
 // (coalesced), the four passes run in LDS across 256 threads, and the Hamming(12,8) soft decoder
 // reads LDS.  A cell's rank in liquid's column walk is a closed form (columns are valid from row 0
 // down to a per-column count), so the passes need no ballots or sequential ranking.
-#define DK_T 256
+// (DK_T threads: sync_plan.hpp)
 #ifndef DK_FUSED
 #define DK_FUSED 1
 #endif
@@ -3353,263 +3351,165 @@ hipError_t sync_reset_launch(ChanState *st, uint32_t nch, int64_t cur, float2 *h
 
 #endif  // SY_PART <= 0
 
-// ---- launchers.  The file is compiled in three parts (-DSY_PART=0/1/2: symbol widths E = 1,2 / 4,8 / 16) so that
-// the template instantiations build in parallel; every part defines the per-width launchers of its widths.
-enum { SYK_SCOUT = 0, SYK_SPEC = 1, SYK_PAYLOAD_FAST = 2, SYK_PAYLOAD_GENERAL = 3, SYK_LEAN = 4, SYK_TAIL = 5, SYK_WALK = 6 };
-// acquisition kernels of the narrow symbols (E = 1, 2): part 3, built with -mllvm -vgpr-regalloc=basic (see SY_ACQ_BUDGET)
-hipError_t sy_launch_acq_e1(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st);
-hipError_t sy_launch_acq_e2(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st);
+// ---- launchers.  The file is compiled in five parts (-DSY_PART=0 .. 4: symbol widths E = 1,2 / 4,8 / 16 / the acquisition kernels of
+// E = 1,2 / the lean segment waves) so that the template instantiations build in parallel; every part defines the launchers of its
+// kernels.  Which kernel a launch runs, its grid, block and LDS and what it rewrites in SyncArgs is decided in sync_plan.hpp; the
+// functions down to sy_issue only issue what a plan names, and none of them reads the launch's error: the entry points behind them
+// do, once behind all the launches of a call.
+hipError_t sy_launch_acq_e1(const SyncLaunch &l, const SyncArgs &a, hipStream_t st);       // part 3 (see SY_ACQ_BUDGET)
+hipError_t sy_launch_acq_e2(const SyncLaunch &l, const SyncArgs &a, hipStream_t st);
 template <int EE>
-static hipError_t sy_launch_acq_width(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st)
+static hipError_t sy_launch_acq_width(const SyncLaunch &l, const SyncArgs &a, hipStream_t st)
 {
-    if (what == SYK_SPEC) hipLaunchKernelGGL((sync_spec_kernel<EE>), dim3(grid), dim3(WV), lds, st, a);
-    else if (what == SYK_TAIL) hipLaunchKernelGGL((sync_tail_kernel<EE>), dim3(grid), dim3(WV), lds, st, a);
-    else hipLaunchKernelGGL((sync_lean_kernel<EE>), dim3(grid), dim3(WV), lds, st, a);
-    return hipGetLastError();
+    if (sync_kernel_in(l.k, SK_SPEC_E1)) hipLaunchKernelGGL((sync_spec_kernel<EE>), dim3(l.grid), dim3(l.block), l.lds, st, a);
+    else if (sync_kernel_in(l.k, SK_TAIL_E1, 2)) hipLaunchKernelGGL((sync_tail_kernel<EE>), dim3(l.grid), dim3(l.block), l.lds, st, a);
+    else if (sync_kernel_in(l.k, SK_LEAN_E1, 2)) hipLaunchKernelGGL((sync_lean_kernel<EE>), dim3(l.grid), dim3(l.block), l.lds, st, a);
+    else return hipErrorInvalidValue;
+    return hipSuccess;
 }
 template <int EE>
-static hipError_t sy_launch_width(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st)
+static hipError_t sy_launch_width(const SyncLaunch &l, const SyncArgs &a, hipStream_t st)
 {
-    switch (what) {
-    case SYK_SCOUT:           hipLaunchKernelGGL((sync_kernel<EE>), dim3(grid), dim3(WV), lds, st, a); break;
-    case SYK_SPEC:
-        if constexpr (EE == 1) return sy_launch_acq_e1(what, a, grid, lds, st);
-        else if constexpr (EE == 2) return sy_launch_acq_e2(what, a, grid, lds, st);
-        else hipLaunchKernelGGL((sync_spec_kernel<EE>), dim3(grid), dim3(WV), lds, st, a);
+    const dim3 g(l.grid), b(l.block);
+    switch (l.k - sync_width_index(EE)) {           // the kernel's family
+    case SK_SYNC_E1:            hipLaunchKernelGGL((sync_kernel<EE>), g, b, l.lds, st, a); break;       // (as the tail kernel: a.tail_only set by the caller)
+    case SK_SPEC_E1: case SK_TAIL_E1: case SK_LEAN_E1:
+        if constexpr (EE == 1) return sy_launch_acq_e1(l, a, st);
+        else if constexpr (EE == 2) return sy_launch_acq_e2(l, a, st);
+        else if (!sync_kernel_in(l.k, SK_SPEC_E1)) return hipErrorInvalidValue;
+        else hipLaunchKernelGGL((sync_spec_kernel<EE>), g, b, l.lds, st, a);
         break;
-    case SYK_TAIL:
-        if constexpr (EE == 1) return sy_launch_acq_e1(what, a, grid, lds, st);
-        else if constexpr (EE == 2) return sy_launch_acq_e2(what, a, grid, lds, st);
-        else hipLaunchKernelGGL((sync_kernel<EE>), dim3(grid), dim3(WV), lds, st, a);       // (a.tail_only set by the caller)
+    case SK_WALK_E1:
+        if constexpr (EE <= 2) hipLaunchKernelGGL((sync_walk_kernel<EE>), g, b, l.lds, st, a);
+        else return hipErrorInvalidValue;
         break;
-    case SYK_LEAN:
-        // (wider symbols keep the full kernel as their scout: hipcc 7.2 cannot allocate the lean one's 64-bit values
-        //  at E >= 4 under any budget worth having)
-        if constexpr (EE == 1) return sy_launch_acq_e1(what, a, grid, lds, st);
-        else if constexpr (EE == 2) return sy_launch_acq_e2(what, a, grid, lds, st);
-        else hipLaunchKernelGGL((sync_kernel<EE>), dim3(grid), dim3(WV), lds, st, a);
-        break;
-    case SYK_WALK:
-        if constexpr (EE <= 2) hipLaunchKernelGGL((sync_walk_kernel<EE>), dim3((grid + SY_WALK_WPB - 1) / SY_WALK_WPB), dim3(WV * SY_WALK_WPB), SY_WALK_WPB * SY_LDS_BYTES(EE * WV), st, a);
-        else hipLaunchKernelGGL((sync_kernel<EE>), dim3(grid), dim3(WV), lds, st, a);
-        break;
-    case SYK_PAYLOAD_FAST:    hipLaunchKernelGGL((payload_kernel<EE, true>), dim3(grid), dim3(WV), lds, st, a); break;
-    case SYK_PAYLOAD_GENERAL: hipLaunchKernelGGL((payload_kernel<EE, false>), dim3(grid), dim3(WV), lds, st, a); break;
+    case SK_PAYLOAD_FAST_E1:    hipLaunchKernelGGL((payload_kernel<EE, true>), g, b, l.lds, st, a); break;
+    case SK_PAYLOAD_GENERAL_E1: hipLaunchKernelGGL((payload_kernel<EE, false>), g, b, l.lds, st, a); break;
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
+    return hipSuccess;
 }
-hipError_t sy_launch_e1(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st);
-hipError_t sy_launch_e2(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st);
-hipError_t sy_launch_e4(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st);
-hipError_t sy_launch_e8(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st);
-hipError_t sy_launch_e16(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st);
+hipError_t sy_launch_e1(const SyncLaunch &l, const SyncArgs &a, hipStream_t st);
+hipError_t sy_launch_e2(const SyncLaunch &l, const SyncArgs &a, hipStream_t st);
+hipError_t sy_launch_e4(const SyncLaunch &l, const SyncArgs &a, hipStream_t st);
+hipError_t sy_launch_e8(const SyncLaunch &l, const SyncArgs &a, hipStream_t st);
+hipError_t sy_launch_e16(const SyncLaunch &l, const SyncArgs &a, hipStream_t st);
 #if SY_PART < 0 || SY_PART == 0
-hipError_t sy_launch_e1(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st) { return sy_launch_width<1>(what, a, grid, lds, st); }
-hipError_t sy_launch_e2(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st) { return sy_launch_width<2>(what, a, grid, lds, st); }
+hipError_t sy_launch_e1(const SyncLaunch &l, const SyncArgs &a, hipStream_t st) { return sy_launch_width<1>(l, a, st); }
+hipError_t sy_launch_e2(const SyncLaunch &l, const SyncArgs &a, hipStream_t st) { return sy_launch_width<2>(l, a, st); }
 #endif
 #if SY_PART < 0 || SY_PART == 1
-hipError_t sy_launch_e4(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st) { return sy_launch_width<4>(what, a, grid, lds, st); }
-hipError_t sy_launch_e8(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st) { return sy_launch_width<8>(what, a, grid, lds, st); }
+hipError_t sy_launch_e4(const SyncLaunch &l, const SyncArgs &a, hipStream_t st) { return sy_launch_width<4>(l, a, st); }
+hipError_t sy_launch_e8(const SyncLaunch &l, const SyncArgs &a, hipStream_t st) { return sy_launch_width<8>(l, a, st); }
 #endif
 #if SY_PART < 0 || SY_PART == 2
-hipError_t sy_launch_e16(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st) { return sy_launch_width<16>(what, a, grid, lds, st); }
+hipError_t sy_launch_e16(const SyncLaunch &l, const SyncArgs &a, hipStream_t st) { return sy_launch_width<16>(l, a, st); }
 #endif
 #if SY_PART < 0 || SY_PART == 3
-hipError_t sy_launch_acq_e1(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st) { return sy_launch_acq_width<1>(what, a, grid, lds, st); }
-hipError_t sy_launch_acq_e2(int what, const SyncArgs &a, unsigned grid, size_t lds, hipStream_t st) { return sy_launch_acq_width<2>(what, a, grid, lds, st); }
+hipError_t sy_launch_acq_e1(const SyncLaunch &l, const SyncArgs &a, hipStream_t st) { return sy_launch_acq_width<1>(l, a, st); }
+hipError_t sy_launch_acq_e2(const SyncLaunch &l, const SyncArgs &a, hipStream_t st) { return sy_launch_acq_width<2>(l, a, st); }
 #endif
 
-// part 4 = the lean segment waves of the 64-subcarrier configurations (acq_lean.hpp)
-hipError_t acq_lean_launch(const SyncArgs &a, unsigned grid, hipStream_t st);
-int acq_lean_waves(const SyncConsts &c);        // waves per SIMD of the lean segment-wave kernel if this design takes it, else 0
+// part 4 = the lean segment waves of the 48- / 64-subcarrier configurations (acq_lean.hpp)
+hipError_t acq_lean_launch(const SyncLaunch &l, const SyncArgs &a, hipStream_t st);
 #if SY_PART < 0 || SY_PART == 4
 #include "acq_lean.hpp"
-int acq_lean_waves(const SyncConsts &c) { return ((c.M == 64 || c.M == 48) && c.E == 1 && c.M_pilot <= 16 && c.M_pilot >= 1 && c.Nen <= 64) ? ACQ_LEAN_WAVES : 0; }
-hipError_t acq_lean_launch(const SyncArgs &a, unsigned grid, hipStream_t st)
+hipError_t acq_lean_launch(const SyncLaunch &l, const SyncArgs &a, hipStream_t st)
 {
-    if (a.c.M == 48) hipLaunchKernelGGL((acq_lean_kernel<63, 48>), dim3(grid), dim3(WV), 0, st, a);
-    else hipLaunchKernelGGL((acq_lean_kernel<63, 64>), dim3(grid), dim3(WV), 0, st, a);
-    return hipGetLastError();
+    if (l.k == SK_ACQ_LEAN_M48) hipLaunchKernelGGL((acq_lean_kernel<63, 48>), dim3(l.grid), dim3(l.block), l.lds, st, a);
+    else hipLaunchKernelGGL((acq_lean_kernel<63, 64>), dim3(l.grid), dim3(l.block), l.lds, st, a);
+    return hipSuccess;
 }
 #endif
 
 // part 1 also holds the lean payload workers of the 128- / 256-subcarrier configurations (payload_wide.hpp)
-hipError_t payload_wide_launch(const SyncArgs &a, unsigned grid, hipStream_t st);
-static inline bool payload_wide_takes(const SyncConsts &c) { return (c.E == 2 || c.E == 4) && c.log2M >= 7 && c.M == WV * c.E && c.M_pilot >= 1 && c.M_pilot <= WV; }
+hipError_t payload_wide_launch(const SyncLaunch &l, const SyncArgs &a, hipStream_t st);
 #if SY_PART < 0 || SY_PART == 1
 #include "payload_wide.hpp"
-hipError_t payload_wide_launch(const SyncArgs &a, unsigned grid, hipStream_t st)
+hipError_t payload_wide_launch(const SyncLaunch &l, const SyncArgs &a, hipStream_t st)
 {
-    if (a.c.E == 2) hipLaunchKernelGGL((payload_wide_kernel<63, 2>), dim3(grid), dim3(WV), 0, st, a);
-    else hipLaunchKernelGGL((payload_wide_kernel<63, 4>), dim3(grid), dim3(WV), 0, st, a);
-    return hipGetLastError();
+    if (l.k == SK_WIDE_E2) hipLaunchKernelGGL((payload_wide_kernel<63, 2>), dim3(l.grid), dim3(l.block), l.lds, st, a);
+    else hipLaunchKernelGGL((payload_wide_kernel<63, 4>), dim3(l.grid), dim3(l.block), l.lds, st, a);
+    return hipSuccess;
 }
 #endif
 
 #if SY_PART <= 0
-static hipError_t sy_launch(int what, const SyncArgs &a0, unsigned grid, size_t lds, hipStream_t st)
+// the one place where a planned launch becomes a kernel launch (a kernel of another part: through that part's launcher)
+static hipError_t sy_issue(const SyncLaunch &l, const SyncArgs &a, hipStream_t st, uint32_t soft_lds = 0, uint32_t msg_lds = 0)
 {
-    // kernels that can end up decoding a packet themselves get the Viterbi decoder's block scratch behind their LDS
-    SyncArgs a = a0;
-    a.vit_off = 0;
-    if (what == SYK_SCOUT || what == SYK_TAIL || what == SYK_PAYLOAD_GENERAL || ((what == SYK_LEAN || what == SYK_WALK) && a.c.E > 2)) {
-        a.vit_off = (uint32_t)((lds + 15) & ~(size_t)15);
-        lds = a.vit_off + (size_t)VIT_B * 8;
-    }
-    switch (a.c.E) {
-    case 1:  return sy_launch_e1(what, a, grid, lds, st);
-    case 2:  return sy_launch_e2(what, a, grid, lds, st);
-    case 4:  return sy_launch_e4(what, a, grid, lds, st);
-    case 8:  return sy_launch_e8(what, a, grid, lds, st);
-    case 16: return sy_launch_e16(what, a, grid, lds, st);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t sync_launch(const SyncArgs &a, hipStream_t st)
-{
-    if (a.nch == 0) return hipSuccess;
-    if (a.c.M > SY_MAXM) return hipErrorInvalidValue;
-    return sy_launch(SYK_SCOUT, a, a.nch, SY_LDS_BYTES(a.c.M), st);
-}
-
-hipError_t sync_launch_lean(const SyncArgs &a, hipStream_t st)
-{
-    if (a.nch == 0) return hipSuccess;
-    if (a.c.M > SY_MAXM) return hipErrorInvalidValue;
-    return sy_launch(SYK_LEAN, a, a.nch, SY_LDS_BYTES(a.c.M), st);
-}
-
-hipError_t sync_launch_walk(const SyncArgs &a, hipStream_t st)
-{
-    if (a.nch == 0) return hipSuccess;
-    if (a.c.M > SY_MAXM) return hipErrorInvalidValue;
-    return sy_launch(SYK_WALK, a, a.nch, SY_LDS_BYTES(a.c.M), st);
-}
-
-hipError_t sync_launch_tail(const SyncArgs &a, hipStream_t st)
-{
-    if (a.nch == 0) return hipSuccess;
-    return sy_launch(SYK_TAIL, a, a.nch, SY_LDS_BYTES(a.c.M), st);
-}
-
-hipError_t sync_launch_spec(const SyncArgs &a, hipStream_t st)
-{
-    if (a.nch == 0 || a.spec_cap == 0 || a.nseg == 0) return hipSuccess;
-    const unsigned grid = a.seg_phase == 1 ? a.nch : a.nch * a.nseg;
-    // scout_build = 2 and 48 / 64 subcarriers with the pilots inside one DPP row: the lean segment waves (acq_lean.hpp); else the Walker's
-    if (acq_lean_waves(a.c) && !a.seg_walker) return acq_lean_launch(a, grid, st);
-    return sy_launch(SYK_SPEC, a, grid, SY_LDS_BYTES(a.c.M), st);
-}
-
-// bytes of LDS a frame's soft bits get in this push's decode launch: 8 per coded byte, at most 56 KiB (longer frames
-// decode in HBM); sized from the longest frame the previous launch saw -- a.enc_hint, read without a sync -- so that more
-// workgroups fit a CU; 0 = no history yet: size for the configured maximum
-static uint32_t decode_soft_lds(const SyncArgs &a)
-{
-    const uint32_t enc_cap = a.enc_hint ? ((a.enc_hint + 127u) & ~127u) : a.c.max_enc_len;
-    size_t soft_lds = (size_t)8 * (enc_cap < a.c.max_enc_len ? enc_cap : a.c.max_enc_len);
-    if (soft_lds > 56 * 1024) soft_lds = 56 * 1024;      // (twice that is the workgroup's soft area: 112 KB + the message)
-    if (soft_lds < 4096) soft_lds = 4096;
-    return (uint32_t)soft_lds;
-}
-
-#ifndef SY_REST_FLOOR
-#define SY_REST_FLOOR 256u
-#endif
-#ifndef SY_GEN_FLOOR
-#define SY_GEN_FLOOR 128u
-#endif
-// does this design's payload stage consist of the lean one-frame-per-wave workers and a launch behind them (kernels.h, split_rest)?
-bool sync_payload_splits(const SyncArgs &a)
-{
-    const bool fast = ((a.c.log2M >= 6 && a.c.M == WV * a.c.E) || (a.c.M == 48 && a.c.E == 1)) && a.c.M_pilot <= WV && !(a.no_fast & 1);
-    return a.scout && fast && (a.c.M == WV || a.c.M == 48) && a.c.M_pilot <= 16 && a.payload_fr == 1 && a.payload_lean && !(a.no_fast & 6);
-}
-hipError_t sync_launch_payload(const SyncArgs &a0, int stage, hipStream_t st)
-{
-    if (a0.nch == 0 || !a0.scout || a0.max_jobs == 0) return hipSuccess;
-    SyncArgs a = a0;
-    const unsigned nj = a.max_jobs;
-    // frames of the most recent launch + a quarter: the workers and decoders walk the live list with a grid stride, so a launch that
-    // holds more than expected only takes a second turn
-    unsigned ngrid = a.frames_hint == ~0u ? nj : a.frames_hint + a.frames_hint / 4 + 64;
-    if (ngrid > nj) ngrid = nj;
-    a.live_off = 0;
-    const bool fast = ((a.c.log2M >= 6 && a.c.M == WV * a.c.E) || (a.c.M == 48 && a.c.E == 1)) && a.c.M_pilot <= WV && !(a.no_fast & 1);
-    const bool m64or48 = a.c.M == WV || a.c.M == 48;                        // the symbol widths of the lean one-frame-per-wave workers (payload_lean.hpp)
-    // the M = 64 lean workers take one BPSK / QPSK frame per wave out of the first `ngrid` of the live list; the launch behind them
-    // walks the rest of it (live_off tells it where the grid ended)
-    if (fast && m64or48 && a.c.M_pilot <= 16 && a.payload_fr == 1 && a.payload_lean && !(a.no_fast & 6)) a.live_off = ngrid;
-    if (stage == 4 && !a.live_off) return hipSuccess;                    // (only the lean workers have a launch behind them)
-    if (!a.live_off) { a.split_rest = 0; a.dec_phase = 0; }
-    a.dec_lds_soft = fast ? decode_soft_lds(a) : 0u;
-    if (!fast) a.gen_list = nullptr;
-    if (stage == 0) {
-        hipLaunchKernelGGL(place_jobs_kernel, dim3(1), dim3(WV), 0, st, a);
-        return hipGetLastError();
-    }
-    if (stage == 2) {
-        if (!fast) return hipSuccess;
-        const size_t soft_lds = a.dec_lds_soft;
-        const size_t msg_lds = ((size_t)a.c.max_payload_len + 4 + 15) & ~(size_t)15;
-        hipLaunchKernelGGL(decode_kernel, dim3(ngrid), dim3(DK_T), 2 * soft_lds + msg_lds + 16, st, a, (uint32_t)soft_lds, (uint32_t)msg_lds);      // soft bits as received | de-interleaved | message
-        return hipGetLastError();
-    }
-    if (stage == 3) {                       // the frames on the general list (filled by decode_kernel)
-        if (!fast) return hipSuccess;
-
-        // (grids from the lists' most recent sizes: kernels.h, list_hint)
-        // (Grid from the list's most recent size -- kernels.h, list_hint -- inside the K = 7 decoder's scratch, a region per workgroup.
-        //  Capping the workgroups per CU with unused dynamic LDS -- 4 = one wave per SIMD, 8, 2 -- changed nothing or cost, when the
-        //  decoder had a kernel of its own: it is bound by vector issue at any occupancy, ~0.17 us per 1200-byte frame with the chip
-        //  full, ~0.15 ms for a wave from start to end: scratch/r5/v27_pad.sh.)
-        unsigned ggrid = a.grid_hint[2] ? (nj < 4096 ? nj : 4096) : SY_GEN_FLOOR;
-        if (a.vit_scratch && ggrid > a.vit_waves) ggrid = a.vit_waves;
-        hipLaunchKernelGGL(decode_general_kernel, dim3(ggrid), dim3(WV), (size_t)VIT_B * 8, st, a);
-        return hipGetLastError();
-    }
-    // M = 64 with the pilots inside one DPP row: payload_multi_kernel, MCRX_PAYLOAD_FR frames per wave (default 1;
-    // 0 = the width-generic worker).  Measured on the bench stream: 1 -> 141.7 Gsample/s, 0 -> 138, 2 -> 138, 4 -> 118.
-    const int fr = a.payload_fr;                                         // (MCRX_PAYLOAD_FR / _LEAN / _XB: read once, when the handle is created)
-    if (fast && a.c.M == 48 && a.c.M_pilot <= 16 && fr == 1 && a.payload_lean && !(a.no_fast & 6)) {
-        // 48 subcarriers: the lean workers' 3 x 16 build (the packed-frame and round-2 workers are 64-subcarrier kernels)
-        unsigned nq = a.grid_hint[0] == ~0u ? nj : 2u * a.grid_hint[0];
-        nq = nq < SY_REST_FLOOR ? SY_REST_FLOOR : (nq > nj ? nj : nq);
-        const size_t pad = (size_t)a.payload_lds_pad;
-        if (stage != 4) hipLaunchKernelGGL((payload_lean_kernel<63, 48>), dim3(ngrid), dim3(WV), pad, st, a);
-        if (stage == 4 || !a.split_rest) hipLaunchKernelGGL((payload_lean_rest_kernel<63, 48>), dim3(a.qam_list ? nq : nj), dim3(WV), pad, st, a);
-        return hipGetLastError();
-    }
-    if (fast && a.c.M == WV && a.c.M_pilot <= 16 && fr > 0 && !(a.no_fast & 6)) {
-        if (fr == 4)      hipLaunchKernelGGL(payload_multi_kernel<4>, dim3((nj + 3) / 4), dim3(WV), 0, st, a);
-        else if (fr == 2) hipLaunchKernelGGL(payload_multi_kernel<2>, dim3((nj + 1) / 2), dim3(WV), 0, st, a);
-        else {
-            // one frame per wave: the lean build (payload_lean.hpp) unless MCRX_PAYLOAD_LEAN=0; MCRX_PAYLOAD_XB picks which
-            // butterfly stages exchange through the LDS crossbar (bit H set: the stage with partners H lanes apart)
-            const int xb = a.payload_xb;
-            const size_t pad = (size_t)a.payload_lds_pad;
-            if (!a.payload_lean) hipLaunchKernelGGL(payload_multi_kernel<1>, dim3(nj), dim3(WV), pad, st, a);
-            else {
-                // (... and one list-driven launch for what the main one does not take: frames beyond its grid, QAM payloads; sized by the
-                //  QAM list's most recent length)
-                unsigned nq = a.grid_hint[0] == ~0u ? nj : 2u * a.grid_hint[0];
-                nq = nq < SY_REST_FLOOR ? SY_REST_FLOOR : (nq > nj ? nj : nq);
-#define SY_LEAN(XB) do { if (stage != 4) hipLaunchKernelGGL(payload_lean_kernel<XB>, dim3(ngrid), dim3(WV), pad, st, a); \
-                         if (stage == 4 || !a.split_rest) hipLaunchKernelGGL(payload_lean_rest_kernel<XB>, dim3(a.qam_list ? nq : nj), dim3(WV), pad, st, a); } while (0)
-                if (xb == 0) SY_LEAN(0);
-                else         SY_LEAN(63);
-#undef SY_LEAN
-            }
+    const dim3 g(l.grid), b(l.block);
+    switch (l.k) {
+    case SK_PLACE:              hipLaunchKernelGGL(place_jobs_kernel, g, b, l.lds, st, a); break;
+    case SK_DECODE:             hipLaunchKernelGGL(decode_kernel, g, b, l.lds, st, a, soft_lds, msg_lds); break;
+    case SK_DECODE_GENERAL:     hipLaunchKernelGGL(decode_general_kernel, g, b, l.lds, st, a); break;
+    case SK_PLEAN_M48:          hipLaunchKernelGGL((payload_lean_kernel<63, 48>), g, b, l.lds, st, a); break;
+    case SK_PLEAN_REST_M48:     hipLaunchKernelGGL((payload_lean_rest_kernel<63, 48>), g, b, l.lds, st, a); break;
+    case SK_MULTI_4:            hipLaunchKernelGGL(payload_multi_kernel<4>, g, b, l.lds, st, a); break;
+    case SK_MULTI_2:            hipLaunchKernelGGL(payload_multi_kernel<2>, g, b, l.lds, st, a); break;
+    case SK_MULTI_1:            hipLaunchKernelGGL(payload_multi_kernel<1>, g, b, l.lds, st, a); break;
+    case SK_PLEAN_XB0:          hipLaunchKernelGGL(payload_lean_kernel<0>, g, b, l.lds, st, a); break;
+    case SK_PLEAN_REST_XB0:     hipLaunchKernelGGL(payload_lean_rest_kernel<0>, g, b, l.lds, st, a); break;
+    case SK_PLEAN_XB63:         hipLaunchKernelGGL(payload_lean_kernel<63>, g, b, l.lds, st, a); break;
+    case SK_PLEAN_REST_XB63:    hipLaunchKernelGGL(payload_lean_rest_kernel<63>, g, b, l.lds, st, a); break;
+    case SK_ACQ_LEAN_M48: case SK_ACQ_LEAN_M64: return acq_lean_launch(l, a, st);
+    case SK_WIDE_E2: case SK_WIDE_E4:           return payload_wide_launch(l, a, st);
+    default:                    // the families with a kernel per symbol width
+        switch (a.c.E) {
+        case 1:  return sy_launch_e1(l, a, st);
+        case 2:  return sy_launch_e2(l, a, st);
+        case 4:  return sy_launch_e4(l, a, st);
+        case 8:  return sy_launch_e8(l, a, st);
+        case 16: return sy_launch_e16(l, a, st);
+        default: return hipErrorInvalidValue;
         }
-        return hipGetLastError();
     }
-    // 128 / 256 subcarriers: the lean one-frame-per-wave workers of payload_wide.hpp (round 6) unless the handle asks for the width-generic
-    // kernel (worker_build = 5, or payload_lean off: A/B and parity tests)
-    if (fast && payload_wide_takes(a.c) && a.payload_lean && a.payload_fr == 1 && !(a.no_fast & 6))
-        return payload_wide_launch(a, ngrid, st);
-    return sy_launch(fast ? SYK_PAYLOAD_FAST : SYK_PAYLOAD_GENERAL, a, nj, SY_LDS_BYTES(a.c.M), st);
+    return hipSuccess;
+}
+
+static SyncDesign sy_design(const SyncConsts &c) { return { c.M, c.E, c.log2M, c.M_pilot, c.Nen, c.max_enc_len, c.max_payload_len }; }
+int acq_lean_waves(const SyncConsts &c) { return sync_lean_waves(sy_design(c)); }
+
+static hipError_t sy_acquire(SyncAcq what, const SyncArgs &a0, hipStream_t st)
+{
+    const SyncAcqPlan p = sync_acq_plan(what, { sy_design(a0.c), a0.nch, a0.nseg, a0.spec_cap, a0.seg_phase, a0.seg_walker });
+    if (p.status != SYNC_LAUNCH) return p.status == SYNC_NOTHING ? hipSuccess : hipErrorInvalidValue;
+    SyncArgs a = a0;
+    a.vit_off = p.vit_off;
+    const hipError_t e = sy_issue(p.l, a, st);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+hipError_t sync_launch(const SyncArgs &a, hipStream_t st) { return sy_acquire(SYNC_ACQ_SCOUT, a, st); }
+hipError_t sync_launch_lean(const SyncArgs &a, hipStream_t st) { return sy_acquire(SYNC_ACQ_LEAN, a, st); }
+hipError_t sync_launch_walk(const SyncArgs &a, hipStream_t st) { return sy_acquire(SYNC_ACQ_WALK, a, st); }
+hipError_t sync_launch_tail(const SyncArgs &a, hipStream_t st) { return sy_acquire(SYNC_ACQ_TAIL, a, st); }
+hipError_t sync_launch_spec(const SyncArgs &a, hipStream_t st) { return sy_acquire(SYNC_ACQ_SPEC, a, st); }
+
+static SyncPayloadInputs sy_payload_inputs(const SyncArgs &a)
+{
+    SyncPayloadInputs in = {};
+    in.d = sy_design(a.c);
+    in.nch = a.nch; in.max_jobs = a.max_jobs; in.frames_hint = a.frames_hint; in.grid_hint0 = a.grid_hint[0]; in.grid_hint2 = a.grid_hint[2];
+    in.vit_waves = a.vit_waves; in.enc_hint = a.enc_hint; in.payload_lds_pad = a.payload_lds_pad;
+    in.have_qam_list = a.qam_list != nullptr; in.have_vit_scratch = a.vit_scratch != nullptr;
+    in.scout = a.scout; in.no_fast = a.no_fast; in.payload_fr = a.payload_fr; in.payload_lean = a.payload_lean; in.payload_xb = a.payload_xb;
+    in.split_rest = a.split_rest; in.dec_phase = a.dec_phase;
+    return in;
+}
+bool sync_payload_splits(const SyncArgs &a) { return sync_payload_splits(sy_payload_inputs(a)); }
+
+hipError_t sync_launch_payload(const SyncArgs &a0, SyncStage stage, hipStream_t st)
+{
+    const SyncPayloadPlan p = sync_payload_plan(sy_payload_inputs(a0), stage);
+    if (p.status != SYNC_LAUNCH) return p.status == SYNC_NOTHING ? hipSuccess : hipErrorInvalidValue;
+    SyncArgs a = a0;
+    a.live_off = p.live_off; a.split_rest = p.split_rest; a.dec_phase = p.dec_phase; a.dec_lds_soft = p.dec_lds_soft; a.vit_off = p.vit_off;
+    if (p.clear_gen_list) a.gen_list = nullptr;
+    for (int i = 0; i < p.n; i++) {
+        const hipError_t e = sy_issue(p.l[i], a, st, p.soft_lds, p.msg_lds);
+        if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
 }
 #endif  // SY_PART <= 0
 

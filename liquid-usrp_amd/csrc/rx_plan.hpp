@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/mcrx_hip.h"
 #include "acq_shared.h"
+#include "sync_plan.hpp"        // sync_fast_design(): which designs the lean path takes
 #include "config_read.hpp"
 
 #include <algorithm>
@@ -174,7 +175,7 @@ inline int rx_plan(const RxInputs &in, RxPlan *out, const char **err)
     unsigned E = 1; while (E < (M + 63) / 64) E <<= 1;
     unsigned log2M = 0;
     if ((M & (M - 1)) == 0) while ((1u << log2M) < M) log2M++;
-    r.lean = (log2M >= 6 && M == 64 * E && in.M_pilot <= 64) || (M == 48 && E == 1 && in.M_pilot <= 64);
+    r.lean = sync_fast_design({ (int)M, (int)E, (int)log2M, (int)in.M_pilot, 0, 0, 0 });
     if (r.scout) {
         r.max_jobs = 2 * r.max_rec + 4 * r.nch + 1024;
         if (cfg.payload_soft) {

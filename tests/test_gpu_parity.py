@@ -688,6 +688,24 @@ def test_both_builds_of_the_rounds_scout_equal_the_oracle(oracle, product, scout
     rx.close(); tx.close()
 
 
+@pytest.mark.parametrize("cfg", [dict(scout_build=1), dict(acquisition=4)], ids=["budgeted_scout", "one_kernel_scout"])
+def test_alternate_scouts_at_two_samples_per_lane(oracle, product, cfg):
+    """The two launch targets of 128-subcarrier symbols (E = 2) that only a configuration field selects (csrc/sync_plan.hpp): the scouts'
+    168-register build (scout_build = 1: sync_lean_kernel<2>) and the whole state machine as the only acquisition kernel
+    (acquisition = 4: sync_kernel<2>).  Two channels, four short frames each, two pushes: the oracle's frames, bytes and flags identical."""
+    N, M, cp, nf, plen = 2, 128, 16, 4, 60
+    iq, _ = oracle.synth_traffic(N, M, cp, 4, nf, payload_len=plen, mod=40, fec1=6, seed=128)
+    x = iq[:len(iq) // (32 * N) * (32 * N)]
+    ora = oracle.MultiChannelRx(N, M, cp, 4)
+    ora.execute(x)
+    assert len(ora.frames) == nf * N and all(f.payload_valid for f in ora.frames)
+    rx = product.multichannelrx(N, M, cp, 4, max_payload_len=64, **cfg)
+    half = len(x) // 2 // (32 * N) * (32 * N)
+    rx.Execute(x[:half]); rx.Execute(x[half:]); rx.Flush()          # (two pushes: a frame straddles the cut)
+    check_frames(rx.frames, ora.frames)
+    rx.close()
+
+
 def test_bulk_host_execute_equals_device_path(product):
     """Execute(host buffer) takes whole tiles straight from the caller's memory in large chunks and stages only
     what does not fill a tile; however the buffer is cut, the frames must equal those of the device path."""
