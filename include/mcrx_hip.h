@@ -629,6 +629,61 @@ int         mcrx_hip_userchan_apply_tiles(mcrx_hip_userchan_t q, const void *d_i
                                           size_t lead_blocks, void *d_out, void *stream);
 const char *mcrx_hip_userchan_last_error(void);
 
+/* ---- per-user channel emulator: fading rays per user (Rayleigh / Rician with Doppler) ----
+ * With fading on, ray i of local channel c is multiplied by a complex gain g_ci(b) -- a function of the ABSOLUTE output block index b
+ * (signed 64-bit) alone, so cuts, leads and channel shards stay invisible bit for bit.  With fading off (the state of a new handle, and
+ * after a NULL) the operator is the one described above, word for word, and launches the same kernels.
+ *   B = 2^log2_block blocks is the update interval; row = b >> log2_block (arithmetic: negative b works), n_r = (uint64_t)(row <<
+ *   log2_block) mod 2^64, f = (b & (B - 1)) 2^-log2_block; e(p) of a 64-bit phase p is (cos, sin)(2 pi (p >> 32) / 2^32).
+ *     G_ci[row] = c_los_ci e((psi_ci << 32) + Lambda_ci n_r) + c_sc_ci sum_{k<S} e((Phi_cik << 32) + N_cik n_r)     phases mod 2^64
+ *     g_ci(b)   = G_ci[row] + f (G_ci[row+1] - G_ci[row])                                                          linear, by definition
+ *     s_c[b]    = sum_{i<T_c} (g_ci(b) a_ci) x_c[b - d_ci]                                                         table order
+ *   The gain is indexed by the output time b, not by b - d_ci.  Rotation and gain behind s_c[b] are unchanged.
+ * log2_block >= 3: granules are 8 blocks and first_block is a multiple of 8, so a granule never straddles a grid row.
+ * The integers are made on the host as the wideband emulator's are (mcrx_hip_chanfade_*), from the Philox4x32-10 words of counter
+ * (k, i, 2, id_c) and key (lo32(seed), hi32(seed)): the third word keeps them apart from the wideband emulator's (k, i, 1, 0), and id_c
+ * is the user's own -- a channel shard that keeps its users' ids reproduces their channels of the whole table bit for bit.
+ * Dopplers are cycles per channel-rate sample.  A user with enabled == 0 has c_los = 1, c_sc = 0, zero steps and phases: G = (1, 0),
+ * and their output equals that of a handle without fading (only the sign of a zero may differ).
+ * The handle keeps the sinusoids' integers and a table of gains in device memory: float2 [row][channel][4], 32 bytes a channel and
+ * row, grown to the (((first_block & (B - 1)) + nblocks - 1) >> log2_block) + 2 rows a call needs, up to table_rows rows
+ * (0: the most rows that fit 64 MiB for the handle's channel count); a longer call runs as consecutive spans on the caller's stream,
+ * each cut at a multiple of 8 blocks, which changes no bit of the output.  Because of that table, calls of
+ * mcrx_hip_userchan_apply_tiles on ONE fading handle must be ordered on the device (one stream, or events of the caller's); handles
+ * without fading stay free of this.  (These functions do not carry the emulator's prefix: its set of entry points is closed.  Errors
+ * are read with mcrx_hip_userchan_last_error.) */
+#define MCRX_USERFADE_MIN_LOG2_BLOCK 3
+#define MCRX_USERFADE_MAX_LOG2_BLOCK 20
+typedef struct {
+    uint32_t enabled, id;                            /* 0: this user does not fade (the rest is not looked at); the user's id_c */
+    double   doppler[MCRX_USERCHAN_MAX_RAYS];        /* f_d >= 0, cycles per channel-rate sample */
+    double   los_doppler[MCRX_USERCHAN_MAX_RAYS];    /* signed, cycles per channel-rate sample */
+    float    rice_k[MCRX_USERCHAN_MAX_RAYS];         /* linear, >= 0, finite */
+    uint32_t los_phase[MCRX_USERCHAN_MAX_RAYS];      /* 2^32 * cycles */
+} mcrx_hip_userfade_user;
+typedef struct {
+    uint32_t struct_size, user_struct_size;          /* sizeof(mcrx_hip_userfade_config), sizeof(mcrx_hip_userfade_user) */
+    uint32_t log2_block, num_sinusoids;              /* 3 .. 20; 1 .. MCRX_CHANEMU_MAX_SINUSOIDS */
+    uint32_t table_rows, reserved;                   /* 0 = default, else >= 2; reserved: 0 */
+    uint64_t seed;
+} mcrx_hip_userfade_config;
+/* users[num_channels of the handle]; f == NULL: fading off (users is not looked at).  Waits for the device before it replaces the
+ * handle's tables.  MCRX_EINVAL, before any device work and with the handle left as it was: a null handle, a null users with f given,
+ * wrong struct sizes, log2_block outside 3 .. 20, num_sinusoids outside 1 .. 16, table_rows == 1, and for a ray (< num_rays) of an
+ * enabled user a Doppler that is not finite, a negative doppler, doppler * B > 1/8 or |los_doppler| * B > 1/8 (the grid must sample
+ * the gain), a rice_k that is negative or not finite. */
+int      mcrx_hip_userfade_set(mcrx_hip_userchan_t q, const mcrx_hip_userfade_config *f, const mcrx_hip_userfade_user *users);
+int      mcrx_hip_userfade_on(mcrx_hip_userchan_t q);                                /* 1 with fading on; 0 for a null handle */
+/* host, no GPU: the integers and coefficients ray `ray` (< MCRX_USERCHAN_MAX_RAYS) of user *u gets -- steps[0] / phases[0] the
+ * line-of-sight term, then the num_sinusoids scattered ones (1 + num_sinusoids entries each); coef = { c_los, c_sc }.  Checks `f` and
+ * that ray of `u` as set does. */
+int      mcrx_hip_userfade_selftest(const mcrx_hip_userfade_config *f, const mcrx_hip_userfade_user *u, unsigned ray, int64_t *steps,
+                                    uint32_t *phases, float coef[2]);
+/* The gain kernel on its own, for tests and measurements: G_ci[first_row + r], r < rows, as float2 [rows][num_channels][4] into the
+ * caller's 16-byte aligned device buffer, asynchronously on `stream` (entries of rays a channel does not have are (1, 0)).
+ * MCRX_EINVAL with fading off. */
+int      mcrx_hip_userfade_gains(mcrx_hip_userchan_t q, long long first_row, uint32_t rows, void *d_table, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,11 @@ _EXPORTS = {
     "mcrx_hip_userchan_lead_blocks": (C.c_uint, [C.c_void_p]),
     "mcrx_hip_userchan_apply_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "mcrx_hip_userchan_last_error": (C.c_char_p, []),
+    "mcrx_hip_userfade_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_userfade_on": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_userfade_selftest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_int64), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_float)]),
+    "mcrx_hip_userfade_gains": (C.c_int, [C.c_void_p, C.c_longlong, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -938,6 +943,85 @@ def userchan_channel(taps=((0, 1.0),), gain_db=0.0, cfo_step=0, phase0=0, delay=
     return u
 
 
+USERFADE_MIN_LOG2_BLOCK, USERFADE_MAX_LOG2_BLOCK = 3, 20      # MCRX_USERFADE_MIN_LOG2_BLOCK, _MAX_LOG2_BLOCK
+
+
+class UserfadeUser(C.Structure):
+    _fields_ = [("enabled", C.c_uint32), ("id", C.c_uint32), ("doppler", C.c_double * USERCHAN_MAX_RAYS),
+                ("los_doppler", C.c_double * USERCHAN_MAX_RAYS), ("rice_k", C.c_float * USERCHAN_MAX_RAYS),
+                ("los_phase", C.c_uint32 * USERCHAN_MAX_RAYS)]
+
+
+class UserfadeConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("user_struct_size", C.c_uint32), ("log2_block", C.c_uint32), ("num_sinusoids", C.c_uint32),
+                ("table_rows", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
+
+
+_USERFADE_KEYS = ("log2_block", "sinusoids", "seed", "table_rows", "users")
+_USERFADE_USER_KEYS = ("doppler", "rice_k", "los_doppler", "los_phase", "id")
+
+
+def userchan_doppler(cycles_per_ofdm_symbol, M, cp):
+    """The userchan Doppler (cycles per channel-rate sample) of a gain that turns `cycles_per_ofdm_symbol` cycles in one OFDM symbol
+    of M + cp channel-rate samples."""
+    return float(cycles_per_ofdm_symbol) / (M + cp)
+
+
+def userfade_user(num_rays, log2_block, index, doppler, rice_k=0.0, los_doppler=0.0, los_phase=0, id=None):
+    """The mcrx_hip_userfade_user structure of one fading user with `num_rays` rays: per-ray entries are scalars (every ray gets them) or
+    sequences of num_rays values; id defaults to `index`, the user's place in the table.  ValueError for what the library refuses."""
+    def per_ray(v, name, conv):
+        vals = [conv(x) for x in v] if hasattr(v, "__len__") else [conv(v)] * num_rays
+        if len(vals) != num_rays:
+            raise ValueError("fading: %s has %d entries for %d rays" % (name, len(vals), num_rays))
+        return vals
+    u = UserfadeUser()
+    uid = index if id is None else id
+    if int(uid) != uid or not 0 <= int(uid) < (1 << 32):
+        raise ValueError("fading: a user's id is a whole number, 0 .. 2^32 - 1")
+    u.enabled, u.id = 1, int(uid)
+    B = float(1 << int(log2_block))
+    fd, fl = per_ray(doppler, "doppler", float), per_ray(los_doppler, "los_doppler", float)
+    rk, ph = per_ray(rice_k, "rice_k", float), per_ray(los_phase, "los_phase", int)
+    for i in range(num_rays):
+        if not (math.isfinite(fd[i]) and math.isfinite(fl[i])):
+            raise ValueError("fading: a Doppler is not finite")
+        if fd[i] < 0.0 or fd[i] * B > 0.125 or abs(fl[i]) * B > 0.125:
+            raise ValueError("fading: 0 <= doppler and doppler * 2^log2_block <= 1/8 (|los_doppler| likewise): the grid must sample the gain")
+        if not (math.isfinite(rk[i]) and rk[i] >= 0.0 and math.isfinite(C.c_float(rk[i]).value)):
+            raise ValueError("fading: rice_k must be finite and not negative")
+        u.doppler[i], u.los_doppler[i], u.rice_k[i], u.los_phase[i] = fd[i], fl[i], rk[i], ph[i] % (1 << 32)
+    return u
+
+
+def userchan_fading(rays, log2_block=4, sinusoids=16, seed=0, table_rows=0, users=None):
+    """(mcrx_hip_userfade_config, mcrx_hip_userfade_user[len(rays)]) of a fading description for channels with rays[c] rays each:
+    users[c] is None (that user does not fade), a dict(doppler, rice_k=0, los_doppler=0, los_phase=0, id=None) or a UserfadeUser."""
+    for v, name, lo, hi in ((log2_block, "log2_block", USERFADE_MIN_LOG2_BLOCK, USERFADE_MAX_LOG2_BLOCK),
+                            (sinusoids, "sinusoids", 1, CHANEMU_MAX_SINUSOIDS)):
+        if int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError("fading: %s must be %d .. %d" % (name, lo, hi))
+    if int(table_rows) != table_rows or int(table_rows) == 1 or not 0 <= int(table_rows) < (1 << 32):
+        raise ValueError("fading: table_rows must be 0 (default) or 2 .. 2^32 - 1")
+    users = list(users) if users is not None else []
+    if len(users) != len(rays):
+        raise ValueError("fading: users has %d entries for %d channels" % (len(users), len(rays)))
+    f = UserfadeConfig()
+    f.struct_size, f.user_struct_size = C.sizeof(UserfadeConfig), C.sizeof(UserfadeUser)
+    f.log2_block, f.num_sinusoids, f.table_rows, f.seed = int(log2_block), int(sinusoids), int(table_rows), int(seed) % (1 << 64)
+    table = (UserfadeUser * len(rays))()
+    for c, u in enumerate(users):
+        if u is None:
+            table[c].id = c
+        elif isinstance(u, UserfadeUser):
+            table[c] = u
+        elif isinstance(u, dict) and "doppler" in u and all(k in _USERFADE_USER_KEYS for k in u):
+            table[c] = userfade_user(rays[c], f.log2_block, c, **u)
+        else:
+            raise ValueError("fading: a user is None or a dict with 'doppler' and keys of %s" % (_USERFADE_USER_KEYS,))
+    return f, table
+
+
 class userchan(object):
     """Per-user channel emulator on the transmitter's channel tiles, between TxTraffic.tiles and multichanneltx.synthesize
     (mcrx_hip_userchan_*): every channel has its own multipath, oscillator, timing and level, at the channel rate.
@@ -947,10 +1031,18 @@ class userchan(object):
     One entry per local channel (1 .. 1024): 1 .. 4 rays with delays in channel-rate samples (<= 255 with the timing offset `delay`
     added), cfo_step / phase0 32-bit phases per channel-rate sample (userchan_cfo_step).  The operator keeps no state: apply() is a
     function of the absolute block index and of the tiles it is handed, which include `lead_blocks` blocks in front of the output's
-    first.  When no channel has a step or a start phase the rotation is not computed; otherwise every channel is rotated."""
+    first.  When no channel has a step or a start phase the rotation is not computed; otherwise every channel is rotated.
 
-    def __init__(self, channels):
+    fading=dict(log2_block=4, sinusoids=16, seed=0, table_rows=0, users=[None | dict(doppler, rice_k=0, los_doppler=0, los_phase=0,
+    id=None), ...]) makes the rays of the users named Rayleigh (rice_k = 0) or Rician fading ones (mcrx_hip_userfade_*): one entry per
+    channel, None for a user who does not fade; Dopplers in cycles per channel-rate sample (userchan_doppler), each of doppler, rice_k,
+    los_doppler, los_phase one value or one per ray; the gains are updated every 2^log2_block blocks (3 .. 20) and interpolated
+    linearly between.  A user's gains follow from the seed and their id (default: their index), which shard() keeps.  Calls on a
+    fading handle share its gain table: keep them ordered on the device (one stream, or events)."""
+
+    def __init__(self, channels, fading=None):
         self._h = C.c_void_p()
+        self._fading = None
         chans = []
         for ch in channels:
             if isinstance(ch, UserchanChannel):
@@ -962,14 +1054,51 @@ class userchan(object):
         if not 1 <= len(chans) <= USERCHAN_MAX_CHANNELS:
             raise ValueError("1 .. %d channels a handle" % USERCHAN_MAX_CHANNELS)
         self._table = (UserchanChannel * len(chans))(*chans)
+        fading = self._fading_structs(fading)
         rc = lib().mcrx_hip_userchan_create(C.byref(self._h), len(chans), C.addressof(self._table), C.sizeof(UserchanChannel))
         if rc != MCRX_OK:
             self._h = C.c_void_p()
             self._chk(rc, "mcrx_hip_userchan_create")
+        if fading is not None:
+            self._set_fading(fading)
 
     @staticmethod
     def _chk(rc, name):
         _raise_rc(rc, name, lib().mcrx_hip_userchan_last_error)
+
+    def _fading_structs(self, fading):
+        if fading is None:
+            return None
+        if not isinstance(fading, dict) or any(k not in _USERFADE_KEYS for k in fading):
+            raise ValueError("fading is None or a dict with keys of %s" % (_USERFADE_KEYS,))
+        return userchan_fading([int(u.num_rays) for u in self._table], **fading)
+
+    def _set_fading(self, structs):
+        if structs is None:
+            self._chk(lib().mcrx_hip_userfade_set(self._h, None, None), "mcrx_hip_userfade_set")
+        else:
+            self._chk(lib().mcrx_hip_userfade_set(self._h, C.addressof(structs[0]), C.addressof(structs[1])), "mcrx_hip_userfade_set")
+        self._fading = structs
+
+    def set_fading(self, fading):
+        """None: fading off (the emulator of constant rays, the present kernels); a dict as at construction: fading on with these
+        parameters.  Waits for the device before the handle's tables change."""
+        self._set_fading(self._fading_structs(fading))
+
+    def fading_on(self):
+        return bool(lib().mcrx_hip_userfade_on(self._h))
+
+    def gains(self, first_row, rows, stream=None):
+        """The gain table's rows first_row .. first_row + rows - 1 (grid row = block >> log2_block, signed) as a complex64 CUDA tensor
+        [rows, num_channels, 4]: what apply() interpolates between; entries of rays a channel does not have, and of users who do not
+        fade, are 1.  For tests and measurements."""
+        import torch
+        out = torch.zeros((int(rows), len(self._table), USERCHAN_MAX_RAYS), dtype=torch.complex64, device="cuda")
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device)
+        self._chk(lib().mcrx_hip_userfade_gains(self._h, int(first_row), int(rows), _dptr(out), _stream_ptr(stream)),
+                  "mcrx_hip_userfade_gains")
+        return out
 
     @property
     def num_channels(self):
@@ -984,7 +1113,13 @@ class userchan(object):
         """A new handle for local channels [first, first + count): what a channel shard of the transmitter (TxTraffic) applies."""
         if int(first) != first or int(count) != count or not (0 <= first and 1 <= count and first + count <= len(self._table)):
             raise ValueError("a shard is channels [first, first + count) of this handle's %d" % len(self._table))
-        return userchan([self._table[c] for c in range(int(first), int(first) + int(count))])
+        sel = range(int(first), int(first) + int(count))
+        fading = None
+        if self._fading is not None:          # the users keep their ids, and with them their gains
+            f, users = self._fading
+            fading = dict(log2_block=f.log2_block, sinusoids=f.num_sinusoids, seed=f.seed, table_rows=f.table_rows,
+                          users=[users[c] for c in sel])
+        return userchan([self._table[c] for c in sel], fading=fading)
 
     def apply(self, tiles, first_block, nblocks, lead_blocks=None, out=None, stream=None):
         """tiles: granules [tile][channel][8] of blocks [first_block - lead_blocks, first_block + nblocks), a contiguous torch complex64

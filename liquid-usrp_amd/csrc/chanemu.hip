@@ -36,24 +36,12 @@
 #include "../../include/mcrx_hip.h"
 #include "devmath.h"
 #include "devscope.hpp"
+#include "fadegen.hpp"
 #include "sc16.hpp"
 
 namespace mcrx {
 
-// Philox4x32-10 (Salmon et al., SC'11), the same code on host (mcrx_hip_chanemu_selftest_words) and device
-struct Philox4 { uint32_t w[4]; };
-__host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    Philox4 o; o.w[0] = c0; o.w[1] = c1; o.w[2] = c2; o.w[3] = c3;
-    return o;
-}
+// (Philox4x32-10 comes from fadegen.hpp: the same code on host -- mcrx_hip_chanemu_selftest_words -- and device)
 // the words of the pair that holds absolute sample n
 __host__ __device__ inline Philox4 chanemu_pair_words(uint64_t seed, uint64_t n)
 {
@@ -251,18 +239,7 @@ static const char *fading_check(const mcrx_hip_chanemu_fading *f, unsigned ray0,
 // the integers and coefficients of one ray (a checked configuration): entry 0 the line-of-sight term, then the S scattered sinusoids
 static void fading_ray(const mcrx_hip_chanemu_fading *f, unsigned i, int64_t *steps, uint32_t *phases, float coef[2])
 {
-    const uint32_t S = f->num_sinusoids;
-    steps[0] = (int64_t)std::rint(f->los_doppler[i] * 18446744073709551616.0);
-    phases[0] = f->los_phase[i];
-    for (uint32_t k = 0; k < S; k++) {
-        const Philox4 w = philox4x32_10(k, i, 1u, 0u, (uint32_t)f->seed, (uint32_t)(f->seed >> 32));
-        const double alpha = 2.0 * 3.14159265358979323846 * ((double)k + (double)w.w[0] * 2.3283064365386963e-10) / (double)S;
-        steps[1 + k] = (int64_t)std::rint(f->doppler[i] * std::cos(alpha) * 18446744073709551616.0);
-        phases[1 + k] = w.w[1];
-    }
-    const double K = (double)f->rice_k[i];
-    coef[0] = (float)std::sqrt(K / (K + 1.0));
-    coef[1] = (float)std::sqrt(1.0 / ((K + 1.0) * (double)S));
+    fade_ray_integers(f->seed, i, 1u, 0u, f->num_sinusoids, f->doppler[i], f->los_doppler[i], f->rice_k[i], f->los_phase[i], steps, phases, coef);
 }
 
 extern "C" int mcrx_hip_chanfade_selftest(const mcrx_hip_chanemu_fading *f, unsigned ray, int64_t *steps, uint32_t *phases, float coef[2])

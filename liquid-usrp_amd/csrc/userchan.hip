@@ -21,6 +21,16 @@
 // wave reads 256 contiguous bytes each, and the plane of steps and phases is read by the rotating build only.
 // Builds without rotation carry none of that code (the template parameter; a handle rotates when any of its channels does).
 //
+// With fading on (mcrx_hip_userfade_*) the constant a_ci becomes g_ci(b) a_ci, a sum of sinusoids sampled on the
+// grid b = row 2^L and interpolated linearly between its rows -- chanemu.hip's definition at the channel rate, per user:
+//   G_ci[row] = c_los e((psi << 32) + Lambda n_r) + c_sc sum_{k<S} e((Phi_k << 32) + N_k n_r)       n_r = row << L, phases mod 2^64
+//   g_ci(b)   = fmaf(f, G_ci[row+1] - G_ci[row], G_ci[row])     row = b >> L, f = (b & (2^L - 1)) 2^-L (exact), per component
+//   s_c[b]    = sum_i (g_ci(b) a_ci) x_c[b - d_ci]              the product in cmul_fx's shape, then the two fmaf per component as above
+// userchan_gain_kernel writes the rows a span needs into the handle's table, float2 [row][channel][4]: a lane per (channel, ray) holds
+// that ray's 1 + S phases and steps in registers and walks a chunk of rows, so a wave loads 64 adjacent integers of every plane
+// ([term][channel * 4 + ray]) and stores 512 contiguous bytes a row.  userchan_kernel<ROT, FADE = true> reads two rows per granule
+// (L >= 3: a granule never straddles a row), one 16-byte word for rays 0, 1 and one for rays 2, 3 of each.
+//
 // Contraction is switched off for this file: sincos_u32's polynomials and everything else round the same way in both builds and in every
 // inlined copy, and the products that matter are written as fmaf.
 #pragma clang fp contract(off)
@@ -32,6 +42,7 @@
 #include "../../include/mcrx_hip.h"
 #include "devmath.h"
 #include "devscope.hpp"
+#include "fadegen.hpp"
 
 namespace mcrx {
 
@@ -43,12 +54,64 @@ struct UserchanArgs {
     uint32_t C, total;              // channels; sample pairs of the output = lanes with work
     uint32_t lead;                  // blocks the input holds in front of the output's first
     uint32_t first_lo;              // the low word of the output's first absolute block index
+    // FADE builds only: the gain table of this span, its row 0 = the grid row of the output's first block
+    const float4 *gtab;             // [row][C][2]: (G of rays 0, 1) / (rays 2, 3)
+    uint32_t frac0, L;              // first block & (2^L - 1); log2 of the update interval
+    float finv;                     // 2^-L
 };
+
+#define USERFADE_TERMS (MCRX_CHANEMU_MAX_SINUSOIDS + 1)     // the line-of-sight term and up to 16 scattered ones
+#define USERFADE_CHUNK 8u                                   // rows a lane of the gain kernel walks
+
+struct UserfadeGainArgs {
+    const uint64_t *step;           // [1 + S][lanes]: 2^64 * cycles per channel-rate sample, entry 0 the line-of-sight term
+    const uint32_t *phase;          // [1 + S][lanes]
+    const float2 *coef;             // [lanes]: c_los, c_sc
+    float2 *table;                  // [rows][lanes]
+    long long row0;                 // the grid row of the table's first
+    uint32_t rows, lanes, L, S;     // lanes = channels * 4
+};
+
+// table[r][lane] = G_lane[row0 + r], r < rows: blockIdx.x is a chunk of rows, blockIdx.y * 256 + threadIdx.x the lane = channel * 4 + ray
+__global__ __launch_bounds__(256) void userchan_gain_kernel(UserfadeGainArgs a)
+{
+    const uint32_t lane = blockIdx.y * 256u + threadIdx.x;
+    if (lane >= a.lanes) return;
+    const uint32_t r0 = blockIdx.x * USERFADE_CHUNK;                    // < rows (the grid)
+    const uint32_t nr = a.rows - r0 < USERFADE_CHUNK ? a.rows - r0 : USERFADE_CHUNK;
+    const uint64_t nb = (uint64_t)(a.row0 + (long long)r0) << a.L;      // the grid index wraps with the 64-bit position
+    uint64_t p[USERFADE_TERMS], dp[USERFADE_TERMS];
+#pragma unroll
+    for (uint32_t j = 0; j < USERFADE_TERMS; j++) {
+        p[j] = dp[j] = 0;
+        if (j <= a.S) {
+            const uint64_t st = a.step[(size_t)j * a.lanes + lane];
+            p[j] = ((uint64_t)a.phase[(size_t)j * a.lanes + lane] << 32) + st * nb;
+            dp[j] = st << a.L;                                          // one row further: st * (nb + 2^L) mod 2^64
+        }
+    }
+    const float2 co = a.coef[lane];
+    float2 *out = a.table + (size_t)r0 * a.lanes + lane;
+    for (uint32_t r = 0; r < nr; r++) {
+        float sn, cs;
+        sincos_u32((uint32_t)(p[0] >> 32), sn, cs);
+        float2 G = make_float2(co.x * cs, co.x * sn);
+        p[0] += dp[0];
+#pragma unroll
+        for (uint32_t k = 1; k < USERFADE_TERMS; k++)
+            if (k <= a.S) {
+                sincos_u32((uint32_t)(p[k] >> 32), sn, cs);
+                G.x = fmaf(co.y, cs, G.x); G.y = fmaf(co.y, sn, G.y);
+                p[k] += dp[k];
+            }
+        out[(size_t)r * a.lanes] = G;
+    }
+}
 
 // the input's sample at block r of its own range (r >= 0), channel c
 __device__ __forceinline__ size_t userchan_at(uint32_t r, uint32_t c, uint32_t C) { return ((size_t)(r >> 3) * C + c) * 8u + (r & 7u); }
 
-template <bool ROT>
+template <bool ROT, bool FADE>
 __global__ __launch_bounds__(256) void userchan_kernel(UserchanArgs a)
 {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
@@ -79,9 +142,30 @@ __global__ __launch_bounds__(256) void userchan_kernel(UserchanArgs a)
         }
     }
     float2 s0 = make_float2(0.f, 0.f), s1 = s0;
+    // FADE: the granule's grid row relative to the table's first, the pair's two fractions, and the two rows' words
+    float4 ga01 = make_float4(0.f, 0.f, 0.f, 0.f), ga23 = ga01, gb01 = ga01, gb23 = ga01;
+    float f0 = 0.f, f1 = 0.f;
+    if (FADE) {
+        const uint32_t pm = a.frac0 + m;                    // < 2^32: frac0 < 2^20, m < 2^31
+        const uint32_t frac = pm & ((1u << a.L) - 1u);      // even, frac + 1 < 2^L
+        f0 = (float)frac * a.finv; f1 = (float)(frac + 1u) * a.finv;
+        const float4 *ra = a.gtab + ((size_t)(pm >> a.L) * a.C + c) * 2u, *rb = ra + (size_t)a.C * 2u;
+        ga01 = ra[0]; gb01 = rb[0];
+        if (T > 2u) { ga23 = ra[1]; gb23 = rb[1]; }
+    }
 #pragma unroll
     for (int i = 0; i < MCRX_USERCHAN_MAX_RAYS; i++)
-        if (i < (int)T) {
+        if (i < (int)T && FADE) {
+            const float4 wa = i < 2 ? ga01 : ga23, wb = i < 2 ? gb01 : gb23;
+            const float2 G0 = (i & 1) ? make_float2(wa.z, wa.w) : make_float2(wa.x, wa.y);
+            const float2 G1 = (i & 1) ? make_float2(wb.z, wb.w) : make_float2(wb.x, wb.y);
+            const float dx = G1.x - G0.x, dy = G1.y - G0.y;
+            const float2 av = make_float2(are[i], aim[i]);
+            const float2 h0 = cmul_fx(make_float2(fmaf(f0, dx, G0.x), fmaf(f0, dy, G0.y)), av);
+            const float2 h1 = cmul_fx(make_float2(fmaf(f1, dx, G0.x), fmaf(f1, dy, G0.y)), av);
+            s0.x = fmaf(h0.x, x0[i].x, fmaf(-h0.y, x0[i].y, s0.x)); s0.y = fmaf(h0.x, x0[i].y, fmaf(h0.y, x0[i].x, s0.y));
+            s1.x = fmaf(h1.x, x1[i].x, fmaf(-h1.y, x1[i].y, s1.x)); s1.y = fmaf(h1.x, x1[i].y, fmaf(h1.y, x1[i].x, s1.y));
+        } else if (i < (int)T) {
             const float ar = are[i], ai = aim[i];
             s0.x = fmaf(ar, x0[i].x, fmaf(-ai, x0[i].y, s0.x)); s0.y = fmaf(ar, x0[i].y, fmaf(ai, x0[i].x, s0.y));
             s1.x = fmaf(ar, x1[i].x, fmaf(-ai, x1[i].y, s1.x)); s1.y = fmaf(ar, x1[i].y, fmaf(ai, x1[i].x, s1.y));
@@ -111,9 +195,16 @@ struct mcrx_hip_userchan_s {
     uint32_t C = 0, lead = 0;   // channels; the largest delay rounded up to 8
     bool rot = false;           // any channel with a step or a start phase: the rotating build, for every channel
     void *table = nullptr;      // the four planes, one allocation: head[C] | ray01[C] | ray23[C] | osc[C]
+    std::vector<uint8_t> T;     // rays per channel (what mcrx_hip_userfade_set checks a user's entries against)
+    bool fade = false;          // fading on: fplanes holds the sinusoids of every (channel, ray)
+    uint32_t fade_L = 0, fade_S = 0;
+    uint64_t fade_cap = 0;      // the most rows of the gain table a span may use
+    void *fplanes = nullptr;    // one allocation: step[1 + S][4 C] (64-bit) | phase[1 + S][4 C] | coef[4 C]
+    float4 *gtab = nullptr; uint64_t gtab_rows = 0;     // the gain table and the rows allocated (grown on demand, never shrunk)
 };
 
 static const size_t USERCHAN_MAX_GRANULES = (size_t)1 << 28;       // (lanes of a launch and the kernel's 32-bit block arithmetic)
+static const size_t USERFADE_TABLE_BYTES = (size_t)64 << 20;       // the default cap of the gain table: 32 bytes a channel and row
 
 extern "C" const char *mcrx_hip_userchan_last_error(void) { return g_uc_err.c_str(); }
 
@@ -154,6 +245,8 @@ extern "C" int mcrx_hip_userchan_create(mcrx_hip_userchan_t *out, unsigned num_c
     mcrx_hip_userchan_t q = new mcrx_hip_userchan_s();
     q->device = current_device();
     q->C = C; q->lead = (D + 7u) / 8u * 8u; q->rot = rot;
+    q->T.resize(C);
+    for (uint32_t c = 0; c < C; c++) q->T[c] = (uint8_t)ch[c].num_rays;
     hipError_t e = hipMalloc(&q->table, host.size() * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemcpy(q->table, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -171,12 +264,29 @@ extern "C" int mcrx_hip_userchan_destroy(mcrx_hip_userchan_t q)
     if (!q) return MCRX_OK;
     (void)hipDeviceSynchronize();
     if (q->table) (void)hipFree(q->table);
+    if (q->fplanes) (void)hipFree(q->fplanes);
+    if (q->gtab) (void)hipFree(q->gtab);
     delete q;
     return MCRX_OK;
 }
 
 extern "C" unsigned mcrx_hip_userchan_num_channels(mcrx_hip_userchan_t q) { return q ? q->C : 0u; }
 extern "C" unsigned mcrx_hip_userchan_lead_blocks(mcrx_hip_userchan_t q) { return q ? q->lead : 0u; }
+
+// rows of the gain table the blocks at fraction `frac` of a grid interval, n >= 1 of them, read: their own grid rows and the one behind the last
+static uint64_t userfade_rows(uint64_t frac, uint64_t n, uint32_t L) { return ((frac + n - 1) >> L) + 2; }
+
+// table[r][channel][4] = G[first_row + r], r < rows (rows >= 1), on `st`
+static void userfade_launch_gains(mcrx_hip_userchan_t q, long long first_row, uint32_t rows, float2 *table, hipStream_t st)
+{
+    UserfadeGainArgs g;
+    const size_t lanes = (size_t)q->C * MCRX_USERCHAN_MAX_RAYS, terms = q->fade_S + 1;
+    g.step = static_cast<const uint64_t *>(q->fplanes);
+    g.phase = reinterpret_cast<const uint32_t *>(g.step + lanes * terms);
+    g.coef = reinterpret_cast<const float2 *>(g.phase + lanes * terms);
+    g.table = table; g.row0 = first_row; g.rows = rows; g.lanes = (uint32_t)lanes; g.L = q->fade_L; g.S = q->fade_S;
+    hipLaunchKernelGGL(userchan_gain_kernel, dim3((unsigned)(((uint64_t)rows + USERFADE_CHUNK - 1u) / USERFADE_CHUNK), (unsigned)((lanes + 255) / 256)), dim3(256), 0, st, g);
+}
 
 extern "C" int mcrx_hip_userchan_apply_tiles(mcrx_hip_userchan_t q, const void *d_in, long long first_block, size_t nblocks,
                                              size_t lead_blocks, void *d_out, void *stream)
@@ -192,20 +302,161 @@ extern "C" int mcrx_hip_userchan_apply_tiles(mcrx_hip_userchan_t q, const void *
     const size_t bi = (lead_blocks + nblocks) * q->C * sizeof(float2), bo = nblocks * q->C * sizeof(float2);
     if (pi < po + bo && po < pi + bi) { g_uc_err = "d_in and d_out overlap: the rays read behind the write front, in-place use is not possible"; return MCRX_EINVAL; }
     if (nblocks == 0) return MCRX_OK;
-    UserchanArgs a;
-    a.in = static_cast<const float2 *>(d_in); a.out = static_cast<float4 *>(d_out);
+    hipStream_t st = (hipStream_t)stream;
+    UserchanArgs a = {};
     const uint32_t *t = static_cast<const uint32_t *>(q->table);
     a.head = reinterpret_cast<const uint4 *>(t);
     a.ray01 = reinterpret_cast<const float4 *>(t + (size_t)q->C * 4u);
     a.ray23 = reinterpret_cast<const float4 *>(t + (size_t)q->C * 8u);
     a.osc = reinterpret_cast<const uint2 *>(t + (size_t)q->C * 12u);
-    a.C = q->C; a.total = (uint32_t)(nblocks / 8 * q->C * 4u);
+    a.C = q->C;
     a.lead = (uint32_t)lead_blocks;
-    a.first_lo = (uint32_t)(uint64_t)first_block;
-    const dim3 grid((a.total + 255u) / 256u);
-    hipStream_t st = (hipStream_t)stream;
-    if (q->rot) hipLaunchKernelGGL(userchan_kernel<true>, grid, dim3(256), 0, st, a);
-    else        hipLaunchKernelGGL(userchan_kernel<false>, grid, dim3(256), 0, st, a);
+    if (!q->fade) {
+        a.in = static_cast<const float2 *>(d_in); a.out = static_cast<float4 *>(d_out);
+        a.total = (uint32_t)(nblocks / 8 * q->C * 4u);
+        a.first_lo = (uint32_t)(uint64_t)first_block;
+        const dim3 grid((a.total + 255u) / 256u);
+        if (q->rot) hipLaunchKernelGGL((userchan_kernel<true, false>), grid, dim3(256), 0, st, a);
+        else        hipLaunchKernelGGL((userchan_kernel<false, false>), grid, dim3(256), 0, st, a);
+        UCCHK(hipGetLastError());
+        return MCRX_OK;
+    }
+    // fading: spans of at most cap - 1 grid intervals, gain kernel -> main kernel each.  The operator is a function of the absolute
+    // block index, so the spans are invisible in the output; a span ends on a grid row or with the call, both multiples of 8 blocks.
+    const uint32_t L = q->fade_L;
+    const uint64_t mask = ((uint64_t)1 << L) - 1;
+    const uint64_t want = userfade_rows((uint64_t)first_block & mask, nblocks, L);
+    const uint64_t cap = want < q->fade_cap ? want : q->fade_cap;
+    if (cap > q->gtab_rows) {                                           // grow (hipFree waits for the calls in flight); steady state: never
+        const uint64_t twice = 2 * q->gtab_rows < q->fade_cap ? 2 * q->gtab_rows : q->fade_cap;
+        const uint64_t rows = twice > cap ? twice : cap;
+        if (q->gtab) { UCCHK(hipFree(q->gtab)); q->gtab = nullptr; q->gtab_rows = 0; }
+        UCCHK(hipMalloc((void **)&q->gtab, (size_t)rows * q->C * 2u * sizeof(float4)));
+        q->gtab_rows = rows;
+    }
+    a.gtab = q->gtab; a.L = L; a.finv = std::ldexp(1.0f, -(int)L);
+    for (size_t off = 0; off < nblocks; ) {
+        const long long pos = first_block + (long long)off;
+        const uint64_t frac = (uint64_t)pos & mask;
+        const uint64_t avail = ((cap - 1) << L) - frac;
+        const size_t m = nblocks - off < avail ? nblocks - off : (size_t)avail;
+        userfade_launch_gains(q, pos >> L, (uint32_t)userfade_rows(frac, m, L), reinterpret_cast<float2 *>(q->gtab), st);
+        UCCHK(hipGetLastError());
+        a.in = static_cast<const float2 *>(d_in) + off * q->C; a.out = static_cast<float4 *>(d_out) + off * q->C / 2u;
+        a.total = (uint32_t)(m / 8 * q->C * 4u);
+        a.first_lo = (uint32_t)(uint64_t)pos; a.frac0 = (uint32_t)frac;
+        const dim3 grid((a.total + 255u) / 256u);
+        if (q->rot) hipLaunchKernelGGL((userchan_kernel<true, true>), grid, dim3(256), 0, st, a);
+        else        hipLaunchKernelGGL((userchan_kernel<false, true>), grid, dim3(256), 0, st, a);
+        UCCHK(hipGetLastError());
+        off += m;
+    }
+    return MCRX_OK;
+}
+
+// ---- fading rays per user (mcrx_hip_userfade_*) ----
+static const char *userfade_check_config(const mcrx_hip_userfade_config *f)
+{
+    if (f->struct_size != sizeof(mcrx_hip_userfade_config)) return "mcrx_hip_userfade_config: wrong struct_size";
+    if (f->user_struct_size != sizeof(mcrx_hip_userfade_user)) return "mcrx_hip_userfade_user: wrong user_struct_size";
+    if (f->log2_block < MCRX_USERFADE_MIN_LOG2_BLOCK || f->log2_block > MCRX_USERFADE_MAX_LOG2_BLOCK) return "log2_block must be 3 .. 20";
+    if (f->num_sinusoids < 1 || f->num_sinusoids > MCRX_CHANEMU_MAX_SINUSOIDS) return "num_sinusoids must be 1 .. 16";
+    if (f->table_rows == 1) return "table_rows must be 0 (default) or at least 2";
+    return nullptr;
+}
+
+// rays [ray0, ray1) of one user against the update interval (users who do not fade are not looked at)
+static const char *userfade_check_user(const mcrx_hip_userfade_config *f, const mcrx_hip_userfade_user *u, unsigned ray0, unsigned ray1)
+{
+    if (!u->enabled) return nullptr;
+    const double B = (double)(1u << f->log2_block);
+    for (unsigned i = ray0; i < ray1; i++) {
+        if (!std::isfinite(u->doppler[i]) || !std::isfinite(u->los_doppler[i])) return "a Doppler is not finite";
+        if (u->doppler[i] < 0.0) return "doppler must not be negative";
+        if (u->doppler[i] * B > 0.125 || std::fabs(u->los_doppler[i]) * B > 0.125) return "a Doppler times the update interval exceeds 1/8: the grid does not sample the gain";
+        if (!std::isfinite(u->rice_k[i]) || u->rice_k[i] < 0.f) return "rice_k must be finite and not negative";
+    }
+    return nullptr;
+}
+
+// the integers and coefficients of one ray of a checked user: entry 0 the line-of-sight term, then the S scattered sinusoids
+static void userfade_ray(const mcrx_hip_userfade_config *f, const mcrx_hip_userfade_user *u, unsigned i, int64_t *steps, uint32_t *phases, float coef[2])
+{
+    if (!u->enabled) {                                                  // G = (1, 0): the ray as it is without fading
+        for (uint32_t k = 0; k <= f->num_sinusoids; k++) { steps[k] = 0; phases[k] = 0; }
+        coef[0] = 1.f; coef[1] = 0.f;
+        return;
+    }
+    fade_ray_integers(f->seed, i, 2u, u->id, f->num_sinusoids, u->doppler[i], u->los_doppler[i], u->rice_k[i], u->los_phase[i], steps, phases, coef);
+}
+
+extern "C" int mcrx_hip_userfade_selftest(const mcrx_hip_userfade_config *f, const mcrx_hip_userfade_user *u, unsigned ray, int64_t *steps,
+                                          uint32_t *phases, float coef[2])
+{
+    if (!f || !u || !steps || !phases || !coef) { g_uc_err = "null pointer"; return MCRX_EINVAL; }
+    if (ray >= MCRX_USERCHAN_MAX_RAYS) { g_uc_err = "ray must be 0 .. 3"; return MCRX_EINVAL; }
+    const char *bad = userfade_check_config(f);
+    if (!bad) bad = userfade_check_user(f, u, ray, ray + 1);
+    if (bad) { g_uc_err = bad; return MCRX_EINVAL; }
+    userfade_ray(f, u, ray, steps, phases, coef);
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_userfade_on(mcrx_hip_userchan_t q) { return q && q->fade ? 1 : 0; }
+
+extern "C" int mcrx_hip_userfade_set(mcrx_hip_userchan_t q, const mcrx_hip_userfade_config *f, const mcrx_hip_userfade_user *users)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_uc_err = "null handle"; return MCRX_EINVAL; }
+    if (!f) {                                                           // off: the planes and the table go with the handle
+        UCCHK(hipDeviceSynchronize());
+        q->fade = false;
+        return MCRX_OK;
+    }
+    if (!users) { g_uc_err = "null user table"; return MCRX_EINVAL; }
+    const char *bad = userfade_check_config(f);
+    for (uint32_t c = 0; c < q->C && !bad; c++) bad = userfade_check_user(f, &users[c], 0, q->T[c]);
+    if (bad) { g_uc_err = bad; return MCRX_EINVAL; }
+    // the planes on the host: [term][lane], lane = channel * 4 + ray; rays a channel does not have are static ones
+    const uint32_t S = f->num_sinusoids, terms = S + 1;
+    const size_t lanes = (size_t)q->C * MCRX_USERCHAN_MAX_RAYS;
+    const size_t bytes = lanes * terms * (sizeof(uint64_t) + sizeof(uint32_t)) + lanes * sizeof(float2);
+    std::vector<uint64_t> host((bytes + 7) / 8, 0);
+    uint64_t *step = host.data();
+    uint32_t *phase = reinterpret_cast<uint32_t *>(step + lanes * terms);
+    float *coef = reinterpret_cast<float *>(phase + lanes * terms);
+    mcrx_hip_userfade_user none = {};
+    for (uint32_t c = 0; c < q->C; c++)
+        for (uint32_t i = 0; i < MCRX_USERCHAN_MAX_RAYS; i++) {
+            int64_t st[USERFADE_TERMS]; uint32_t ph[USERFADE_TERMS]; float co[2];
+            userfade_ray(f, i < q->T[c] ? &users[c] : &none, i, st, ph, co);
+            const size_t lane = (size_t)c * MCRX_USERCHAN_MAX_RAYS + i;
+            for (uint32_t k = 0; k < terms; k++) { step[k * lanes + lane] = (uint64_t)st[k]; phase[k * lanes + lane] = ph[k]; }
+            coef[lane * 2] = co[0]; coef[lane * 2 + 1] = co[1];
+        }
+    UCCHK(hipDeviceSynchronize());                                      // calls in flight read the planes about to go
+    void *planes = nullptr;
+    UCCHK(hipMalloc(&planes, bytes));
+    hipError_t e = hipMemcpy(planes, host.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(planes); g_uc_err = std::string("fading planes: ") + hipGetErrorString(e); return MCRX_EHIP; }
+    if (q->fplanes) (void)hipFree(q->fplanes);
+    q->fplanes = planes;
+    q->fade_L = f->log2_block; q->fade_S = S;
+    const uint64_t fit = USERFADE_TABLE_BYTES / ((size_t)q->C * 2u * sizeof(float4));
+    q->fade_cap = f->table_rows ? f->table_rows : fit;
+    q->fade = true;
+    return MCRX_OK;
+}
+
+// the gain kernel on its own, into the caller's buffer: what apply_tiles computes for itself, for tests and measurements
+extern "C" int mcrx_hip_userfade_gains(mcrx_hip_userchan_t q, long long first_row, uint32_t rows, void *d_table, void *stream)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_uc_err = "null handle"; return MCRX_EINVAL; }
+    if (!q->fade) { g_uc_err = "fading is off"; return MCRX_EINVAL; }
+    if (!d_table || (reinterpret_cast<uintptr_t>(d_table) & 15u)) { g_uc_err = "d_table must be a 16-byte aligned device buffer"; return MCRX_EINVAL; }
+    if (rows == 0) return MCRX_OK;
+    userfade_launch_gains(q, first_row, rows, static_cast<float2 *>(d_table), (hipStream_t)stream);
     UCCHK(hipGetLastError());
     return MCRX_OK;
 }
