@@ -601,7 +601,8 @@ int      mcrx_hip_chanfade_gains(mcrx_hip_chanemu_t q, uint64_t first_row, uint3
  * lead, gives the one-call output bit for bit.
  * Rotation: when every channel of the handle has cfo_step == 0 && phase0 == 0 the rotation is not computed at all (s_c goes to the gain
  * as it is); otherwise EVERY channel of the handle is rotated, those with a zero step and phase by the oscillator value of phase 0.
- * A user's timing offset is an integer delay added to all of their rays; it has no field of its own.
+ * A user's integer timing offset is a delay added to all of their rays; a fractional one, and a sample clock of their own, are
+ * mcrx_hip_userclock_* below.
  * At most 2^28 granules (tiles * channels) a call. */
 #define MCRX_USERCHAN_MAX_RAYS     4
 #define MCRX_USERCHAN_MAX_DELAY    255      /* channel-rate samples */
@@ -621,7 +622,7 @@ int         mcrx_hip_userchan_create(mcrx_hip_userchan_t *out, unsigned num_chan
                                      size_t struct_size);
 int         mcrx_hip_userchan_destroy(mcrx_hip_userchan_t q);
 unsigned    mcrx_hip_userchan_num_channels(mcrx_hip_userchan_t q);                   /* 0 for a null handle */
-unsigned    mcrx_hip_userchan_lead_blocks(mcrx_hip_userchan_t q);                    /* largest delay rounded up to 8; 0 for a null handle */
+unsigned    mcrx_hip_userchan_lead_blocks(mcrx_hip_userchan_t q);                    /* largest delay rounded up to 8 (with a clock on: see mcrx_hip_userclock_*); 0 for a null handle */
 /* Asynchronous on `stream` (a hipStream_t, NULL = the default stream).  MCRX_EINVAL: a null handle or buffer, a buffer that is not
  * 16-byte aligned, nblocks, lead_blocks or first_block not a multiple of 8, lead_blocks below mcrx_hip_userchan_lead_blocks(), input
  * and output ranges that overlap, more than 2^28 granules. */
@@ -683,6 +684,71 @@ int      mcrx_hip_userfade_selftest(const mcrx_hip_userfade_config *f, const mcr
  * caller's 16-byte aligned device buffer, asynchronously on `stream` (entries of rays a channel does not have are (1, 0)).
  * MCRX_EINVAL with fading off. */
 int      mcrx_hip_userfade_gains(mcrx_hip_userchan_t q, long long first_row, uint32_t rows, void *d_table, void *stream);
+
+/* ---- per-user channel emulator: each user's own sample clock and fractional timing ----
+ * A user's radio has one oscillator: the error that moves their carrier (cfo_step) also moves their sample clock.  With a clock on,
+ * local channel c transmits z_c[b] = x_c(b - tau_c(b)) instead of x_c[b], IN FRONT of their multipath, and the operator above runs
+ * on z unchanged (rays, fading gains, rotation, gain):  s_c[b] = sum_i (g_ci(b)) a_ci z_c[b - d_ci].
+ * The delay is a straight line in the ABSOLUTE output block index b (signed 64-bit), all in integers:
+ *     tau_fp_c(b) = delay_fp_c + floor( sco_c * (b - origin_c) / 2^16 )        Q32 samples, int64 (an arithmetic shift: floor)
+ *     n  = tau_fp >> 32          whole samples
+ *     mu = tau_fp & 0xffffffff   fraction
+ *   delay_fp: the delay at b = origin in units of 2^-32 samples; sco: signed, units of 2^-48 samples per sample (1 ppm = 281 474 977),
+ *   |sco| <= 2^38 (about 977 ppm); origin: a signed 64-bit block index.
+ * z is interpolated by a 32-tap polyphase filter of 64 phases with linear interpolation between phases (part of the definition, as
+ * the fading gains' is of theirs), in fp32, summed in the order j = 0 .. 31 from zero with one fused multiply-add per tap and component:
+ *     z_c[b]  = sum_{j<32} h_j(mu) x_c[b - n + 15 - j]                          z is ROUNDED TO fp32 here
+ *     h_j(mu) = fmaf(f, W[r+1][j] - W[r][j], W[r][j])                           r = mu >> 26, f = ((mu >> 2) & 0xffffff) 2^-24 (exact)
+ *     W[p][j] = fp32( sinc(t) I0(6.0 sqrt(1 - (t/16)^2)) / I0(6.0) ),  t = j - 15 - p/64,  p = 0 .. 64, computed in double; rows 0 and
+ *               64 are set to the exact unit vectors (tap 15, tap 16); mcrx_hip_userclock_table reports W.
+ * The taps reach 15 samples ahead of b - n, so n >= MCRX_USERCLOCK_MIN_DELAY on every block of a call, and n <= the configured
+ * max_delay (15 .. 255).  tau is linear over a call, so the host checks the two ends -- blocks first_block - D and first_block +
+ * nblocks - 1, D the handle's largest ray delay (0 for mcrx_hip_userclock_apply_tiles) -- and refuses the call with MCRX_EINVAL,
+ * before anything is launched and with a message naming the channel, when a clocked user's n leaves [15, max_delay] there or when
+ * sco * (b - origin) leaves int64.  This is the documented limit: all users' traffic comes on one block grid, so a drift can use up
+ * only the room max_delay gives it (at 20 ppm, 200 samples of room are 10^7 blocks); a longer run moves origin, which is a timing
+ * jump, as a real user's re-synchronisation is.  A user with enabled == 0 has z = x, bit for bit.
+ * Lead: with a clock on mcrx_hip_userchan_lead_blocks() is the largest ray delay + max_delay + 16 rounded up to 8, and
+ * mcrx_hip_userclock_lead_blocks() is max_delay + 16 rounded up to 8 (the stage alone); with the clock off the first is as above and
+ * the second 0.  Cuts, leads, spans and channel shards stay invisible bit for bit; with the clock off (a new handle, and after a
+ * NULL) the operator is the one described above, word for word, and launches the same kernels.
+ * The handle keeps z of a span in a scratch buffer of its own, grown on demand to span_blocks blocks (0: what fits 64 MiB for the
+ * handle's channel count; else a multiple of 8) plus the rays' lead; a longer call runs as consecutive spans on the caller's stream,
+ * which changes no bit.  Because of that buffer, calls of mcrx_hip_userchan_apply_tiles on ONE clocked handle must be ordered on the
+ * device (one stream, or events of the caller's), as on a fading handle.  (A prefix of its own: the emulator's set of entry points
+ * is closed.  Errors are read with mcrx_hip_userchan_last_error.) */
+#define MCRX_USERCLOCK_TAPS      32
+#define MCRX_USERCLOCK_PHASES    64
+#define MCRX_USERCLOCK_MIN_DELAY 15
+#define MCRX_USERCLOCK_MAX_DELAY 255
+typedef struct {
+    uint32_t enabled, reserved;     /* 0: this user has no clock of their own, z = x (the rest is not looked at) */
+    uint64_t delay_fp;              /* 2^-32 samples, at b = origin */
+    int64_t  sco, origin;           /* 2^-48 samples per sample, |sco| <= 2^38; a block index */
+} mcrx_hip_userclock_user;          /* 32 bytes */
+typedef struct {
+    uint32_t struct_size, user_struct_size;     /* sizeof(mcrx_hip_userclock_config), sizeof(mcrx_hip_userclock_user) */
+    uint32_t max_delay;                         /* 15 .. 255: the most whole samples of delay any block may have */
+    uint32_t span_blocks;                       /* 0 = default, else a multiple of 8 */
+} mcrx_hip_userclock_config;
+/* users[num_channels of the handle]; cfg == NULL: the clock off (users is not looked at).  Waits for the device before the handle's
+ * tables change.  MCRX_EINVAL, before any device work and with the handle left as it was: a null handle, a null users with cfg
+ * given, wrong struct sizes, max_delay outside 15 .. 255, a span_blocks that is not a multiple of 8, and for an enabled user
+ * |sco| > 2^38 or a delay_fp whose n lies outside [15, max_delay]. */
+int      mcrx_hip_userclock_set(mcrx_hip_userchan_t q, const mcrx_hip_userclock_config *cfg, const mcrx_hip_userclock_user *users);
+int      mcrx_hip_userclock_on(mcrx_hip_userchan_t q);                               /* 1 with a clock on; 0 for a null handle */
+unsigned mcrx_hip_userclock_lead_blocks(mcrx_hip_userchan_t q);                      /* max_delay + 16 rounded up to 8; 0 with the clock off */
+/* host, no GPU: the integer delay tau_fp and the 32 interpolated coefficients h_j this user's block `block` gets.  Checks cfg and user
+ * as set does, and the block as a call does (n outside [15, max_delay] there, a product beyond int64: MCRX_EINVAL, nothing written).
+ * A user with enabled == 0 gets tau_fp = 0 and the unit vector of tap 15. */
+int      mcrx_hip_userclock_selftest(const mcrx_hip_userclock_config *cfg, const mcrx_hip_userclock_user *user, long long block,
+                                     int64_t *tau_fp, float h[MCRX_USERCLOCK_TAPS]);
+int      mcrx_hip_userclock_table(float W[(MCRX_USERCLOCK_PHASES + 1) * MCRX_USERCLOCK_TAPS]);      /* host: W[p][j] */
+/* The clock stage on its own, for tests and measurements: z of blocks [first_block, first_block + nblocks) in the tiles' layout into
+ * d_out, from d_in holding blocks [first_block - lead_blocks, first_block + nblocks); lead_blocks >= mcrx_hip_userclock_lead_blocks();
+ * alignment, granules, overlap and size rules as for mcrx_hip_userchan_apply_tiles.  MCRX_EINVAL with the clock off. */
+int      mcrx_hip_userclock_apply_tiles(mcrx_hip_userchan_t q, const void *d_in, long long first_block, size_t nblocks,
+                                        size_t lead_blocks, void *d_out, void *stream);
 
 #ifdef __cplusplus
 }

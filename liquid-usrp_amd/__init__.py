@@ -193,6 +193,12 @@ _EXPORTS = {
     "mcrx_hip_userfade_selftest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_int64), C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_float)]),
     "mcrx_hip_userfade_gains": (C.c_int, [C.c_void_p, C.c_longlong, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_userclock_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_userclock_on": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_userclock_lead_blocks": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_userclock_selftest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_int64), C.POINTER(C.c_float)]),
+    "mcrx_hip_userclock_table": (C.c_int, [C.POINTER(C.c_float)]),
+    "mcrx_hip_userclock_apply_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -1022,6 +1028,66 @@ def userchan_fading(rays, log2_block=4, sinusoids=16, seed=0, table_rows=0, user
     return f, table
 
 
+USERCLOCK_TAPS, USERCLOCK_PHASES, USERCLOCK_MIN_DELAY, USERCLOCK_MAX_DELAY = 32, 64, 15, 255     # MCRX_USERCLOCK_*
+USERCLOCK_MAX_SCO = 1 << 38       # |sco|, 2^-48 samples per sample: about 977 ppm
+
+
+class UserclockUser(C.Structure):
+    _fields_ = [("enabled", C.c_uint32), ("reserved", C.c_uint32), ("delay_fp", C.c_uint64), ("sco", C.c_int64), ("origin", C.c_int64)]
+
+
+class UserclockConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("user_struct_size", C.c_uint32), ("max_delay", C.c_uint32), ("span_blocks", C.c_uint32)]
+
+
+_USERCLOCK_KEYS = ("max_delay", "span_blocks", "users")
+_USERCLOCK_USER_KEYS = ("delay", "ppm", "origin")
+
+
+def userclock_user(max_delay, delay, ppm=0.0, origin=0):
+    """The mcrx_hip_userclock_user structure of one user with a clock of their own: delay_fp = rint(delay * 2^32) (delay in channel-rate
+    samples at block `origin`, its whole part 15 .. max_delay), sco = rint(ppm * 1e-6 * 2^48).  ValueError for what the library refuses."""
+    delay, ppm = float(delay), float(ppm)
+    if not (math.isfinite(delay) and math.isfinite(ppm)):
+        raise ValueError("clock: delay and ppm must be finite")
+    dfp, sco = int(np.rint(delay * 4294967296.0)), int(np.rint(ppm * 1e-6 * 281474976710656.0))
+    if not USERCLOCK_MIN_DELAY <= (dfp >> 32) <= int(max_delay):
+        raise ValueError("clock: the whole samples of a delay are %d .. max_delay (%d)" % (USERCLOCK_MIN_DELAY, int(max_delay)))
+    if abs(sco) > USERCLOCK_MAX_SCO:
+        raise ValueError("clock: |ppm| is at most 2^38 * 2^-48 * 1e6, about 976.56")
+    if int(origin) != origin or not -(1 << 63) <= int(origin) < (1 << 63):
+        raise ValueError("clock: origin is a signed 64-bit block index")
+    u = UserclockUser()
+    u.enabled, u.delay_fp, u.sco, u.origin = 1, dfp, sco, int(origin)
+    return u
+
+
+def userchan_clock(num_channels, max_delay=64, span_blocks=0, users=None):
+    """(mcrx_hip_userclock_config, mcrx_hip_userclock_user[num_channels]) of a clock description: users[c] is None (that user keeps the
+    receiver's clock: z = x), a dict(delay, ppm=0.0, origin=0) or a UserclockUser."""
+    if int(max_delay) != max_delay or not USERCLOCK_MIN_DELAY <= int(max_delay) <= USERCLOCK_MAX_DELAY:
+        raise ValueError("clock: max_delay must be %d .. %d" % (USERCLOCK_MIN_DELAY, USERCLOCK_MAX_DELAY))
+    if int(span_blocks) != span_blocks or int(span_blocks) % 8 or not 0 <= int(span_blocks) < (1 << 32):
+        raise ValueError("clock: span_blocks must be 0 (default) or a multiple of 8 below 2^32")
+    users = list(users) if users is not None else []
+    if len(users) != num_channels:
+        raise ValueError("clock: users has %d entries for %d channels" % (len(users), num_channels))
+    f = UserclockConfig()
+    f.struct_size, f.user_struct_size = C.sizeof(UserclockConfig), C.sizeof(UserclockUser)
+    f.max_delay, f.span_blocks = int(max_delay), int(span_blocks)
+    table = (UserclockUser * num_channels)()
+    for c, u in enumerate(users):
+        if u is None:
+            continue
+        if isinstance(u, UserclockUser):
+            table[c] = u
+        elif isinstance(u, dict) and "delay" in u and all(k in _USERCLOCK_USER_KEYS for k in u):
+            table[c] = userclock_user(f.max_delay, **u)
+        else:
+            raise ValueError("clock: a user is None or a dict with 'delay' and keys of %s" % (_USERCLOCK_USER_KEYS,))
+    return f, table
+
+
 class userchan(object):
     """Per-user channel emulator on the transmitter's channel tiles, between TxTraffic.tiles and multichanneltx.synthesize
     (mcrx_hip_userchan_*): every channel has its own multipath, oscillator, timing and level, at the channel rate.
@@ -1038,11 +1104,18 @@ class userchan(object):
     channel, None for a user who does not fade; Dopplers in cycles per channel-rate sample (userchan_doppler), each of doppler, rice_k,
     los_doppler, los_phase one value or one per ray; the gains are updated every 2^log2_block blocks (3 .. 20) and interpolated
     linearly between.  A user's gains follow from the seed and their id (default: their index), which shard() keeps.  Calls on a
-    fading handle share its gain table: keep them ordered on the device (one stream, or events)."""
+    fading handle share its gain table: keep them ordered on the device (one stream, or events).
 
-    def __init__(self, channels, fading=None):
+    clock=dict(max_delay=64, span_blocks=0, users=[None | dict(delay=16.25, ppm=20.0, origin=0), ...]) gives the users named a sample
+    clock and a fractional timing of their own (mcrx_hip_userclock_*), in front of their multipath: they transmit x(b - tau(b)) with
+    tau = delay + ppm 1e-6 (b - origin) channel-rate samples, interpolated by 32 taps; the whole samples of tau must stay within
+    15 .. max_delay on every block of a call (a call that leaves the range is refused), and lead_blocks grows by max_delay + 16.
+    None for a user on the receiver's clock.  Calls on a clocked handle share its scratch buffer: keep them ordered on the device."""
+
+    def __init__(self, channels, fading=None, clock=None):
         self._h = C.c_void_p()
         self._fading = None
+        self._clock = None
         chans = []
         for ch in channels:
             if isinstance(ch, UserchanChannel):
@@ -1055,12 +1128,15 @@ class userchan(object):
             raise ValueError("1 .. %d channels a handle" % USERCHAN_MAX_CHANNELS)
         self._table = (UserchanChannel * len(chans))(*chans)
         fading = self._fading_structs(fading)
+        clock = self._clock_structs(clock)
         rc = lib().mcrx_hip_userchan_create(C.byref(self._h), len(chans), C.addressof(self._table), C.sizeof(UserchanChannel))
         if rc != MCRX_OK:
             self._h = C.c_void_p()
             self._chk(rc, "mcrx_hip_userchan_create")
         if fading is not None:
             self._set_fading(fading)
+        if clock is not None:
+            self._set_clock(clock)
 
     @staticmethod
     def _chk(rc, name):
@@ -1088,6 +1164,39 @@ class userchan(object):
     def fading_on(self):
         return bool(lib().mcrx_hip_userfade_on(self._h))
 
+    def _clock_structs(self, clock):
+        if clock is None:
+            return None
+        if not isinstance(clock, dict) or any(k not in _USERCLOCK_KEYS for k in clock):
+            raise ValueError("clock is None or a dict with keys of %s" % (_USERCLOCK_KEYS,))
+        return userchan_clock(len(self._table), **clock)
+
+    def _set_clock(self, structs):
+        if structs is None:
+            self._chk(lib().mcrx_hip_userclock_set(self._h, None, None), "mcrx_hip_userclock_set")
+        else:
+            self._chk(lib().mcrx_hip_userclock_set(self._h, C.addressof(structs[0]), C.addressof(structs[1])), "mcrx_hip_userclock_set")
+        self._clock = structs
+
+    def set_clock(self, clock):
+        """None: every user on the receiver's clock again (the present kernels, the present lead); a dict as at construction: these
+        clocks.  Waits for the device before the handle's tables change."""
+        self._set_clock(self._clock_structs(clock))
+
+    def clock_on(self):
+        return bool(lib().mcrx_hip_userclock_on(self._h))
+
+    @property
+    def clock_lead_blocks(self):
+        """blocks resample() needs in front of its output's first: max_delay + 16 rounded up to 8 (0 with the clock off)"""
+        return int(lib().mcrx_hip_userclock_lead_blocks(self._h))
+
+    def resample(self, tiles, first_block, nblocks, lead_blocks=None, out=None, stream=None):
+        """The clock stage alone: z of blocks [first_block, first_block + nblocks) -- what the users transmit, in front of their rays --
+        from tiles as apply() takes them, with lead_blocks (default: clock_lead_blocks) blocks in front.  For tests and measurements."""
+        return self._on_tiles(lib().mcrx_hip_userclock_apply_tiles, "mcrx_hip_userclock_apply_tiles",
+                              self.clock_lead_blocks if lead_blocks is None else int(lead_blocks), tiles, first_block, nblocks, out, stream)
+
     def gains(self, first_row, rows, stream=None):
         """The gain table's rows first_row .. first_row + rows - 1 (grid row = block >> log2_block, signed) as a complex64 CUDA tensor
         [rows, num_channels, 4]: what apply() interpolates between; entries of rays a channel does not have, and of users who do not
@@ -1106,7 +1215,8 @@ class userchan(object):
 
     @property
     def lead_blocks(self):
-        """blocks apply() needs in front of its output's first: the largest delay rounded up to 8"""
+        """blocks apply() needs in front of its output's first: the largest delay rounded up to 8; with a clock on the largest delay +
+        max_delay + 16, rounded up to 8"""
         return int(lib().mcrx_hip_userchan_lead_blocks(self._h))
 
     def shard(self, first, count):
@@ -1119,16 +1229,23 @@ class userchan(object):
             f, users = self._fading
             fading = dict(log2_block=f.log2_block, sinusoids=f.num_sinusoids, seed=f.seed, table_rows=f.table_rows,
                           users=[users[c] for c in sel])
-        return userchan([self._table[c] for c in sel], fading=fading)
+        clock = None
+        if self._clock is not None:           # ... and their clocks
+            f, users = self._clock
+            clock = dict(max_delay=f.max_delay, span_blocks=f.span_blocks, users=[users[c] for c in sel])
+        return userchan([self._table[c] for c in sel], fading=fading, clock=clock)
 
     def apply(self, tiles, first_block, nblocks, lead_blocks=None, out=None, stream=None):
         """tiles: granules [tile][channel][8] of blocks [first_block - lead_blocks, first_block + nblocks), a contiguous torch complex64
         CUDA tensor (TxTraffic.tiles' layout for this handle's channels); lead_blocks defaults to the handle's.  Returns the granules
         of blocks [first_block, first_block + nblocks) -- in `out` when given, which must not overlap `tiles`.  Asynchronous on
         `stream` (default: torch's current stream of the tiles' device)."""
+        return self._on_tiles(lib().mcrx_hip_userchan_apply_tiles, "mcrx_hip_userchan_apply_tiles",
+                              self.lead_blocks if lead_blocks is None else int(lead_blocks), tiles, first_block, nblocks, out, stream)
+
+    def _on_tiles(self, fn, name, lead, tiles, first_block, nblocks, out, stream):
         import torch
         C_ = len(self._table)
-        lead = self.lead_blocks if lead_blocks is None else int(lead_blocks)
         nblocks = int(nblocks)
         if nblocks < 0 or lead < 0:
             raise ValueError("block counts are not negative")
@@ -1144,8 +1261,7 @@ class userchan(object):
         if nblocks:              # (an empty tensor has no address to pass)
             if stream is None:
                 stream = torch.cuda.current_stream(tiles.device)
-            self._chk(lib().mcrx_hip_userchan_apply_tiles(self._h, _dptr(tiles), int(first_block), nblocks, lead, _dptr(out),
-                                                          _stream_ptr(stream)), "mcrx_hip_userchan_apply_tiles")
+            self._chk(fn(self._h, _dptr(tiles), int(first_block), nblocks, lead, _dptr(out), _stream_ptr(stream)), name)
         return out.view(-1)[:nblocks * C_]
 
     def generate(self, tx, frames_per_channel, payload_len, mod=LIQUID_MODEM_QPSK, fec0=LIQUID_FEC_NONE, fec1=LIQUID_FEC_HAMMING128,

@@ -31,11 +31,21 @@
 // ([term][channel * 4 + ray]) and stores 512 contiguous bytes a row.  userchan_kernel<ROT, FADE = true> reads two rows per granule
 // (L >= 3: a granule never straddles a row), one 16-byte word for rays 0, 1 and one for rays 2, 3 of each.
 //
+// With a clock on (mcrx_hip_userclock_*) the user transmits z_c[b] = x_c(b - tau_c(b)) instead of x_c[b], in front
+// of all of the above: tau_fp(b) = delay_fp + floor(sco (b - origin) / 2^16) in Q32 samples (int64), n = tau_fp >> 32, mu its low word,
+//   z_c[b]  = sum_{j<32} h_j(mu) x_c[b - n + 15 - j]          j = 0 .. 31 from zero, one fmaf per tap and component; z is fp32
+//   h_j(mu) = fmaf(f, W[r+1][j] - W[r][j], W[r][j])           r = mu >> 26, f = ((mu >> 2) & 0xffffff) 2^-24
+// userclock_kernel writes z of a span into the handle's scratch buffer, in the tiles' layout, and userchan_kernel runs on that.  A
+// workgroup takes 16 adjacent channels x 128 output blocks: it stages the 21 tile rows each of its channels needs (its own window: n is
+// per channel) and W in LDS, then a wave walks four tiles with userchan_kernel's lane layout -- lane = (channel, sample pair) -- and
+// stores 1 KB a tile.
+//
 // Contraction is switched off for this file: sincos_u32's polynomials and everything else round the same way in both builds and in every
 // inlined copy, and the products that matter are written as fmaf.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <cstring>
 #include <stdint.h>
 #include <string>
 #include <vector>
@@ -43,6 +53,7 @@
 #include "devmath.h"
 #include "devscope.hpp"
 #include "fadegen.hpp"
+#include "design.hpp"
 
 namespace mcrx {
 
@@ -183,6 +194,94 @@ __global__ __launch_bounds__(256) void userchan_kernel(UserchanArgs a)
     a.out[g] = make_float4(gain * s0.x, gain * s0.y, gain * s1.x, gain * s1.y);
 }
 
+#define UCLK_BLOCKS 128u                    // output blocks a workgroup takes
+#define UCLK_CH     16u                     // adjacent channels a workgroup takes: a wave is 16 channels x 4 sample pairs, as in userchan_kernel
+#define UCLK_ROWS   21u                     // tile rows staged per channel: 128 + 31 samples, one step of n and 7 of alignment are 167 <= 168
+#define UCLK_XS     (UCLK_ROWS * 8u + 2u)   // samples a channel's window takes in LDS (16-byte aligned rows, off the power of two)
+#define UCLK_WS     (MCRX_USERCLOCK_TAPS + 1u)      // a row of W in LDS: lanes of different phases r read different banks
+
+struct UserclockArgs {
+    const float2 *in; float4 *out;
+    const uint4 *par;               // [C][2]: delay_fp, sco / origin, enabled (a user without a clock: 15 << 32, 0 / 0, 0)
+    const float *W;                 // [65][32]
+    long long first;                // the output's first absolute block index
+    uint32_t C, tiles;              // channels; tiles of the output
+    uint32_t lead;                  // blocks the input holds in front of the output's first
+    uint32_t in_rows;               // tile rows the input holds: lead / 8 + tiles
+    uint32_t skip;                  // output blocks below this one are written as zeros and read nothing
+};
+
+// h_j(mu) from the two rows of W around the fraction: the definition's one fused multiply-add, the same on the host and on the device
+__host__ __device__ __forceinline__ float userclock_coef(float w0, float w1, float f) { return fmaf(f, w1 - w0, w0); }
+// tau_fp(b): the product wraps where the host has not checked it (blocks below `skip` never get here)
+__host__ __device__ __forceinline__ int64_t userclock_tau(int64_t delay_fp, int64_t sco, int64_t origin, int64_t b)
+{
+    return delay_fp + ((int64_t)((uint64_t)sco * (uint64_t)(b - origin)) >> 16);
+}
+
+// blockIdx.x: 128 output blocks; blockIdx.y: 16 channels
+__global__ __launch_bounds__(256) void userclock_kernel(UserclockArgs a)
+{
+    __shared__ float sW[(MCRX_USERCLOCK_PHASES + 1) * UCLK_WS];
+    __shared__ __attribute__((aligned(16))) float2 sX[UCLK_CH * UCLK_XS];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    for (uint32_t i = t; i < (MCRX_USERCLOCK_PHASES + 1) * MCRX_USERCLOCK_TAPS; i += 256u) sW[(i >> 5) * UCLK_WS + (i & 31u)] = a.W[i];
+    const uint32_t cl = lane >> 2, q = lane & 3u, c = blockIdx.y * UCLK_CH + cl;
+    const uint32_t m0 = blockIdx.x * UCLK_BLOCKS, left = a.tiles * 8u - m0;        // (the grid: m0 < tiles * 8 <= 2^31)
+    const uint32_t nb = left < UCLK_BLOCKS ? left : UCLK_BLOCKS;
+    const uint32_t ma = m0 > a.skip ? m0 : a.skip, mb = m0 + nb - 1u;               // the blocks computed here: [ma, mb], none when ma > mb
+    const bool live = c < a.C && ma <= mb;
+    int64_t dfp = 0, sco = 0, org = 0, base = 0;                                    // base: the input block (of its own range) at sX[.][0]
+    bool on = false;
+    if (live) {
+        const uint4 p0 = a.par[2u * c], p1 = a.par[2u * c + 1u];
+        dfp = (int64_t)(((uint64_t)p0.y << 32) | p0.x); sco = (int64_t)(((uint64_t)p0.w << 32) | p0.z);
+        org = (int64_t)(((uint64_t)p1.y << 32) | p1.x); on = p1.z != 0u;
+        // tau is a straight line: the largest n of the workgroup's blocks is at one of its ends, and the smallest at most one below
+        const int64_t na = userclock_tau(dfp, sco, org, a.first + ma) >> 32, nz = userclock_tau(dfp, sco, org, a.first + mb) >> 32;
+        const int64_t lo = (int64_t)a.lead + ma - (na > nz ? na : nz) - 16;         // the first sample any of them reads
+        base = (lo >> 3) * 8;                                                       // (floor: rows in front of the input are not loaded)
+    }
+    // the window: tile rows base / 8 .. + 20 of this lane's channel, 16 bytes a lane -- four lanes a granule, as the output's
+    for (uint32_t row = wave; row < UCLK_ROWS; row += 4u) {
+        const int64_t gr = (base >> 3) + row;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live && gr >= 0 && gr < (int64_t)a.in_rows) v = *reinterpret_cast<const float4 *>(a.in + ((size_t)gr * a.C + c) * 8u + q * 2u);
+        *reinterpret_cast<float4 *>(&sX[cl * UCLK_XS + row * 8u + q * 2u]) = v;
+    }
+    __syncthreads();
+    if (c >= a.C) return;
+    const float2 *xw = sX + cl * UCLK_XS;
+    for (uint32_t i = 0; i < 4u; i++) {
+        const uint32_t m = m0 + (wave * 4u + i) * 8u + q * 2u;                      // the pair's first block
+        if (m > mb) break;
+        float2 z[2];
+#pragma unroll
+        for (uint32_t s = 0; s < 2u; s++) {
+            const uint32_t ms = m + s;
+            z[s] = make_float2(0.f, 0.f);
+            if (ms < a.skip) continue;
+            if (!on) { z[s] = xw[(int64_t)a.lead + ms - base]; continue; }           // z = x, bit for bit (the window lies as for n = 15)
+            const int64_t tau = userclock_tau(dfp, sco, org, a.first + ms);
+            const uint32_t mu = (uint32_t)(uint64_t)tau, r = mu >> 26;
+            const float f = (float)((mu >> 2) & 0xffffffu) * 0x1p-24f;
+            int64_t p = (int64_t)a.lead + ms - (tau >> 32) + 15 - base;             // tap 0's sample; 31 <= p < 168 by the choice of base
+            p = p < 31 ? 31 : (p > (int64_t)UCLK_XS - 1 ? (int64_t)UCLK_XS - 1 : p);   // (held there whatever the integers are)
+            const float *w0 = sW + r * UCLK_WS, *w1 = w0 + UCLK_WS;
+            const float2 *x = xw + p;
+            float zr = 0.f, zi = 0.f;
+#pragma unroll
+            for (int j = 0; j < MCRX_USERCLOCK_TAPS; j++) {
+                const float h = userclock_coef(w0[j], w1[j], f);
+                const float2 v = x[-j];
+                zr = fmaf(h, v.x, zr); zi = fmaf(h, v.y, zi);
+            }
+            z[s] = make_float2(zr, zi);
+        }
+        a.out[((size_t)(m >> 3) * a.C + c) * 4u + q] = make_float4(z[0].x, z[0].y, z[1].x, z[1].y);
+    }
+}
+
 }  // namespace mcrx
 
 using namespace mcrx;
@@ -193,6 +292,7 @@ static thread_local std::string g_uc_err;
 struct mcrx_hip_userchan_s {
     int device = -1;            // the HIP device the handle was created on: every entry point runs with it current (devscope.hpp)
     uint32_t C = 0, lead = 0;   // channels; the largest delay rounded up to 8
+    uint32_t D = 0;             // the largest delay itself
     bool rot = false;           // any channel with a step or a start phase: the rotating build, for every channel
     void *table = nullptr;      // the four planes, one allocation: head[C] | ray01[C] | ray23[C] | osc[C]
     std::vector<uint8_t> T;     // rays per channel (what mcrx_hip_userfade_set checks a user's entries against)
@@ -201,10 +301,18 @@ struct mcrx_hip_userchan_s {
     uint64_t fade_cap = 0;      // the most rows of the gain table a span may use
     void *fplanes = nullptr;    // one allocation: step[1 + S][4 C] (64-bit) | phase[1 + S][4 C] | coef[4 C]
     float4 *gtab = nullptr; uint64_t gtab_rows = 0;     // the gain table and the rows allocated (grown on demand, never shrunk)
+    bool clock = false;         // a clock on: cplanes holds every user's integers and W
+    uint32_t clk_max = 0;       // the configured max_delay
+    uint64_t clk_span = 0;      // the most blocks of z a span computes (a multiple of 8)
+    std::vector<mcrx_hip_userclock_user> clk_users;     // what a call's two ends are checked against
+    void *cplanes = nullptr;    // one allocation: par[C][2] (16-byte words) | W[65][32]
+    float2 *zbuf = nullptr; uint64_t zbuf_blocks = 0;   // z of a span, in the tiles' layout, and the blocks allocated (grown on demand)
 };
 
 static const size_t USERCHAN_MAX_GRANULES = (size_t)1 << 28;       // (lanes of a launch and the kernel's 32-bit block arithmetic)
 static const size_t USERFADE_TABLE_BYTES = (size_t)64 << 20;       // the default cap of the gain table: 32 bytes a channel and row
+static const size_t USERCLOCK_SPAN_BYTES = (size_t)64 << 20;       // the default cap of a span's z: 8 bytes a channel and block
+static inline uint32_t round_up8(uint32_t v) { return (v + 7u) / 8u * 8u; }
 
 extern "C" const char *mcrx_hip_userchan_last_error(void) { return g_uc_err.c_str(); }
 
@@ -244,7 +352,7 @@ extern "C" int mcrx_hip_userchan_create(mcrx_hip_userchan_t *out, unsigned num_c
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { g_uc_err = "no HIP device (no CPU fallback)"; return MCRX_EHIP; }
     mcrx_hip_userchan_t q = new mcrx_hip_userchan_s();
     q->device = current_device();
-    q->C = C; q->lead = (D + 7u) / 8u * 8u; q->rot = rot;
+    q->C = C; q->D = D; q->lead = round_up8(D); q->rot = rot;
     q->T.resize(C);
     for (uint32_t c = 0; c < C; c++) q->T[c] = (uint8_t)ch[c].num_rays;
     hipError_t e = hipMalloc(&q->table, host.size() * sizeof(uint32_t));
@@ -266,12 +374,19 @@ extern "C" int mcrx_hip_userchan_destroy(mcrx_hip_userchan_t q)
     if (q->table) (void)hipFree(q->table);
     if (q->fplanes) (void)hipFree(q->fplanes);
     if (q->gtab) (void)hipFree(q->gtab);
+    if (q->cplanes) (void)hipFree(q->cplanes);
+    if (q->zbuf) (void)hipFree(q->zbuf);
     delete q;
     return MCRX_OK;
 }
 
 extern "C" unsigned mcrx_hip_userchan_num_channels(mcrx_hip_userchan_t q) { return q ? q->C : 0u; }
-extern "C" unsigned mcrx_hip_userchan_lead_blocks(mcrx_hip_userchan_t q) { return q ? q->lead : 0u; }
+extern "C" unsigned mcrx_hip_userclock_lead_blocks(mcrx_hip_userchan_t q) { return q && q->clock ? round_up8(q->clk_max + 16u) : 0u; }
+extern "C" unsigned mcrx_hip_userchan_lead_blocks(mcrx_hip_userchan_t q)
+{
+    if (!q) return 0u;
+    return q->clock ? round_up8(q->D + q->clk_max + 16u) : q->lead;
+}
 
 // rows of the gain table the blocks at fraction `frac` of a grid interval, n >= 1 of them, read: their own grid rows and the one behind the last
 static uint64_t userfade_rows(uint64_t frac, uint64_t n, uint32_t L) { return ((frac + n - 1) >> L) + 2; }
@@ -288,21 +403,24 @@ static void userfade_launch_gains(mcrx_hip_userchan_t q, long long first_row, ui
     hipLaunchKernelGGL(userchan_gain_kernel, dim3((unsigned)(((uint64_t)rows + USERFADE_CHUNK - 1u) / USERFADE_CHUNK), (unsigned)((lanes + 255) / 256)), dim3(256), 0, st, g);
 }
 
-extern "C" int mcrx_hip_userchan_apply_tiles(mcrx_hip_userchan_t q, const void *d_in, long long first_block, size_t nblocks,
-                                             size_t lead_blocks, void *d_out, void *stream)
+// what every call on tiles is checked for (q not null); need_lead / lead_what: the least lead and the message below it
+static const char *userchan_check_call(mcrx_hip_userchan_t q, const void *d_in, long long first_block, size_t nblocks, size_t lead_blocks,
+                                       const void *d_out, size_t need_lead, const char *lead_what)
 {
-    DevScope dev_scope_(q ? q->device : -1);
-    if (!q) { g_uc_err = "null handle"; return MCRX_EINVAL; }
-    if (!d_in || !d_out) { g_uc_err = "null buffer"; return MCRX_EINVAL; }
+    if (!d_in || !d_out) return "null buffer";
     const uintptr_t pi = reinterpret_cast<uintptr_t>(d_in), po = reinterpret_cast<uintptr_t>(d_out);
-    if ((pi & 15u) || (po & 15u)) { g_uc_err = "d_in and d_out must be 16-byte aligned"; return MCRX_EINVAL; }
-    if ((nblocks % 8) || (lead_blocks % 8) || (first_block % 8)) { g_uc_err = "nblocks, lead_blocks and first_block come in granules of 8 blocks"; return MCRX_EINVAL; }
-    if (lead_blocks < q->lead) { g_uc_err = "lead_blocks is below the handle's largest delay rounded up to 8 (mcrx_hip_userchan_lead_blocks)"; return MCRX_EINVAL; }
-    if (nblocks / 8 > USERCHAN_MAX_GRANULES / q->C || lead_blocks > ((size_t)1 << 30)) { g_uc_err = "at most 2^28 granules a call (and 2^30 blocks of lead)"; return MCRX_EINVAL; }
+    if ((pi & 15u) || (po & 15u)) return "d_in and d_out must be 16-byte aligned";
+    if ((nblocks % 8) || (lead_blocks % 8) || (first_block % 8)) return "nblocks, lead_blocks and first_block come in granules of 8 blocks";
+    if (lead_blocks < need_lead) return lead_what;
+    if (nblocks / 8 > USERCHAN_MAX_GRANULES / q->C || lead_blocks > ((size_t)1 << 30)) return "at most 2^28 granules a call (and 2^30 blocks of lead)";
     const size_t bi = (lead_blocks + nblocks) * q->C * sizeof(float2), bo = nblocks * q->C * sizeof(float2);
-    if (pi < po + bo && po < pi + bi) { g_uc_err = "d_in and d_out overlap: the rays read behind the write front, in-place use is not possible"; return MCRX_EINVAL; }
-    if (nblocks == 0) return MCRX_OK;
-    hipStream_t st = (hipStream_t)stream;
+    if (pi < po + bo && po < pi + bi) return "d_in and d_out overlap: the rays read behind the write front, in-place use is not possible";
+    return nullptr;
+}
+
+// the operator of rays, gains, rotation and level on checked arguments (nblocks > 0): the kernels of a handle without a clock
+static int userchan_run(mcrx_hip_userchan_t q, const void *d_in, long long first_block, size_t nblocks, size_t lead_blocks, void *d_out, hipStream_t st)
+{
     UserchanArgs a = {};
     const uint32_t *t = static_cast<const uint32_t *>(q->table);
     a.head = reinterpret_cast<const uint4 *>(t);
@@ -349,6 +467,43 @@ extern "C" int mcrx_hip_userchan_apply_tiles(mcrx_hip_userchan_t q, const void *
         if (q->rot) hipLaunchKernelGGL((userchan_kernel<true, true>), grid, dim3(256), 0, st, a);
         else        hipLaunchKernelGGL((userchan_kernel<false, true>), grid, dim3(256), 0, st, a);
         UCCHK(hipGetLastError());
+        off += m;
+    }
+    return MCRX_OK;
+}
+
+static bool userclock_check_range(mcrx_hip_userchan_t q, long long first_block, size_t nblocks, uint32_t D);
+static int userclock_launch(mcrx_hip_userchan_t q, const float2 *in, long long first_block, size_t nblocks, size_t lead_blocks, uint32_t skip,
+                            float2 *out, hipStream_t st);
+
+extern "C" int mcrx_hip_userchan_apply_tiles(mcrx_hip_userchan_t q, const void *d_in, long long first_block, size_t nblocks,
+                                             size_t lead_blocks, void *d_out, void *stream)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_uc_err = "null handle"; return MCRX_EINVAL; }
+    const char *bad = userchan_check_call(q, d_in, first_block, nblocks, lead_blocks, d_out, mcrx_hip_userchan_lead_blocks(q),
+                                          q->clock ? "lead_blocks is below the largest delay + max_delay + 16 rounded up to 8 (mcrx_hip_userchan_lead_blocks)"
+                                                   : "lead_blocks is below the handle's largest delay rounded up to 8 (mcrx_hip_userchan_lead_blocks)");
+    if (bad) { g_uc_err = bad; return MCRX_EINVAL; }
+    if (nblocks == 0) return MCRX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (!q->clock) return userchan_run(q, d_in, first_block, nblocks, lead_blocks, d_out, st);
+    // a clock on: spans of at most clk_span blocks, clock kernel -> z (with the rays' lead in front) -> the operator on z.  Both are
+    // functions of the absolute block index, so the spans are invisible in the output.  z in front of block first - D is not read.
+    if (!userclock_check_range(q, first_block, nblocks, q->D)) return MCRX_EINVAL;
+    const size_t lz = q->lead, lead_in = lead_blocks - lz;                 // (lead_blocks >= D + max_delay + 16: z of block first - D has its window)
+    const uint64_t span = nblocks < q->clk_span ? nblocks : q->clk_span;
+    if (lz + span > q->zbuf_blocks) {                                       // grow (hipFree waits for the calls in flight); steady state: never
+        if (q->zbuf) { UCCHK(hipFree(q->zbuf)); q->zbuf = nullptr; q->zbuf_blocks = 0; }
+        UCCHK(hipMalloc((void **)&q->zbuf, (size_t)(lz + span) * q->C * sizeof(float2)));
+        q->zbuf_blocks = lz + span;
+    }
+    for (size_t off = 0; off < nblocks; ) {
+        const size_t m = nblocks - off < span ? nblocks - off : (size_t)span;
+        const long long pos = first_block + (long long)off;
+        int rc = userclock_launch(q, static_cast<const float2 *>(d_in) + off * q->C, pos - (long long)lz, lz + m, lead_in, (uint32_t)lz - q->D, q->zbuf, st);
+        if (rc == MCRX_OK) rc = userchan_run(q, q->zbuf, pos, m, lz, static_cast<float2 *>(d_out) + off * q->C, st);
+        if (rc != MCRX_OK) return rc;
         off += m;
     }
     return MCRX_OK;
@@ -459,4 +614,178 @@ extern "C" int mcrx_hip_userfade_gains(mcrx_hip_userchan_t q, long long first_ro
     userfade_launch_gains(q, first_row, rows, static_cast<float2 *>(d_table), (hipStream_t)stream);
     UCCHK(hipGetLastError());
     return MCRX_OK;
+}
+
+// ---- each user's own sample clock and fractional timing (mcrx_hip_userclock_*) ----
+static void userclock_make_table(float *W)
+{
+    const double ib = besseli0(6.0);
+    for (int p = 0; p <= MCRX_USERCLOCK_PHASES; p++)
+        for (int j = 0; j < MCRX_USERCLOCK_TAPS; j++) {
+            const double t = (double)(j - 15) - (double)p / MCRX_USERCLOCK_PHASES;
+            const double x = M_PI * t, sn = std::fabs(t) < 1e-12 ? 1.0 : std::sin(x) / x;
+            const double r = t / 16.0, w = 1.0 - r * r;
+            float v = (float)(sn * besseli0(6.0 * std::sqrt(w < 0.0 ? 0.0 : w)) / ib);
+            if (p == 0) v = j == 15 ? 1.f : 0.f;                        // the two ends are whole-sample delays: exact unit vectors
+            if (p == MCRX_USERCLOCK_PHASES) v = j == 16 ? 1.f : 0.f;
+            W[p * MCRX_USERCLOCK_TAPS + j] = v;
+        }
+}
+
+static const float *userclock_table()
+{
+    static const std::vector<float> W = [] { std::vector<float> w((MCRX_USERCLOCK_PHASES + 1) * MCRX_USERCLOCK_TAPS); userclock_make_table(w.data()); return w; }();
+    return W.data();
+}
+
+static const char *userclock_check_config(const mcrx_hip_userclock_config *f)
+{
+    if (f->struct_size != sizeof(mcrx_hip_userclock_config)) return "mcrx_hip_userclock_config: wrong struct_size";
+    if (f->user_struct_size != sizeof(mcrx_hip_userclock_user)) return "mcrx_hip_userclock_user: wrong user_struct_size";
+    if (f->max_delay < MCRX_USERCLOCK_MIN_DELAY || f->max_delay > MCRX_USERCLOCK_MAX_DELAY) return "max_delay must be 15 .. 255";
+    if (f->span_blocks % 8u) return "span_blocks must be 0 (default) or a multiple of 8";
+    return nullptr;
+}
+
+static const char *userclock_check_user(uint32_t max_delay, const mcrx_hip_userclock_user *u)
+{
+    if (!u->enabled) return nullptr;
+    if (u->sco > ((int64_t)1 << 38) || u->sco < -((int64_t)1 << 38)) return "|sco| exceeds 2^38";
+    const uint64_t n = u->delay_fp >> 32;
+    if (n < MCRX_USERCLOCK_MIN_DELAY || n > max_delay) return "delay_fp: the whole samples of the delay lie outside [15, max_delay]";
+    return nullptr;
+}
+
+// tau_fp of a checked, enabled user at block b: nullptr, or what is wrong there
+static const char *userclock_at(uint32_t max_delay, const mcrx_hip_userclock_user *u, long long b, int64_t *tau_fp)
+{
+    long long d, p;
+    if (__builtin_sub_overflow(b, (long long)u->origin, &d) || __builtin_mul_overflow((long long)u->sco, d, &p)) return "sco * (block - origin) leaves int64";
+    const int64_t tau = (int64_t)u->delay_fp + ((int64_t)p >> 16);      // (delay_fp < 2^40, the shifted product < 2^47)
+    const int64_t n = tau >> 32;
+    if (n < MCRX_USERCLOCK_MIN_DELAY || n > (int64_t)max_delay) return "the whole samples of the delay leave [15, max_delay]";
+    *tau_fp = tau;
+    return nullptr;
+}
+
+// the two ends of a call -- blocks first_block - D and first_block + nblocks - 1 (nblocks > 0) -- for every user with a clock
+static bool userclock_check_range(mcrx_hip_userchan_t q, long long first_block, size_t nblocks, uint32_t D)
+{
+    long long ends[2];
+    if (__builtin_sub_overflow(first_block, (long long)D, &ends[0]) || __builtin_add_overflow(first_block, (long long)(nblocks - 1), &ends[1])) {
+        g_uc_err = "the call's blocks leave int64";
+        return false;
+    }
+    for (uint32_t c = 0; c < q->C; c++) {
+        if (!q->clk_users[c].enabled) continue;
+        for (int e = 0; e < 2; e++) {
+            int64_t tau;
+            const char *bad = userclock_at(q->clk_max, &q->clk_users[c], ends[e], &tau);
+            if (bad) { g_uc_err = "channel " + std::to_string(c) + ", block " + std::to_string(ends[e]) + ": " + bad; return false; }
+        }
+    }
+    return true;
+}
+
+// z of blocks [first_block, first_block + nblocks) into out (the tiles' layout), blocks below `skip` of them as zeros
+static int userclock_launch(mcrx_hip_userchan_t q, const float2 *in, long long first_block, size_t nblocks, size_t lead_blocks, uint32_t skip,
+                            float2 *out, hipStream_t st)
+{
+    UserclockArgs a;
+    a.in = in; a.out = reinterpret_cast<float4 *>(out);
+    a.par = static_cast<const uint4 *>(q->cplanes);
+    a.W = reinterpret_cast<const float *>(a.par + (size_t)q->C * 2u);
+    a.first = first_block; a.C = q->C; a.tiles = (uint32_t)(nblocks / 8);
+    a.lead = (uint32_t)lead_blocks; a.in_rows = (uint32_t)((lead_blocks + nblocks) / 8); a.skip = skip;
+    const dim3 grid((unsigned)((nblocks + UCLK_BLOCKS - 1u) / UCLK_BLOCKS), (q->C + UCLK_CH - 1u) / UCLK_CH);
+    hipLaunchKernelGGL(userclock_kernel, grid, dim3(256), 0, st, a);
+    UCCHK(hipGetLastError());
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_userclock_on(mcrx_hip_userchan_t q) { return q && q->clock ? 1 : 0; }
+
+extern "C" int mcrx_hip_userclock_table(float *W)
+{
+    if (!W) { g_uc_err = "null pointer"; return MCRX_EINVAL; }
+    const float *t = userclock_table();
+    for (int i = 0; i < (MCRX_USERCLOCK_PHASES + 1) * MCRX_USERCLOCK_TAPS; i++) W[i] = t[i];
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_userclock_selftest(const mcrx_hip_userclock_config *f, const mcrx_hip_userclock_user *u, long long block, int64_t *tau_fp, float *h)
+{
+    if (!f || !u || !tau_fp || !h) { g_uc_err = "null pointer"; return MCRX_EINVAL; }
+    const char *bad = userclock_check_config(f);
+    if (!bad) bad = userclock_check_user(f->max_delay, u);
+    int64_t tau = 0;
+    if (!bad && u->enabled) bad = userclock_at(f->max_delay, u, block, &tau);
+    if (bad) { g_uc_err = bad; return MCRX_EINVAL; }
+    *tau_fp = tau;
+    if (!u->enabled) {                                                  // z = x: n = 0 in the definition's indexing
+        for (int j = 0; j < MCRX_USERCLOCK_TAPS; j++) h[j] = j == 15 ? 1.f : 0.f;
+        return MCRX_OK;
+    }
+    const uint32_t mu = (uint32_t)(uint64_t)tau, r = mu >> 26;
+    const float fr = (float)((mu >> 2) & 0xffffffu) * 0x1p-24f;
+    const float *w0 = userclock_table() + r * MCRX_USERCLOCK_TAPS, *w1 = w0 + MCRX_USERCLOCK_TAPS;
+    for (int j = 0; j < MCRX_USERCLOCK_TAPS; j++) h[j] = userclock_coef(w0[j], w1[j], fr);
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_userclock_set(mcrx_hip_userchan_t q, const mcrx_hip_userclock_config *f, const mcrx_hip_userclock_user *users)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_uc_err = "null handle"; return MCRX_EINVAL; }
+    if (!f) {                                                           // off: the planes and the buffer go with the handle
+        UCCHK(hipDeviceSynchronize());
+        q->clock = false;
+        return MCRX_OK;
+    }
+    if (!users) { g_uc_err = "null user table"; return MCRX_EINVAL; }
+    const char *bad = userclock_check_config(f);
+    for (uint32_t c = 0; c < q->C && !bad; c++) {
+        bad = userclock_check_user(f->max_delay, &users[c]);
+        if (bad) { g_uc_err = "channel " + std::to_string(c) + ": " + bad; return MCRX_EINVAL; }
+    }
+    if (bad) { g_uc_err = bad; return MCRX_EINVAL; }
+    // the planes on the host: 32 bytes a channel, then W.  A user without a clock keeps the window of n = 15 (the kernel copies x)
+    const size_t words = (size_t)q->C * 4u, wn = (size_t)(MCRX_USERCLOCK_PHASES + 1) * MCRX_USERCLOCK_TAPS;
+    const size_t bytes = words * sizeof(uint64_t) + wn * sizeof(float);
+    std::vector<uint64_t> host((bytes + 7) / 8, 0);
+    for (uint32_t c = 0; c < q->C; c++) {
+        const mcrx_hip_userclock_user &u = users[c];
+        uint64_t *w = host.data() + (size_t)c * 4u;
+        if (u.enabled) { w[0] = u.delay_fp; w[1] = (uint64_t)u.sco; w[2] = (uint64_t)u.origin; w[3] = 1u; }
+        else           { w[0] = (uint64_t)MCRX_USERCLOCK_MIN_DELAY << 32; w[1] = w[2] = w[3] = 0; }
+    }
+    std::memcpy(host.data() + words, userclock_table(), wn * sizeof(float));
+    UCCHK(hipDeviceSynchronize());                                      // calls in flight read the planes about to go
+    void *planes = nullptr;
+    UCCHK(hipMalloc(&planes, bytes));
+    hipError_t e = hipMemcpy(planes, host.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(planes); g_uc_err = std::string("clock planes: ") + hipGetErrorString(e); return MCRX_EHIP; }
+    if (q->cplanes) (void)hipFree(q->cplanes);
+    q->cplanes = planes;
+    q->clk_users.assign(users, users + q->C);
+    q->clk_max = f->max_delay;
+    const uint64_t fit = USERCLOCK_SPAN_BYTES / ((size_t)q->C * sizeof(float2)) / UCLK_BLOCKS * UCLK_BLOCKS;
+    q->clk_span = f->span_blocks ? f->span_blocks : fit;
+    q->clock = true;
+    return MCRX_OK;
+}
+
+// the clock kernel on its own, into the caller's buffer: what apply_tiles computes for itself, for tests and measurements
+extern "C" int mcrx_hip_userclock_apply_tiles(mcrx_hip_userchan_t q, const void *d_in, long long first_block, size_t nblocks,
+                                              size_t lead_blocks, void *d_out, void *stream)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_uc_err = "null handle"; return MCRX_EINVAL; }
+    if (!q->clock) { g_uc_err = "the clock is off"; return MCRX_EINVAL; }
+    const char *bad = userchan_check_call(q, d_in, first_block, nblocks, lead_blocks, d_out, mcrx_hip_userclock_lead_blocks(q),
+                                          "lead_blocks is below max_delay + 16 rounded up to 8 (mcrx_hip_userclock_lead_blocks)");
+    if (bad) { g_uc_err = bad; return MCRX_EINVAL; }
+    if (nblocks == 0) return MCRX_OK;
+    if (!userclock_check_range(q, first_block, nblocks, 0u)) return MCRX_EINVAL;
+    return userclock_launch(q, static_cast<const float2 *>(d_in), first_block, nblocks, lead_blocks, 0u, static_cast<float2 *>(d_out), (hipStream_t)stream);
 }
