@@ -750,6 +750,87 @@ int      mcrx_hip_userclock_table(float W[(MCRX_USERCLOCK_PHASES + 1) * MCRX_USE
 int      mcrx_hip_userclock_apply_tiles(mcrx_hip_userchan_t q, const void *d_in, long long first_block, size_t nblocks,
                                         size_t lead_blocks, void *d_out, void *stream);
 
+/* ---- RF front end on the wideband stream: IQ imbalance and LO leakage, oscillator phase noise, amplifier ----
+ * The radios at either end of the air: what couples one user's signal into another user's channel.  Memoryless in the samples and
+ * STATELESS: the caller passes the absolute index of the first sample (any 64-bit value), so a stream cut anywhere, a time shard on any
+ * GPU and any launch geometry give the bits of one call.  x[n] is the input, cf32 or sc16 (a word means (re, im) * 2^-15).  Three
+ * stages, each switched by a bit of `stages` (a stage that is off is not computed at all), in the sequence `order` sets:
+ *   order = 0 (a transmitter): mixer, oscillator, amplifier         order = 1 (a receiver): amplifier, oscillator, mixer
+ * z is a stage's input and u its output, all fp32, every product that matters one fmaf:
+ * Mixer (MCRX_RFCHAIN_MIXER): u = alpha z + beta conj(z) + d -- IQ imbalance (the image of channel c lands in channel N - 1 - c, its
+ *   rejection is |alpha|^2 / |beta|^2) and LO leakage d:
+ *     u.re = fmaf(alpha.re, z.re, fmaf(-alpha.im, z.im, fmaf(beta.re, z.re, fmaf( beta.im, z.im, d.re))))
+ *     u.im = fmaf(alpha.re, z.im, fmaf( alpha.im, z.re, fmaf(beta.im, z.re, fmaf(-beta.re, z.im, d.im))))
+ * Oscillator (MCRX_RFCHAIN_OSCILLATOR): u = z e(theta(n)), a stationary phase noise common to all channels, a function of the sample
+ *   index: a sum of S = pn_sinusoids sinusoids sampled on the grid n = b 2^L (L = pn_log2_block, B = 2^L) and interpolated linearly
+ *   between its rows -- linear interpolation of the angle is part of the definition, as it is for the fading gains.  In turns:
+ *     Theta[b] = sum_{k<S} c cos 2 pi ((((Phi_k << 32) + N_k n_b) mod 2^64) >> 32) / 2^32      n_b = (b << L) mod 2^64; from 0.0f, k
+ *                                                                                             ascending, acc = fmaf(c, cos_k, acc)
+ *     theta(n) = fmaf(f, Theta[b+1] - Theta[b], Theta[b])                                     b = n >> L, f = (n & (B - 1)) 2^-L (exact)
+ *     p        = (uint32_t)(int32_t)rintf(theta * 2^32),  (sn, cs) = sincos of the 32-bit phase p (the emulators' sincos_u32)
+ *     u.re = fmaf(z.re, cs, -(z.im * sn)),  u.im = fmaf(z.re, sn, z.im * cs)                  the channel emulator's rotation
+ *   c = pn_rms sqrt(2 / S) / (2 pi) rounded to fp32 on the host (pn_rms in radians: the rms of theta).  The integers are made on the
+ *   host from pn_seed: the Philox4x32-10 words w0, w1 of counter (k, 0, 3, 0) and key (lo32(seed), hi32(seed)) (third counter word: 0 is
+ *   noise, 1 the wideband emulator's fading, 2 the users' fading) give u_k = (k + (w0 + 0.5) 2^-32) / S, f_k = clamp(pn_bandwidth
+ *   tan(pi (u_k - 1/2)), -1/(8B), +1/(8B)) -- a stratified draw from a Lorentzian line of half-width pn_bandwidth cycles per sample --
+ *   N_k = rint(f_k 2^64) (int64) and Phi_k = w1.
+ *   Theta lives in a table the handle owns (a row is one float), written by a kernel of its own in front of the samples' kernel and
+ *   grown on demand up to pn_table_rows rows (0: 2^18); a call that needs more runs as consecutive spans on the caller's stream, which
+ *   changes no bit of the output.  Because of that table, calls on ONE handle with the oscillator on must be ordered on the device
+ *   (one stream, or events of the caller's); handles without it are free of this.
+ * Amplifier (MCRX_RFCHAIN_AMPLIFIER): memoryless, Rapp AM/AM and a Saleh-shaped AM/PM, A = amp_sat, p = amp_smooth (1, 2 or 4):
+ *     t = fmaf(z.re, z.re, z.im * z.im) * r             r = fp32(1 / A^2), made on the host (the division in double)
+ *     q = 1 + t (p = 1);  sqrtf(fmaf(t, t, 1)) (p = 2);  sqrtf(sqrtf(fmaf(t2, t2, 1))), t2 = t * t (p = 4)
+ *     G = amp_gain / sqrtf(q)                           = amp_gain (1 + (|z| / A)^2p)^(-1 / 2p); division and roots correctly rounded
+ *     w = (G z.re, G z.im)
+ *     phi = amp_ampm * (t / (1 + t)) turns; p32 = (uint32_t)(int32_t)rintf(phi * 2^32); u = w rotated by p32 as above.
+ *                                                       amp_ampm == 0: skipped, no sincos, u = w
+ * Behind the last stage v = gain u (one multiply per component; skipped when gain == 1, so that a handle with no stage on and gain 1
+ * is a pure load-convert-store that keeps NaN payloads and the sign of zero).  out = v (cf32) or Q(v) (sc16: the shared quantiser as it
+ * stands, with the shared clip count).  The integers of an sc16-out handle are Q of a cf32-out handle's floats exactly. */
+#define MCRX_RFCHAIN_MIXER      1u
+#define MCRX_RFCHAIN_OSCILLATOR 2u
+#define MCRX_RFCHAIN_AMPLIFIER  4u
+#define MCRX_RFCHAIN_MAX_SINUSOIDS 16
+typedef struct mcrx_hip_rfchain_s *mcrx_hip_rfchain_t;
+typedef struct {
+    uint32_t struct_size, order, stages;                /* sizeof(mcrx_hip_rfchain_config); 0 = tx, 1 = rx; MCRX_RFCHAIN_* bits */
+    uint32_t input_format, output_format;               /* 0 = cf32, 1 = sc16 */
+    float    alpha_re, alpha_im, beta_re, beta_im, dc_re, dc_im;      /* mixer */
+    uint32_t pn_sinusoids, pn_log2_block, pn_table_rows;              /* oscillator: 1 .. 16; 1 .. 24; 0 = default, else >= 2 */
+    float    pn_rms;                                    /* radians rms, >= 0 */
+    double   pn_bandwidth;                              /* half-width of the line, cycles per wideband sample, >= 0 */
+    uint64_t pn_seed;
+    float    amp_sat, amp_gain, amp_ampm;               /* amplifier: A > 0; small-signal gain; AM/PM at full compression, turns */
+    uint32_t amp_smooth;                                /* 1, 2 or 4 */
+    float    gain;
+} mcrx_hip_rfchain_config;
+/* MCRX_EINVAL, before a device is looked for: null pointers, a wrong struct_size, order above 1, unknown stage bits, a format that is not
+ * 0 or 1, a gain that is not finite; with the mixer on a coefficient that is not finite; with the oscillator on pn_sinusoids outside
+ * 1 .. 16, pn_log2_block outside 1 .. 24, pn_table_rows == 1, pn_rms or pn_bandwidth negative or not finite, pn_bandwidth * B > 1/8
+ * (the grid must sample the angle), pn_rms * sqrt(2 S) >= pi / 2 (keeps |theta| < 1/4 turn); with the amplifier on amp_smooth other than
+ * 1, 2, 4, an amp_sat that is not finite and positive or whose 1 / A^2 is not a finite positive fp32, an amp_gain that is not finite,
+ * |amp_ampm| > 1/4 or not finite.  Fields of a stage that is off are not looked at. */
+int      mcrx_hip_rfchain_create(mcrx_hip_rfchain_t *out, const mcrx_hip_rfchain_config *cfg);
+int      mcrx_hip_rfchain_destroy(mcrx_hip_rfchain_t q);
+/* n samples at d_in (the handle's input format) -> n samples at d_out (its output format), the first of them absolute sample
+ * first_sample, asynchronously on `stream` (NULL = the default stream); at most 2^32 samples a call.  MCRX_EINVAL, nothing written: a
+ * null handle or buffer, a cf32 buffer not 8-byte aligned, an sc16 buffer not 4-byte aligned, ranges that overlap -- EXCEPT d_in ==
+ * d_out with equal formats: a lane writes only what it read, so in-place use is allowed.  (Pairs of samples go as 16-byte (sc16:
+ * 8-byte) words where the addresses allow.) */
+int      mcrx_hip_rfchain_execute_device(mcrx_hip_rfchain_t q, const void *d_in, uint64_t first_sample, size_t n, void *d_out, void *stream);
+/* mctx_hip_clipped's semantics; counter and event exist only on a handle with sc16 output; always 0 on a cf32 one */
+int      mcrx_hip_rfchain_clipped(mcrx_hip_rfchain_t q, uint64_t *samples, int reset);
+unsigned mcrx_hip_rfchain_input_format(mcrx_hip_rfchain_t q);                        /* 0 for a null handle */
+unsigned mcrx_hip_rfchain_output_format(mcrx_hip_rfchain_t q);                       /* 0 for a null handle */
+/* host, no GPU: the oscillator's integers N_k (steps) and Phi_k (phases), pn_sinusoids entries each, and c (*coef).  Checks cfg as
+ * create does, the oscillator's fields whether or not its bit is set. */
+int      mcrx_hip_rfchain_selftest(const mcrx_hip_rfchain_config *cfg, int64_t *steps, uint32_t *phases, float *coef);
+/* The table kernel on its own, for tests and measurements: Theta[first_row + r], r < rows, as floats into the caller's 4-byte aligned
+ * device buffer, asynchronously on `stream`.  MCRX_EINVAL with the oscillator off. */
+int      mcrx_hip_rfchain_phase_rows(mcrx_hip_rfchain_t q, uint64_t first_row, uint32_t rows, void *d_table, void *stream);
+const char *mcrx_hip_rfchain_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,15 @@ _EXPORTS = {
     "mcrx_hip_userclock_selftest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_int64), C.POINTER(C.c_float)]),
     "mcrx_hip_userclock_table": (C.c_int, [C.POINTER(C.c_float)]),
     "mcrx_hip_userclock_apply_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_rfchain_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcrx_hip_rfchain_destroy": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_rfchain_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_rfchain_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
+    "mcrx_hip_rfchain_input_format": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_rfchain_output_format": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_rfchain_selftest": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "mcrx_hip_rfchain_phase_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_rfchain_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -893,6 +902,172 @@ class chanemu(object):
     def close(self):
         if self._h:
             lib().mcrx_hip_chanemu_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+RFCHAIN_MIXER, RFCHAIN_OSCILLATOR, RFCHAIN_AMPLIFIER = 1, 2, 4      # MCRX_RFCHAIN_* stage bits
+RFCHAIN_ORDERS = {"tx": 0, "rx": 1}                                 # mixer, oscillator, amplifier / amplifier, oscillator, mixer
+
+
+class RfchainConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("order", C.c_uint32), ("stages", C.c_uint32), ("input_format", C.c_uint32),
+                ("output_format", C.c_uint32), ("alpha_re", C.c_float), ("alpha_im", C.c_float), ("beta_re", C.c_float),
+                ("beta_im", C.c_float), ("dc_re", C.c_float), ("dc_im", C.c_float), ("pn_sinusoids", C.c_uint32),
+                ("pn_log2_block", C.c_uint32), ("pn_table_rows", C.c_uint32), ("pn_rms", C.c_float), ("pn_bandwidth", C.c_double),
+                ("pn_seed", C.c_uint64), ("amp_sat", C.c_float), ("amp_gain", C.c_float), ("amp_ampm", C.c_float),
+                ("amp_smooth", C.c_uint32), ("gain", C.c_float)]
+
+
+def rfchain_iq(gain_db, phase_deg, side="tx"):
+    """The mixer coefficients dict(alpha=, beta=) of a modulator (side="tx") or demodulator ("rx") whose Q arm has gain_db more gain and
+    phase_deg more phase than its I arm.  The image rejection is |alpha|^2 / |beta|^2."""
+    if side not in ("tx", "rx"):
+        raise ValueError("side must be 'tx' or 'rx', not %r" % (side,))
+    g, phi = 10.0 ** (float(gain_db) / 20.0), math.radians(float(phase_deg))
+    e = complex(math.cos(phi), math.sin(phi))
+    alpha = (1.0 + g * e) / 2.0 if side == "tx" else (1.0 + g * e.conjugate()) / 2.0
+    return dict(alpha=alpha, beta=(1.0 - g * e) / 2.0)
+
+
+def rfchain_backoff(ibo_db, rms):
+    """The amplifier's saturation amplitude A that puts a signal of amplitude `rms` ibo_db below it (input back-off)."""
+    return float(rms) * 10.0 ** (float(ibo_db) / 20.0)
+
+
+def rfchain_config(order="tx", mixer=None, phase_noise=None, amplifier=None, gain=1.0, input_format="cf32", output_format="cf32"):
+    """The mcrx_hip_rfchain_config of rfchain's arguments.  ValueError for a malformed argument; the values themselves are judged by
+    the library (mcrx_hip_rfchain_create, before it looks for a device)."""
+    def section(d, name, required, optional):
+        if d is None:
+            return None
+        if not isinstance(d, dict) or any(k not in required and k not in optional for k in d) or any(k not in d for k in required):
+            raise ValueError("%s is None or a dict with %s and optionally %s" % (name, required, tuple(optional)))
+        return dict(optional, **d)
+
+    def whole(v, name, bits=32):
+        if int(v) != v or not 0 <= int(v) < (1 << bits):
+            raise ValueError("%s must be a whole number, 0 .. 2^%d - 1" % (name, bits))
+        return int(v)
+    c = RfchainConfig()
+    c.struct_size = C.sizeof(RfchainConfig)
+    if order not in RFCHAIN_ORDERS:
+        raise ValueError("order must be 'tx' or 'rx', not %r" % (order,))
+    c.order = RFCHAIN_ORDERS[order]
+    c.input_format = _format_code(input_format, INPUT_FORMATS, "input_format")
+    c.output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
+    c.gain = float(gain)
+    m = section(mixer, "mixer", ("alpha", "beta"), dict(dc=0.0))
+    if m is not None:
+        al, be, dc = complex(m["alpha"]), complex(m["beta"]), complex(m["dc"])
+        c.alpha_re, c.alpha_im, c.beta_re, c.beta_im, c.dc_re, c.dc_im = al.real, al.imag, be.real, be.imag, dc.real, dc.imag
+        c.stages |= RFCHAIN_MIXER
+    p = section(phase_noise, "phase_noise", ("rms_deg", "bandwidth"), dict(sinusoids=16, log2_block=10, seed=0, table_rows=0))
+    if p is not None:
+        c.pn_sinusoids, c.pn_log2_block = whole(p["sinusoids"], "sinusoids"), whole(p["log2_block"], "log2_block")
+        c.pn_table_rows, c.pn_seed = whole(p["table_rows"], "table_rows"), int(p["seed"]) % (1 << 64)
+        c.pn_rms, c.pn_bandwidth = math.radians(float(p["rms_deg"])), float(p["bandwidth"])
+        c.stages |= RFCHAIN_OSCILLATOR
+    a = section(amplifier, "amplifier", ("sat",), dict(smooth=2, gain=1.0, ampm_deg=0.0))
+    if a is not None:
+        c.amp_sat, c.amp_gain, c.amp_ampm = float(a["sat"]), float(a["gain"]), float(a["ampm_deg"]) / 360.0
+        c.amp_smooth = whole(a["smooth"], "smooth")
+        c.stages |= RFCHAIN_AMPLIFIER
+    return c
+
+
+def rfchain_integers(cfg):
+    """(steps, phases, c) of the oscillator of an RfchainConfig: the library's own integers N_k, Phi_k and its fp32 coefficient
+    (mcrx_hip_rfchain_selftest; host only)."""
+    S = int(cfg.pn_sinusoids)
+    steps, phases, coef = (C.c_int64 * 16)(), (C.c_uint32 * 16)(), C.c_float()
+    _raise_rc(lib().mcrx_hip_rfchain_selftest(C.addressof(cfg), steps, phases, C.byref(coef)), "mcrx_hip_rfchain_selftest",
+              lib().mcrx_hip_rfchain_last_error)
+    return [int(v) for v in steps[:S]], [int(v) for v in phases[:S]], float(coef.value)
+
+
+class rfchain(object):
+    """RF front end on the wideband stream (mcrx_hip_rfchain_*): the radios at either end of the air.
+
+        rfchain(order="tx", mixer=None | dict(alpha, beta, dc=0), phase_noise=None | dict(rms_deg, bandwidth, sinusoids=16,
+                log2_block=10, seed=0, table_rows=0), amplifier=None | dict(sat, smooth=2, gain=1.0, ampm_deg=0.0), gain=1.0,
+                input_format="cf32", output_format="cf32")
+
+    mixer: u = alpha z + beta conj(z) + dc (rfchain_iq makes alpha, beta of an imbalance in dB and degrees); phase_noise: a stationary
+    phase of rms_deg degrees rms with a Lorentzian line of half-width `bandwidth` cycles per sample, common to all channels;
+    amplifier: Rapp AM/AM of smoothness 1, 2 or 4 that saturates at amplitude `sat` (rfchain_backoff) with a Saleh-shaped AM/PM that
+    tends to ampm_deg.  order "tx" runs mixer, oscillator, amplifier; "rx" the reverse.  A section that is None is not computed.
+    The operator is memoryless and stateless: execute(x, first_sample) takes the absolute index of x[0], so a stream may be cut, or
+    sharded in time over GPUs, anywhere.  sc16 tensors are contiguous int16 of shape (n, 2)."""
+
+    def __init__(self, order="tx", mixer=None, phase_noise=None, amplifier=None, gain=1.0, input_format="cf32", output_format="cf32"):
+        self._h = C.c_void_p()
+        c = rfchain_config(order, mixer, phase_noise, amplifier, gain, input_format, output_format)
+        rc = lib().mcrx_hip_rfchain_create(C.byref(self._h), C.addressof(c))
+        if rc != MCRX_OK:
+            self._h = C.c_void_p()
+            self._chk(rc, "mcrx_hip_rfchain_create")
+        self.config, self.input_format, self.output_format, self.stages = c, int(c.input_format), int(c.output_format), int(c.stages)
+
+    @staticmethod
+    def _chk(rc, name):
+        _raise_rc(rc, name, lib().mcrx_hip_rfchain_last_error)
+
+    def execute(self, x, first_sample=0, out=None, stream=None):
+        """x: samples first_sample .. first_sample + n - 1 of the stream, a contiguous CUDA tensor: complex64, or on an sc16-in handle
+        int16 of shape (n, 2).  out (optional): where they go, in the output format, with room for n samples; `out is x` (the same
+        address) is allowed with equal formats, any other overlap is refused.  Returns the n samples written.  Asynchronous on
+        `stream` (default: torch's current stream of x's device)."""
+        import torch
+        in16, out16 = self.input_format == INPUT_FORMATS["sc16"], self.output_format == OUTPUT_FORMATS["sc16"]
+        if in16:
+            n = _sc16_device_samples(x, "front end")
+        else:
+            if x.dtype != torch.complex64:
+                raise TypeError("this front end takes complex64 device tensors, not %s" % x.dtype)
+            n = int(x.numel())
+        if not x.is_cuda or not x.is_contiguous():
+            raise ValueError("device samples must be contiguous CUDA tensors")
+        if out is None:
+            out = _empty_samples(n, self.output_format, x.device)
+        else:
+            if out.dtype != (torch.int16 if out16 else torch.complex64):
+                raise TypeError("out must be %s for this front end" % ("int16" if out16 else "complex64"))
+            if not out.is_cuda or not out.is_contiguous() or int(out.numel()) < (2 * n if out16 else n):
+                raise ValueError("out must be a contiguous CUDA tensor with room for %d samples" % n)
+        if n == 0:              # (an empty tensor has no address to pass)
+            return out.view(-1, 2)[:0] if out16 else out.view(-1)[:0]
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        self._chk(lib().mcrx_hip_rfchain_execute_device(self._h, _dptr(x), int(first_sample) % (1 << 64), n, _dptr(out),
+                                                        _stream_ptr(stream)), "mcrx_hip_rfchain_execute_device")
+        return out.view(-1, 2)[:n] if out16 else out.view(-1)[:n]
+
+    def phase_rows(self, first_row, rows, stream=None):
+        """The oscillator's table rows first_row .. first_row + rows - 1 (grid row b = n >> log2_block), in turns, as a float32 CUDA
+        tensor: what the execute calls interpolate between.  For tests and measurements."""
+        import torch
+        out = torch.zeros(int(rows), dtype=torch.float32, device="cuda")
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device)
+        self._chk(lib().mcrx_hip_rfchain_phase_rows(self._h, int(first_row) % (1 << 64), int(rows), _dptr(out), _stream_ptr(stream)),
+                  "mcrx_hip_rfchain_phase_rows")
+        return out
+
+    def clipped(self, reset=False):
+        """Samples clipped by the sc16-out calls since the count was last reset (waits for the last such call only); 0 on a cf32 one."""
+        n = C.c_uint64(0)
+        self._chk(lib().mcrx_hip_rfchain_clipped(self._h, C.byref(n), 1 if reset else 0), "mcrx_hip_rfchain_clipped")
+        return int(n.value)
+
+    def close(self):
+        if self._h:
+            lib().mcrx_hip_rfchain_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

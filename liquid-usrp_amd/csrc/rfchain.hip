@@ -1,0 +1,344 @@
+// rfchain.hip -- RF front end on the wideband stream for gfx950: IQ imbalance and LO leakage, oscillator phase noise, amplifier
+// compression; cf32 or sc16 in, cf32 or sc16 out (mcrx_hip_rfchain_*; the definition with every fmaf is in
+// include/mcrx_hip.h).
+//
+// Memoryless in the samples and stateless: everything is a function of the sample's value and its ABSOLUTE index n, which the caller
+// passes -- never of how the stream is cut into calls, of the GPU a time shard runs on or of the launch geometry.
+//   mixer       u = alpha z + beta conj(z) + d              four nested fmaf per component
+//   oscillator  u = z e(theta(n))                           theta(n) = fmaf(f, Theta[b+1] - Theta[b], Theta[b]), b = n >> L; sincos_u32,
+//                                                           chanemu_sample's rotation
+//   amplifier   u = (G z) e(phi)                            G = amp_gain / sqrtf(q(t)), t = |z|^2 / A^2; phi = ampm t / (1 + t) turns
+//   order 0: mixer, oscillator, amplifier; order 1: amplifier, oscillator, mixer; then v = gain u, out = v or Q(v) (sc16.hpp)
+// rfchain_phase_kernel writes the rows of Theta a span of samples needs into the handle's table (one float a row), a lane per row;
+// the integers of its sinusoids are made on the host from pn_seed (rfchain_plan.hpp) and travel as kernel arguments.
+//
+// rfchain_kernel<STAGES, FIN, FOUT>: streaming, no LDS.  A lane owns the index-aligned pair (2k, 2k + 1): 2^L is even, so a pair never
+// straddles a grid row and the two table rows serve both samples; its accesses are 16 bytes (sc16: 8) where the address allows -- a
+// uniform choice, all lanes' pairs have the same parity.  The stage mask and the formats are template parameters: a build carries
+// only its stages' code, and the build with none is load, convert, store.  `order`, the amplifier's smoothness and "AM/PM on" are
+// wave-uniform branches on kernel arguments.  A lane writes only the samples it read: in-place use is allowed with equal formats.
+//
+// Contraction is switched off for this file: every build rounds the same way, so the integers of an sc16 handle are Q of a cf32
+// handle's floats, and the products that matter are written as fmaf.
+#pragma clang fp contract(off)
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <stdint.h>
+#include <string>
+#include "../../include/mcrx_hip.h"
+#include "devmath.h"
+#include "devscope.hpp"
+#include "fadegen.hpp"
+#include "rfchain_plan.hpp"
+#include "sc16.hpp"
+
+namespace mcrx {
+
+enum { RF_MIX = MCRX_RFCHAIN_MIXER, RF_OSC = MCRX_RFCHAIN_OSCILLATOR, RF_AMP = MCRX_RFCHAIN_AMPLIFIER };
+
+struct RfchainArgs {
+    const void *in; void *out;
+    unsigned long long *clip;                               // sc16-out builds: the handle's count of clipped samples
+    uint64_t pos, n;                                        // absolute index of in[0]; samples of this launch
+    uint32_t order;
+    float ar, ai, br, bi, dr, di;                           // mixer
+    // oscillator builds only: the table of this span, its row 0 = grid row row0 = pos >> L; rows = rows it holds; finv = 2^-L
+    const float *tab; uint64_t row0; uint32_t L, rows; float finv;
+    float inv_a2, amp_gain, ampm; uint32_t smooth;          // amplifier
+    float gain;
+};
+
+// the oscillator's sinusoids
+struct RfchainPhase {
+    int64_t step[MCRX_RFCHAIN_MAX_SINUSOIDS];               // 2^64 * cycles per wideband sample
+    uint32_t phase[MCRX_RFCHAIN_MAX_SINUSOIDS];             // 2^32 * cycles
+    float c; uint32_t S;
+};
+
+// table[row] = Theta[row0 + row], row < rows: a lane per row, the integers are scalar loads
+__global__ __launch_bounds__(256) void rfchain_phase_kernel(RfchainPhase t, float *table, uint64_t row0, uint32_t rows, uint32_t L)
+{
+    const uint32_t row = blockIdx.x * 256u + threadIdx.x;
+    if (row >= rows) return;
+    const uint64_t nb = (row0 + row) << L;                              // the grid index wraps with the 64-bit position
+    float acc = 0.f;
+    for (uint32_t k = 0; k < t.S; k++) {
+        float sn, cs;
+        sincos_u32((uint32_t)((((uint64_t)t.phase[k] << 32) + (uint64_t)t.step[k] * nb) >> 32), sn, cs);
+        acc = fmaf(t.c, cs, acc);
+    }
+    table[row] = acc;
+}
+
+// (uint32_t)(int32_t)rintf(turns * 2^32): the hardware's conversion, as sc16_round's (it saturates and turns NaN into 0, where the C cast
+// is undefined -- an infinite input sample reaches this through the amplifier's phi)
+__device__ __forceinline__ uint32_t rfchain_phase_word(float turns)
+{
+    const float r = __builtin_rintf(turns * 4294967296.0f);
+    int i;
+    asm("v_cvt_i32_f32_e32 %0, %1" : "=v"(i) : "v"(r));
+    return (uint32_t)i;
+}
+// z e(p), chanemu_sample's shape
+__device__ __forceinline__ float2 rfchain_rotate(float2 z, uint32_t p)
+{
+    float sn, cs;
+    sincos_u32(p, sn, cs);
+    return make_float2(fmaf(z.x, cs, -(z.y * sn)), fmaf(z.x, sn, z.y * cs));
+}
+__device__ __forceinline__ float2 rfchain_mixer(const RfchainArgs &a, float2 z)
+{
+    return make_float2(fmaf(a.ar, z.x, fmaf(-a.ai, z.y, fmaf(a.br, z.x, fmaf(a.bi, z.y, a.dr)))),
+                       fmaf(a.ar, z.y, fmaf(a.ai, z.x, fmaf(a.bi, z.x, fmaf(-a.br, z.y, a.di)))));
+}
+__device__ __forceinline__ float2 rfchain_amplifier(const RfchainArgs &a, float2 z)
+{
+    const float t = fmaf(z.x, z.x, z.y * z.y) * a.inv_a2;
+    float q;
+    if (a.smooth == 1u) q = 1.0f + t;
+    else if (a.smooth == 2u) q = sqrtf(fmaf(t, t, 1.0f));
+    else { const float t2 = t * t; q = sqrtf(sqrtf(fmaf(t2, t2, 1.0f))); }
+    const float G = a.amp_gain / sqrtf(q);
+    const float2 w = make_float2(G * z.x, G * z.y);
+    if (a.ampm == 0.f) return w;
+    return rfchain_rotate(w, rfchain_phase_word(a.ampm * (t / (1.0f + t))));
+}
+
+template <int STAGES>
+__device__ __forceinline__ float2 rfchain_sample(const RfchainArgs &a, float2 z, float theta)
+{
+    constexpr bool several = (STAGES & (STAGES - 1)) != 0;             // one stage alone has no sequence
+    if (!several || a.order == 0u) {
+        if (STAGES & RF_MIX) z = rfchain_mixer(a, z);
+        if (STAGES & RF_OSC) z = rfchain_rotate(z, rfchain_phase_word(theta));
+        if (STAGES & RF_AMP) z = rfchain_amplifier(a, z);
+    } else {
+        if (STAGES & RF_AMP) z = rfchain_amplifier(a, z);
+        if (STAGES & RF_OSC) z = rfchain_rotate(z, rfchain_phase_word(theta));
+        if (STAGES & RF_MIX) z = rfchain_mixer(a, z);
+    }
+    if (a.gain != 1.0f) z = make_float2(a.gain * z.x, a.gain * z.y);
+    return z;
+}
+
+template <int STAGES, int FIN, int FOUT>
+__global__ __launch_bounds__(256) void rfchain_kernel(RfchainArgs a)
+{
+    // lane g owns absolute samples base + 2 g, + 1 with base = pos & ~1: relative to in[0] that is m0 = 2 g - (pos & 1), m0 + 1
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint32_t odd = (uint32_t)(a.pos & 1u);
+    const long long m0 = (long long)(2 * g) - (long long)odd;
+    const bool ok0 = m0 >= 0 && m0 < (long long)a.n, ok1 = m0 + 1 < (long long)a.n;      // (m0 + 1 >= 0 always)
+    uint32_t nclip = 0;
+    if (ok0 || ok1) {
+        float2 x0 = make_float2(0.f, 0.f), x1 = x0;                     // (the masked half of an edge pair computes on a zero)
+        if (FIN == IQ_SC16) {
+            const uint32_t *p = reinterpret_cast<const uint32_t *>(a.in) + m0;
+            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
+                const uint2 w = *reinterpret_cast<const uint2 *>(p);
+                x0 = sc16_unpack(w.x); x1 = sc16_unpack(w.y);
+            } else { if (ok0) x0 = sc16_unpack(p[0]); if (ok1) x1 = sc16_unpack(p[1]); }
+        } else {
+            const float2 *p = reinterpret_cast<const float2 *>(a.in) + m0;
+            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+                const float4 v = *reinterpret_cast<const float4 *>(p);
+                x0 = make_float2(v.x, v.y); x1 = make_float2(v.z, v.w);
+            } else { if (ok0) x0 = p[0]; if (ok1) x1 = p[1]; }
+        }
+        float th0 = 0.f, th1 = 0.f;
+        if (STAGES & RF_OSC) {
+            const uint64_t nabs = (a.pos - odd) + 2 * g;                // even; wraps with the 64-bit position
+            const uint64_t row = ((nabs >> a.L) - a.row0) & (~(uint64_t)0 >> a.L);
+            const float *trow = a.tab + (size_t)(row < a.rows - 1u ? row : a.rows - 2u);      // (row + 1 < rows for every pair of the span)
+            const float T0 = trow[0], dT = trow[1] - T0;
+            const uint32_t frac = (uint32_t)nabs & ((1u << a.L) - 1u);
+            th0 = fmaf((float)frac * a.finv, dT, T0); th1 = fmaf((float)(frac + 1u) * a.finv, dT, T0);
+        }
+        const float2 v0 = rfchain_sample<STAGES>(a, x0, th0);
+        const float2 v1 = rfchain_sample<STAGES>(a, x1, th1);
+        if (FOUT == IQ_SC16) {
+            uint32_t *o = reinterpret_cast<uint32_t *>(a.out) + m0;
+            uint32_t c0 = 0, c1 = 0;
+            const uint32_t q0 = sc16_sample(v0.x, v0.y, c0), q1 = sc16_sample(v1.x, v1.y, c1);
+            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(o) & 7u) == 0) *reinterpret_cast<uint2 *>(o) = make_uint2(q0, q1);
+            else { if (ok0) o[0] = q0; if (ok1) o[1] = q1; }
+            nclip = (ok0 ? c0 : 0u) + (ok1 ? c1 : 0u);
+        } else {
+            float2 *o = reinterpret_cast<float2 *>(a.out) + m0;
+            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) *reinterpret_cast<float4 *>(o) = make_float4(v0.x, v0.y, v1.x, v1.y);
+            else { if (ok0) o[0] = v0; if (ok1) o[1] = v1; }
+        }
+    }
+    if (FOUT == IQ_SC16) sc16_clip_commit(a.clip, nclip);               // every lane of every wave gets here
+}
+
+}  // namespace mcrx
+
+using namespace mcrx;
+
+static thread_local std::string g_rf_err;
+#define RFCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_rf_err = std::string(#x) + ": " + hipGetErrorString(e_); return MCRX_EHIP; } } while (0)
+
+struct mcrx_hip_rfchain_s {
+    int device = -1;            // the HIP device the handle was created on: every entry point runs with it current (devscope.hpp)
+    mcrx_hip_rfchain_config cfg;
+    Sc16ClipCount clip;         // sc16-out handles only (allocated at creation): clipped samples since the handle was made
+    RfchainPhase pt = {};       // oscillator on: its sinusoids
+    uint32_t cap = 0;           // the most rows of the table a span may use
+    float *tab = nullptr; uint32_t tab_rows = 0;    // Theta's table and the rows allocated (grown on demand, never shrunk)
+};
+
+// 2^18 rows = 1 MB at most (chanemu's row count): at L = 10 one span for 2.7e8 samples, at L = 6 spans of 1.7e7 samples
+static const uint32_t RFCHAIN_DEFAULT_ROWS = 1u << 18;
+
+extern "C" const char *mcrx_hip_rfchain_last_error(void) { return g_rf_err.c_str(); }
+
+extern "C" int mcrx_hip_rfchain_selftest(const mcrx_hip_rfchain_config *cfg, int64_t *steps, uint32_t *phases, float *coef)
+{
+    if (!cfg || !steps || !phases || !coef) { g_rf_err = "null pointer"; return MCRX_EINVAL; }
+    const char *bad = rfchain_check(cfg);
+    if (!bad) bad = rfchain_osc_check(cfg);
+    if (bad) { g_rf_err = bad; return MCRX_EINVAL; }
+    rfchain_phase_integers(cfg, steps, phases, coef);
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_rfchain_create(mcrx_hip_rfchain_t *out, const mcrx_hip_rfchain_config *cfg)
+{
+    if (!out) { g_rf_err = "null pointer"; return MCRX_EINVAL; }
+    *out = nullptr;
+    if (!cfg) { g_rf_err = "null configuration"; return MCRX_EINVAL; }
+    if (const char *bad = rfchain_check(cfg)) { g_rf_err = bad; return MCRX_EINVAL; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { g_rf_err = "no HIP device (no CPU fallback)"; return MCRX_EHIP; }
+    mcrx_hip_rfchain_t q = new mcrx_hip_rfchain_s();
+    q->device = current_device();
+    q->cfg = *cfg;
+    if (cfg->stages & MCRX_RFCHAIN_OSCILLATOR) {
+        q->pt.S = cfg->pn_sinusoids;
+        rfchain_phase_integers(cfg, q->pt.step, q->pt.phase, &q->pt.c);
+        q->cap = cfg->pn_table_rows ? cfg->pn_table_rows : RFCHAIN_DEFAULT_ROWS;
+    }
+    if (cfg->output_format == IQ_SC16) {
+        const hipError_t e = q->clip.ensure();
+        if (e != hipSuccess) { g_rf_err = std::string("clip counter: ") + hipGetErrorString(e); mcrx_hip_rfchain_destroy(q); return MCRX_EHIP; }
+    }
+    *out = q;
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_rfchain_destroy(mcrx_hip_rfchain_t q)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) return MCRX_OK;
+    (void)hipDeviceSynchronize();
+    if (q->tab) (void)hipFree(q->tab);
+    q->clip.release();
+    delete q;
+    return MCRX_OK;
+}
+
+extern "C" unsigned mcrx_hip_rfchain_input_format(mcrx_hip_rfchain_t q) { return q ? q->cfg.input_format : 0u; }
+extern "C" unsigned mcrx_hip_rfchain_output_format(mcrx_hip_rfchain_t q) { return q ? q->cfg.output_format : 0u; }
+
+template <int FIN, int FOUT>
+static void rfchain_launch(uint32_t stages, const RfchainArgs &a, dim3 grid, hipStream_t st)
+{
+    switch (stages) {
+#define RFCHAIN_CASE(S) case S: hipLaunchKernelGGL((rfchain_kernel<S, FIN, FOUT>), grid, dim3(256), 0, st, a); break;
+    RFCHAIN_CASE(0) RFCHAIN_CASE(1) RFCHAIN_CASE(2) RFCHAIN_CASE(3) RFCHAIN_CASE(4) RFCHAIN_CASE(5) RFCHAIN_CASE(6) RFCHAIN_CASE(7)
+#undef RFCHAIN_CASE
+    }
+}
+
+// rows of the table the samples pos .. pos + n - 1 read (n >= 1): their own grid rows and the one behind the last
+static uint64_t rfchain_rows(uint64_t pos, uint64_t n, uint32_t L) { return (((pos & (((uint64_t)1 << L) - 1)) + n - 1) >> L) + 2; }
+
+extern "C" int mcrx_hip_rfchain_execute_device(mcrx_hip_rfchain_t q, const void *d_in, uint64_t first_sample, size_t n, void *d_out, void *stream)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_rf_err = "null handle"; return MCRX_EINVAL; }
+    if (!d_in || !d_out) { g_rf_err = "null buffer"; return MCRX_EINVAL; }
+    const mcrx_hip_rfchain_config &c = q->cfg;
+    const bool in16 = c.input_format == IQ_SC16, out16 = c.output_format == IQ_SC16;
+    const uintptr_t pi = reinterpret_cast<uintptr_t>(d_in), po = reinterpret_cast<uintptr_t>(d_out);
+    if (pi & (in16 ? 3u : 7u)) { g_rf_err = in16 ? "d_in must be 4-byte aligned" : "d_in must be 8-byte aligned"; return MCRX_EINVAL; }
+    if (po & (out16 ? 3u : 7u)) { g_rf_err = out16 ? "d_out must be 4-byte aligned" : "d_out must be 8-byte aligned"; return MCRX_EINVAL; }
+    if (n > ((size_t)1 << 32)) { g_rf_err = "at most 2^32 samples a call"; return MCRX_EINVAL; }      // (a lane per pair, 2^31 lanes a launch)
+    const size_t si = in16 ? 4u : 8u, so = out16 ? 4u : 8u;
+    if (pi < po + n * so && po < pi + n * si && !(pi == po && in16 == out16)) {
+        g_rf_err = "d_in and d_out overlap: in-place use takes d_in == d_out and equal formats";
+        return MCRX_EINVAL;
+    }
+    if (n == 0) return MCRX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const bool osc = (c.stages & MCRX_RFCHAIN_OSCILLATOR) != 0;
+    const uint32_t L = c.pn_log2_block;
+    uint32_t cap = 0;                                                   // oscillator: the rows of the table a span may use
+    if (osc) {
+        const uint64_t want = rfchain_rows(first_sample, n, L);
+        cap = (uint32_t)(want < q->cap ? want : q->cap);
+        if (cap > q->tab_rows) {                                        // grow (hipFree waits for the calls in flight); steady state: never
+            const uint64_t twice = 2ull * q->tab_rows < q->cap ? 2ull * q->tab_rows : q->cap;
+            const uint32_t rows = (uint32_t)(twice > cap ? twice : cap);
+            if (q->tab) { RFCHK(hipFree(q->tab)); q->tab = nullptr; q->tab_rows = 0; }
+            RFCHK(hipMalloc((void **)&q->tab, (size_t)rows * sizeof(float)));
+            q->tab_rows = rows;
+        }
+    }
+    RfchainArgs a = {};
+    a.clip = q->clip.device(); a.order = c.order;
+    a.ar = c.alpha_re; a.ai = c.alpha_im; a.br = c.beta_re; a.bi = c.beta_im; a.dr = c.dc_re; a.di = c.dc_im;
+    if (c.stages & MCRX_RFCHAIN_AMPLIFIER) { a.inv_a2 = rfchain_inv_sat2(c.amp_sat); a.amp_gain = c.amp_gain; a.ampm = c.amp_ampm; a.smooth = c.amp_smooth; }
+    a.gain = c.gain;
+    // without the oscillator one span; with it, spans of at most cap - 1 grid intervals: table kernel -> samples' kernel each.
+    // The operator is a function of the absolute index, so the spans are invisible in the output.
+    uint64_t pos = first_sample;
+    for (size_t off = 0; off < n; ) {
+        size_t m = n - off;
+        if (osc) {
+            const uint64_t avail = ((uint64_t)(cap - 1) << L) - (pos & (((uint64_t)1 << L) - 1));
+            m = m < avail ? m : (size_t)avail;
+            a.L = L; a.row0 = pos >> L; a.rows = (uint32_t)rfchain_rows(pos, m, L); a.tab = q->tab;
+            a.finv = std::ldexp(1.0f, -(int)L);
+            hipLaunchKernelGGL(rfchain_phase_kernel, dim3((a.rows + 255) / 256), dim3(256), 0, st, q->pt, q->tab, a.row0, a.rows, L);
+            RFCHK(hipGetLastError());
+        }
+        a.in = static_cast<const char *>(d_in) + off * si;
+        a.out = static_cast<char *>(d_out) + off * so;
+        a.pos = pos; a.n = m;
+        const uint64_t pairs = ((pos & 1u) + m + 1) >> 1;
+        const dim3 grid((unsigned)((pairs + 255) / 256));
+        if (in16) { if (out16) rfchain_launch<IQ_SC16, IQ_SC16>(c.stages, a, grid, st); else rfchain_launch<IQ_SC16, IQ_CF32>(c.stages, a, grid, st); }
+        else      { if (out16) rfchain_launch<IQ_CF32, IQ_SC16>(c.stages, a, grid, st); else rfchain_launch<IQ_CF32, IQ_CF32>(c.stages, a, grid, st); }
+        RFCHK(hipGetLastError());
+        pos += m;
+        off += m;
+    }
+    if (out16) RFCHK(q->clip.mark(st));
+    return MCRX_OK;
+}
+
+// the table kernel on its own, into the caller's buffer: what execute_device computes for itself, for tests and measurements
+extern "C" int mcrx_hip_rfchain_phase_rows(mcrx_hip_rfchain_t q, uint64_t first_row, uint32_t rows, void *d_table, void *stream)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_rf_err = "null handle"; return MCRX_EINVAL; }
+    if (!(q->cfg.stages & MCRX_RFCHAIN_OSCILLATOR)) { g_rf_err = "the oscillator is off"; return MCRX_EINVAL; }
+    if (!d_table || (reinterpret_cast<uintptr_t>(d_table) & 3u)) { g_rf_err = "d_table must be a 4-byte aligned device buffer"; return MCRX_EINVAL; }
+    if (rows == 0) return MCRX_OK;
+    hipLaunchKernelGGL(rfchain_phase_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, q->pt,
+                       static_cast<float *>(d_table), first_row, rows, q->cfg.pn_log2_block);
+    RFCHK(hipGetLastError());
+    return MCRX_OK;
+}
+
+extern "C" int mcrx_hip_rfchain_clipped(mcrx_hip_rfchain_t q, uint64_t *samples, int reset)
+{
+    DevScope dev_scope_(q ? q->device : -1);
+    if (!q) { g_rf_err = "null handle"; return MCRX_EINVAL; }
+    uint64_t n = 0;
+    RFCHK(q->clip.read(&n, reset != 0));
+    if (samples) *samples = n;
+    return MCRX_OK;
+}
