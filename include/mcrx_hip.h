@@ -831,6 +831,94 @@ int      mcrx_hip_rfchain_selftest(const mcrx_hip_rfchain_config *cfg, int64_t *
 int      mcrx_hip_rfchain_phase_rows(mcrx_hip_rfchain_t q, uint64_t first_row, uint32_t rows, void *d_table, void *stream);
 const char *mcrx_hip_rfchain_last_error(void);
 
+/* ---- Receiver calibration on the wideband stream: blind DC offset and IQ correction ----
+ * What a radio front end does before its samples reach the host: it removes the LO leakage d and the conjugate image that a receive
+ * mixer u = alpha z + beta conj(z) + d leaves (the image of channel c lies in channel N - 1 - c), without knowing alpha, beta or d.
+ * A STATEFUL operator, cf32 or sc16 in, cf32 or sc16 out (or nothing out).  For every sample u[n] one pass over the data can
+ *   apply:    correct u[n] with the coefficients (m, w) the handle holds, and
+ *   measure:  add u[n] to the moments the next coefficients are made of.
+ * Coefficients and moments live in device memory and are updated by a kernel: a free-running stream never synchronises with the host.
+ * Moments, of the RAW input (feed-forward): cnt, S1 = sum u, S2 = sum u^2 (complex), P = sum |u|^2, kept as sum re, sum im,
+ *   sum re^2 - sum im^2, 2 sum re im, sum re^2 + sum im^2.  sc16 input: exact integers of the int16 components, int64 from lane to
+ *   handle; a sample adds at most 2^31, so a call that would bring the samples measured since the last update above 2^31 is refused.
+ *   cf32 input: every product is formed in fp64 from the fp32 components (exact) and summed in fp64 in a fixed order -- a lane over its
+ *   own pairs, ascending; the wave's tree; the workgroup's waves in order; one partial row per workgroup; the fold kernel over the rows
+ *   (thread t of 256 the rows t, t + 256, ... ascending, then a wave's tree and the waves in order).  No floating-point atomics.  The grid, and which samples
+ *   a workgroup takes, are a function of the call's (position, n) only.
+ * Update, one lane on the device in fp64, at a block boundary or on request, with cnt > 0:
+ *   b = (S1, S2, P) / cnt                         (sc16: times 2^-15, 2^-30, exact); a block whose means are not finite counts as
+ *                                                 degenerate and is dropped whole
+ *   R = b (first update), else R += mu_j (b - R)  mu_j = max(1 / (j + 1), 2^-forget_log2), j = earlier updates: the cumulative mean
+ *                                                 that turns exponential
+ *   the block accumulators are cleared, j += 1
+ *   m = R.s1, c2 = R.s2 - m^2, pc = R.p - |m|^2, D = pc^2 - |c2|^2
+ *   w = c2 / (pc + sqrt(D))                       for u = alpha z + beta conj(z) + d with z proper (E z^2 = 0) this is exactly
+ *                                                 beta / conj(alpha) and m = d: (u - m) - w conj(u - m) = alpha (1 - |w|^2) z
+ *   pc <= 0, D <= 0 or D not finite: the previous coefficients stay and `degenerate` goes up.
+ *   Stored: (float)m with MCRX_RFCAL_DC set, else 0; (float)w with MCRX_RFCAL_IQ set, else 0.  The central moments always use m.
+ *   While the handle is held (mcrx_hip_rfcal_hold) nothing is measured and no update runs.
+ * Apply, fp32, every product that matters one fmaf:
+ *     t  = (u.re - m.re, u.im - m.im)
+ *     y.re = fmaf(-w.re, t.re, fmaf(-w.im, t.im, t.re))
+ *     y.im = fmaf( w.re, t.im, fmaf(-w.im, t.re, t.im))
+ *     v = gain * y            (skipped when gain == 1)
+ *     out = v (cf32) or Q(v) (sc16: the shared quantiser with the shared clip count)
+ *   The integers of an sc16-out handle are Q of a cf32-out handle's floats exactly.  Until a handle has had its first update or a set,
+ *   the launches carry no apply code (known on the host, no readback): such a handle with gain 1 is load, convert, store and keeps NaN
+ *   payloads and -0.0.  In-place use (d_in == d_out, equal formats) is allowed: a lane writes only what it read.
+ * Blocks: the handle keeps the absolute position of its next sample.  period_log2 = k in 6 .. 30: block j is the samples
+ *   [j 2^k, (j + 1) 2^k) of the absolute index; a call is split there on the host and fold + update are enqueued behind each segment
+ *   that ends a block, so block j is corrected with what the blocks before it measured and the first block after a reset passes
+ *   uncorrected.  period_log2 = 0: nothing updates until mcrx_hip_rfcal_update.
+ * Cuts.  sc16 input: output and state are a function of the stream and of the absolute positions of the updates -- any cutting into
+ *   calls gives the same bits.  cf32 input: the same calls give the same bits, but DIFFERENTLY CUT CALLS GIVE COEFFICIENTS THAT DIFFER
+ *   BY THE fp64 SUMMATION ERROR (each block moment within about 2 n 2^-53 sum |term| of the exact sum, n the block's samples): the one
+ *   place this operator is weaker than the emulators' "cut anywhere".  Calls on one handle must be ordered on the device.
+ * Limitation: the estimator assumes a proper signal.  Frames that start together in mirror channels c and N - 1 - c carry the same
+ *   preamble, whose product does not average out; longer payloads dilute the bias. */
+#define MCRX_RFCAL_DC 1u
+#define MCRX_RFCAL_IQ 2u
+typedef struct mcrx_hip_rfcal_s *mcrx_hip_rfcal_t;
+typedef struct {
+    uint32_t struct_size, stages;                       /* sizeof(mcrx_hip_rfcal_config); MCRX_RFCAL_* bits */
+    uint32_t input_format, output_format;               /* 0 = cf32, 1 = sc16 */
+    uint32_t period_log2, forget_log2;                  /* 0 (manual) or 6 .. 30; 0 .. 30 */
+    float    gain;
+} mcrx_hip_rfcal_config;
+typedef struct {
+    float    m_re, m_im, w_re, w_im;                    /* the coefficients apply uses */
+    double   mean[5];                                   /* R: s1.re, s1.im, s2.re, s2.im, p */
+    double   acc[5];                                    /* cf32 input: the block accumulators S1.re, S1.im, S2.re, S2.im, P */
+    int64_t  acc_int[5];                                /* sc16 input: the same as exact integers of the int16 components */
+    uint64_t count;                                     /* samples in the block accumulators */
+    uint64_t updates, measured, degenerate;             /* j; samples measured since the reset; updates that kept the coefficients */
+} mcrx_hip_rfcal_state;
+/* MCRX_EINVAL before a device is looked for, *out cleared: null pointers, a wrong struct_size, unknown stage bits, a format that is not
+ * 0 or 1, period_log2 other than 0 or 6 .. 30, forget_log2 above 30, a gain that is not finite. */
+int      mcrx_hip_rfcal_create(mcrx_hip_rfcal_t *out, const mcrx_hip_rfcal_config *cfg);
+int      mcrx_hip_rfcal_destroy(mcrx_hip_rfcal_t q);
+/* position := pos, and coefficients, means, accumulators and counters cleared -- without synchronising the device: the next kernel of
+ * the handle clears them.  The clip count stays. */
+int      mcrx_hip_rfcal_reset_at(mcrx_hip_rfcal_t q, uint64_t pos);
+uint64_t mcrx_hip_rfcal_position(mcrx_hip_rfcal_t q);                                /* 0 for a null handle */
+/* The next n samples of the stream, asynchronously on `stream`; d_out == NULL: measure only.  At most 2^32 samples a call.  MCRX_EINVAL,
+ * nothing written, nothing consumed, position and state as before: a null handle or d_in, a cf32 buffer not 8-byte aligned, an sc16
+ * buffer not 4-byte aligned, ranges that overlap other than d_in == d_out with equal formats, and on an sc16-in handle that is not
+ * held a call that would bring the samples measured since the last update above 2^31. */
+int      mcrx_hip_rfcal_execute_device(mcrx_hip_rfcal_t q, const void *d_in, size_t n, void *d_out, void *stream);
+int      mcrx_hip_rfcal_update(mcrx_hip_rfcal_t q, void *stream);                    /* MCRX_EINVAL when period_log2 != 0 */
+int      mcrx_hip_rfcal_hold(mcrx_hip_rfcal_t q, int on);                            /* held: launches without the measuring code */
+int      mcrx_hip_rfcal_set(mcrx_hip_rfcal_t q, float m_re, float m_im, float w_re, float w_im, void *stream);     /* finite values */
+/* waits for the handle's work on `stream` */
+int      mcrx_hip_rfcal_read(mcrx_hip_rfcal_t q, mcrx_hip_rfcal_state *out, void *stream);
+int      mcrx_hip_rfcal_clipped(mcrx_hip_rfcal_t q, uint64_t *samples, int reset);   /* mctx_hip_clipped's semantics */
+/* host, no GPU: the segments the call (pos, n) is split into -- seg_len[i], and seg_updates[i] = 1 where segment i ends a block -- the
+ * first `cap` of them written, *nseg = how many there are.  Checks cfg as create does and the call as execute does (n above 2^32, the
+ * 2^31 guard of an sc16-in handle that has measured nothing since its last update). */
+int      mcrx_hip_rfcal_selftest(const mcrx_hip_rfcal_config *cfg, uint64_t pos, uint64_t n, uint64_t *seg_len, uint32_t *seg_updates,
+                                 size_t cap, uint64_t *nseg);
+const char *mcrx_hip_rfcal_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,19 @@ _EXPORTS = {
     "mcrx_hip_rfchain_selftest": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "mcrx_hip_rfchain_phase_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mcrx_hip_rfchain_last_error": (C.c_char_p, []),
+    "mcrx_hip_rfcal_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcrx_hip_rfcal_destroy": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_rfcal_reset_at": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "mcrx_hip_rfcal_position": (C.c_uint64, [C.c_void_p]),
+    "mcrx_hip_rfcal_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_rfcal_update": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mcrx_hip_rfcal_hold": (C.c_int, [C.c_void_p, C.c_int]),
+    "mcrx_hip_rfcal_set": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "mcrx_hip_rfcal_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_rfcal_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
+    "mcrx_hip_rfcal_selftest": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_size_t,
+                                          C.POINTER(C.c_uint64)]),
+    "mcrx_hip_rfcal_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -1068,6 +1081,182 @@ class rfchain(object):
     def close(self):
         if self._h:
             lib().mcrx_hip_rfchain_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+RFCAL_DC, RFCAL_IQ = 1, 2      # MCRX_RFCAL_* stage bits
+
+
+class RfcalConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("stages", C.c_uint32), ("input_format", C.c_uint32), ("output_format", C.c_uint32),
+                ("period_log2", C.c_uint32), ("forget_log2", C.c_uint32), ("gain", C.c_float)]
+
+
+class RfcalState(C.Structure):
+    _fields_ = [("m_re", C.c_float), ("m_im", C.c_float), ("w_re", C.c_float), ("w_im", C.c_float), ("mean", C.c_double * 5),
+                ("acc", C.c_double * 5), ("acc_int", C.c_int64 * 5), ("count", C.c_uint64), ("updates", C.c_uint64),
+                ("measured", C.c_uint64), ("degenerate", C.c_uint64)]
+
+
+def rfcal_config(dc=True, iq=True, period_log2=0, forget_log2=30, gain=1.0, input_format="cf32", output_format="cf32"):
+    """The mcrx_hip_rfcal_config of rfcal's arguments.  ValueError for a malformed argument; the values themselves are judged by the
+    library (mcrx_hip_rfcal_create, before it looks for a device)."""
+    def whole(v, name):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < (1 << 32):
+            raise ValueError("%s must be a whole number, 0 .. 2^32 - 1" % name)
+        return int(v)
+    c = RfcalConfig()
+    c.struct_size = C.sizeof(RfcalConfig)
+    if not isinstance(dc, (bool, np.bool_)) or not isinstance(iq, (bool, np.bool_)):
+        raise ValueError("dc and iq are True or False")
+    c.stages = (RFCAL_DC if dc else 0) | (RFCAL_IQ if iq else 0)
+    c.input_format = _format_code(input_format, INPUT_FORMATS, "input_format")
+    c.output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
+    c.period_log2, c.forget_log2 = whole(period_log2, "period_log2"), whole(forget_log2, "forget_log2")
+    c.gain = float(gain)
+    return c
+
+
+def rfcal_segments(cfg, pos, n, cap=None):
+    """(lengths, ends_block) of the segments the library splits the call (pos, n) of an RfcalConfig into (mcrx_hip_rfcal_selftest; host
+    only); at most `cap` of them are listed (default: all).  ValueError where execute would refuse the call."""
+    nseg = C.c_uint64(0)
+    err = lib().mcrx_hip_rfcal_last_error
+    _raise_rc(lib().mcrx_hip_rfcal_selftest(C.addressof(cfg), int(pos) % (1 << 64), int(n), None, None, 0, C.byref(nseg)),
+              "mcrx_hip_rfcal_selftest", err)
+    k = int(nseg.value) if cap is None else min(int(cap), int(nseg.value))
+    lens, ends = (C.c_uint64 * max(k, 1))(), (C.c_uint32 * max(k, 1))()
+    _raise_rc(lib().mcrx_hip_rfcal_selftest(C.addressof(cfg), int(pos) % (1 << 64), int(n), lens, ends, k, C.byref(nseg)),
+              "mcrx_hip_rfcal_selftest", err)
+    return [int(v) for v in lens[:k]], [bool(v) for v in ends[:k]]
+
+
+def rfcal_as_mixer(m, w):
+    """The rfchain mixer dict(alpha, beta, dc) that applies the correction (u - m) - w conj(u - m) of a finished calibration:
+    rfchain(order="rx", mixer=rfcal_as_mixer(m, w)) is the frozen corrector."""
+    m, w = complex(m), complex(w)
+    return dict(alpha=1.0 + 0.0j, beta=-w, dc=-m + w * m.conjugate())
+
+
+class rfcal(object):
+    """Receiver calibration on the wideband stream (mcrx_hip_rfcal_*): blind DC offset and IQ correction.
+
+        rfcal(dc=True, iq=True, period_log2=0, forget_log2=30, gain=1.0, input_format="cf32", output_format="cf32")
+
+    Stateful: the handle keeps the absolute position of its next sample, the moments of the raw input and the coefficients (m, w) made
+    of them, all on the device.  execute(x) corrects x with the coefficients the handle holds and measures it for the next ones;
+    measure(x) only measures.  period_log2 = k in 6 .. 30: the coefficients are renewed by themselves at every multiple of 2^k of the
+    absolute index; 0: by update().  The running means are the cumulative mean of the blocks until 2^-forget_log2 is the larger weight.
+    Calls on one handle must be ordered on the device.  sc16 tensors are contiguous int16 of shape (n, 2)."""
+
+    def __init__(self, dc=True, iq=True, period_log2=0, forget_log2=30, gain=1.0, input_format="cf32", output_format="cf32"):
+        self._h = C.c_void_p()
+        c = rfcal_config(dc, iq, period_log2, forget_log2, gain, input_format, output_format)
+        rc = lib().mcrx_hip_rfcal_create(C.byref(self._h), C.addressof(c))
+        if rc != MCRX_OK:
+            self._h = C.c_void_p()
+            self._chk(rc, "mcrx_hip_rfcal_create")
+        self.config, self.input_format, self.output_format = c, int(c.input_format), int(c.output_format)
+
+    @staticmethod
+    def _chk(rc, name):
+        _raise_rc(rc, name, lib().mcrx_hip_rfcal_last_error)
+
+    def _samples(self, x):
+        import torch
+        if self.input_format == INPUT_FORMATS["sc16"]:
+            n = _sc16_device_samples(x, "calibration")
+        else:
+            if x.dtype != torch.complex64:
+                raise TypeError("this calibration takes complex64 device tensors, not %s" % x.dtype)
+            n = int(x.numel())
+        if not x.is_cuda or not x.is_contiguous():
+            raise ValueError("device samples must be contiguous CUDA tensors")
+        return n
+
+    def execute(self, x, out=None, stream=None):
+        """x: the next n samples of the stream, a contiguous CUDA tensor: complex64, or on an sc16-in handle int16 of shape (n, 2).
+        out (optional): where the corrected samples go, in the output format, with room for n; `out is x` is allowed with equal
+        formats, any other overlap is refused.  Returns the n samples written.  Asynchronous on `stream` (default: torch's current
+        stream of x's device)."""
+        import torch
+        out16 = self.output_format == OUTPUT_FORMATS["sc16"]
+        n = self._samples(x)
+        if out is None:
+            out = _empty_samples(n, self.output_format, x.device)
+        else:
+            if out.dtype != (torch.int16 if out16 else torch.complex64):
+                raise TypeError("out must be %s for this calibration" % ("int16" if out16 else "complex64"))
+            if not out.is_cuda or not out.is_contiguous() or int(out.numel()) < (2 * n if out16 else n):
+                raise ValueError("out must be a contiguous CUDA tensor with room for %d samples" % n)
+        if n == 0:              # (an empty tensor has no address to pass)
+            return out.view(-1, 2)[:0] if out16 else out.view(-1)[:0]
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        self._chk(lib().mcrx_hip_rfcal_execute_device(self._h, _dptr(x), n, _dptr(out), _stream_ptr(stream)), "mcrx_hip_rfcal_execute_device")
+        return out.view(-1, 2)[:n] if out16 else out.view(-1)[:n]
+
+    def measure(self, x, stream=None):
+        """The next n samples of the stream, measured only (nothing is written); returns n."""
+        import torch
+        n = self._samples(x)
+        if n:
+            if stream is None:
+                stream = torch.cuda.current_stream(x.device)
+            self._chk(lib().mcrx_hip_rfcal_execute_device(self._h, _dptr(x), n, None, _stream_ptr(stream)), "mcrx_hip_rfcal_execute_device")
+        return n
+
+    @staticmethod
+    def _current(stream):
+        import torch
+        return _stream_ptr(torch.cuda.current_stream() if stream is None else stream)
+
+    def update(self, stream=None):
+        """Make the coefficients of what has been measured (period_log2 = 0 handles only: ValueError otherwise)."""
+        self._chk(lib().mcrx_hip_rfcal_update(self._h, self._current(stream)), "mcrx_hip_rfcal_update")
+
+    def hold(self, on=True):
+        """While held the handle measures nothing and no update runs: execute only applies."""
+        self._chk(lib().mcrx_hip_rfcal_hold(self._h, 1 if on else 0), "mcrx_hip_rfcal_hold")
+
+    def set(self, m, w, stream=None):
+        """Write the coefficients: the DC offset m and the image coefficient w (complex, finite)."""
+        m, w = complex(m), complex(w)
+        self._chk(lib().mcrx_hip_rfcal_set(self._h, m.real, m.imag, w.real, w.imag, self._current(stream)), "mcrx_hip_rfcal_set")
+
+    def read(self, stream=None):
+        """The handle's state as a dict (waits for the handle's work on `stream`): m, w (complex, the fp32 coefficients), mean (the
+        five running means s1.re, s1.im, s2.re, s2.im, p), acc (the block accumulators: exact Python ints on an sc16-in handle, floats
+        otherwise), count, updates, measured, degenerate, and irr_db = -20 log10 |w| (inf while w is 0)."""
+        s = RfcalState()
+        self._chk(lib().mcrx_hip_rfcal_read(self._h, C.addressof(s), self._current(stream)), "mcrx_hip_rfcal_read")
+        w = complex(s.w_re, s.w_im)
+        acc = [int(v) for v in s.acc_int] if self.input_format == INPUT_FORMATS["sc16"] else [float(v) for v in s.acc]
+        return dict(m=complex(s.m_re, s.m_im), w=w, mean=[float(v) for v in s.mean], acc=acc, count=int(s.count), updates=int(s.updates),
+                    measured=int(s.measured), degenerate=int(s.degenerate), irr_db=-20.0 * math.log10(abs(w)) if abs(w) > 0.0 else math.inf)
+
+    def reset_at(self, pos):
+        """The next sample is absolute sample pos; coefficients, means, accumulators and counters are cleared (no synchronisation)."""
+        self._chk(lib().mcrx_hip_rfcal_reset_at(self._h, int(pos) % (1 << 64)), "mcrx_hip_rfcal_reset_at")
+
+    def position(self):
+        return int(lib().mcrx_hip_rfcal_position(self._h))
+
+    def clipped(self, reset=False):
+        """Samples clipped by the sc16-out calls since the count was last reset (waits for the last such call only); 0 on a cf32 one."""
+        n = C.c_uint64(0)
+        self._chk(lib().mcrx_hip_rfcal_clipped(self._h, C.byref(n), 1 if reset else 0), "mcrx_hip_rfcal_clipped")
+        return int(n.value)
+
+    def close(self):
+        if self._h:
+            lib().mcrx_hip_rfcal_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
