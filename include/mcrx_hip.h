@@ -919,6 +919,69 @@ int      mcrx_hip_rfcal_selftest(const mcrx_hip_rfcal_config *cfg, uint64_t pos,
                                  size_t cap, uint64_t *nseg);
 const char *mcrx_hip_rfcal_last_error(void);
 
+/* ---- Crest-factor reduction on the wideband stream: clip-and-filter ahead of DAC and amplifier ----
+ * The transmitter's channels add coherently in their preambles and pilots: its peaks reach several times the rms.  This stage takes
+ * what exceeds an amplitude A out of the stream, band-limited by a real symmetric low-pass so that the correction stays inside the
+ * band the channels occupy (|f| <= 1/4 cycle per sample) and does not splatter into the outer half.  It buys headroom and containment
+ * with in-band error: the EVM of every channel gets worse.  cf32 in, cf32 or sc16 out.
+ * Configuration: threshold A; half_len H in 1 .. 64 and the taps h[0 .. H] of the filter h[-k] = h[k]; passes P in 1 .. 4; gain;
+ * output_format.  A2 = fp32(A * A), the product made on the host in double.  ONE PASS maps a sequence x to y, all in fp32:
+ *     t    = fmaf(x.re, x.re, x.im * x.im)
+ *     e[n] = (0, 0)                     unless t > A2 (so a NaN gives 0)
+ *            (s x.re, s x.im),          s = 1 - A / sqrtf(t), division and root correctly rounded
+ *     c[n] = acc_H per component:       acc_0 = h[0] * e[n];  acc_k = fmaf(h[k], e[n-k] + e[n+k], acc_{k-1}),  k = 1 .. H
+ *     y[n] = x[n] - c[n]
+ * P passes run one behind the other.  Behind the last v = gain * y (one multiply per component; skipped when gain == 1), and
+ * out = v (cf32) or Q(v) (sc16: the shared quantiser as it stands, with the shared clip count).
+ * Nothing depends on the absolute index: the operator is STATELESS and NON-CAUSAL.  halo = P * H; a call reads n + 2 * halo input
+ * samples and writes n output samples, d_out[i] belongs to d_in[i + halo]: the caller supplies lead and tail, the way
+ * mctx_hip_synthesize_tiles takes its lead.  At the two ends of a stream lead and tail are zeros.  Consequences:
+ *   - a stream cut anywhere, each piece with its halos, gives the bits of one call;
+ *   - the integers of an sc16-out handle are Q of a cf32-out handle's floats exactly;
+ *   - where no sample within reach exceeds A, c = +0 and y = x bit for bit for every word that is not a NaN, -0.0 included (a NaN
+ *     stays a NaN): h[0] * (+0) is a zero, fmaf(h[k], +0, zero) keeps it a zero, and that zero is +0 as soon as one tap is not
+ *     negative -- DESIGN.md section 4.20 works the signs out.  A launch therefore skips the filter for the waves whose window
+ *     holds no sample above A, which changes no bit.  (With EVERY tap h[0 .. H] negative c = -0, x = -0.0 comes out as +0.0 as
+ *     the definition says, and the launches of such a handle skip nothing.)
+ *   - in-place use is refused: neighbours are read.
+ * With P > 1 the passes run as one launch each through scratch buffers the handle owns (grown on demand); pass p covers the samples
+ * [-(P - 1 - p) H, n + (P - 1 - p) H) around the output.  Because of those buffers, calls on ONE handle with P > 1 must be ordered
+ * on the device (one stream, or events of the caller's), as with a userclock; handles with P = 1 are free of this.
+ * Statistics, integer atomics only, none issued while nothing happens:
+ *   over[p]  samples with t > A2 at the input of pass p, counted over the samples of the caller's n outputs only, never the halos;
+ *   peak2    the largest |y|^2 = fmaf(y.re, y.re, y.im * y.im) of the last pass's n outputs, before the gain (a NaN does not count).
+ * Both are independent of order, hence of cuts and of the launch geometry. */
+#define MCRX_CFR_MAX_HALF_LEN 64
+#define MCRX_CFR_MAX_PASSES   4
+typedef struct mcrx_hip_cfr_s *mcrx_hip_cfr_t;
+typedef struct {
+    uint32_t struct_size, half_len, passes, output_format;      /* sizeof(mcrx_hip_cfr_config); H; P; 0 = cf32, 1 = sc16 */
+    float    threshold, gain;                                   /* A, against the full scale 1.0; v = gain y */
+    float    taps[MCRX_CFR_MAX_HALF_LEN + 1];                   /* h[0 .. H]; the entries behind h[H] are not looked at */
+} mcrx_hip_cfr_config;
+/* MCRX_EINVAL before a device is looked for, *out cleared: null pointers, a wrong struct_size, half_len outside 1 .. 64, passes
+ * outside 1 .. 4, an output format that is not 0 or 1, a threshold that is not finite and positive or whose A2 is not a finite
+ * positive fp32, a gain or one of the taps h[0 .. H] that is not finite. */
+int      mcrx_hip_cfr_create(mcrx_hip_cfr_t *out, const mcrx_hip_cfr_config *cfg);
+int      mcrx_hip_cfr_destroy(mcrx_hip_cfr_t q);
+unsigned mcrx_hip_cfr_halo(mcrx_hip_cfr_t q);                                        /* P * H; 0 for a null handle */
+unsigned mcrx_hip_cfr_output_format(mcrx_hip_cfr_t q);                               /* 0 for a null handle */
+/* n + 2 * halo cf32 samples at d_in -> n samples at d_out (the handle's output format), asynchronously on `stream` (NULL = the
+ * default stream).  n == 0: MCRX_OK, nothing done.  MCRX_EINVAL, nothing written: a null handle or buffer, a cf32 buffer not 8-byte
+ * aligned, an sc16 output not 4-byte aligned, ranges that overlap in any way (d_in == d_out included), n + 2 * halo > 2^32. */
+int      mcrx_hip_cfr_execute_device(mcrx_hip_cfr_t q, const void *d_in, size_t n, void *d_out, void *stream);
+/* mctx_hip_clipped's semantics; counter and event exist only on a handle with sc16 output; always 0 on a cf32 one */
+int      mcrx_hip_cfr_clipped(mcrx_hip_cfr_t q, uint64_t *samples, int reset);
+/* over[p], p < 4 (0 behind the handle's last pass) and peak2 since the last reset; waits for the handle's last call only.  Either
+ * pointer may be null. */
+int      mcrx_hip_cfr_stats(mcrx_hip_cfr_t q, uint64_t over[MCRX_CFR_MAX_PASSES], float *peak2, int reset);
+/* host, no GPU: the taps of a windowed-sinc low-pass, h[k] = 2 fc sinc(2 fc k) w(k), k = 0 .. half_len, fc = cutoff in cycles per
+ * sample, w(k) = I0(beta sqrt(1 - (2 k / (2 half_len + 1))^2)) / I0(beta) (the transmitter's Kaiser window), scaled so that
+ * h[0] + 2 sum_{k >= 1} h[k] = 1; all in double, then rounded to fp32.  MCRX_EINVAL: a null h, half_len outside 1 .. 64, cutoff
+ * outside (0, 0.5), beta < 0, values that are not finite. */
+int      mcrx_hip_cfr_design(uint32_t half_len, double cutoff, double beta, float *h);
+const char *mcrx_hip_cfr_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,15 @@ _EXPORTS = {
     "mcrx_hip_rfcal_selftest": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_size_t,
                                           C.POINTER(C.c_uint64)]),
     "mcrx_hip_rfcal_last_error": (C.c_char_p, []),
+    "mcrx_hip_cfr_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcrx_hip_cfr_destroy": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_cfr_halo": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_cfr_output_format": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_cfr_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_cfr_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
+    "mcrx_hip_cfr_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.c_int]),
+    "mcrx_hip_cfr_design": (C.c_int, [C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_float)]),
+    "mcrx_hip_cfr_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -1081,6 +1090,133 @@ class rfchain(object):
     def close(self):
         if self._h:
             lib().mcrx_hip_rfchain_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+CFR_MAX_HALF_LEN, CFR_MAX_PASSES = 64, 4      # MCRX_CFR_MAX_HALF_LEN, MCRX_CFR_MAX_PASSES
+
+
+class CfrConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("half_len", C.c_uint32), ("passes", C.c_uint32), ("output_format", C.c_uint32),
+                ("threshold", C.c_float), ("gain", C.c_float), ("taps", C.c_float * (CFR_MAX_HALF_LEN + 1))]
+
+
+def cfr_lowpass(half_len, cutoff, beta):
+    """The taps h[0 .. half_len] (float32) of the library's Kaiser-windowed low-pass of 2 half_len + 1 taps with its edge at `cutoff`
+    cycles per sample, scaled to unit gain at zero frequency (mcrx_hip_cfr_design; host only)."""
+    if int(half_len) != half_len or not 1 <= int(half_len) <= CFR_MAX_HALF_LEN:
+        raise ValueError("half_len must be a whole number, 1 .. %d" % CFR_MAX_HALF_LEN)
+    h = (C.c_float * (CFR_MAX_HALF_LEN + 1))()
+    _raise_rc(lib().mcrx_hip_cfr_design(int(half_len), float(cutoff), float(beta), h), "mcrx_hip_cfr_design", lib().mcrx_hip_cfr_last_error)
+    return np.array(h[:int(half_len) + 1], np.float32)
+
+
+def cfr_threshold(papr_db, rms):
+    """The threshold A that lies papr_db above a signal of amplitude `rms`: an absolute amplitude against the full scale 1.0."""
+    return float(rms) * 10.0 ** (float(papr_db) / 20.0)
+
+
+def cfr_config(threshold, taps=None, half_len=31, cutoff=0.28, beta=5.65, passes=1, gain=1.0, output_format="cf32"):
+    """The mcrx_hip_cfr_config of cfr's arguments.  ValueError for a malformed argument; the values themselves are judged by the
+    library (mcrx_hip_cfr_create, before it looks for a device)."""
+    c = CfrConfig()
+    c.struct_size = C.sizeof(CfrConfig)
+    c.output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
+    if int(passes) != passes or not 0 <= int(passes) < (1 << 32):
+        raise ValueError("passes must be a whole number")
+    c.passes, c.threshold, c.gain = int(passes), float(threshold), float(gain)
+    if taps is None:
+        taps = cfr_lowpass(half_len, cutoff, beta)
+    taps = np.asarray(taps)
+    if taps.ndim != 1 or not 2 <= taps.size <= CFR_MAX_HALF_LEN + 1 or taps.dtype.kind not in "fiu":
+        raise ValueError("taps are the real numbers h[0 .. H], H = 1 .. %d" % CFR_MAX_HALF_LEN)
+    c.half_len = int(taps.size) - 1
+    for k, v in enumerate(taps):
+        c.taps[k] = float(v)
+    return c
+
+
+class cfr(object):
+    """Crest-factor reduction on the wideband stream (mcrx_hip_cfr_*): clip-and-filter between the transmitter and its DAC or amplifier.
+
+        cfr(threshold, taps=None, half_len=31, cutoff=0.28, beta=5.65, passes=1, gain=1.0, output_format="cf32")
+
+    What exceeds the amplitude `threshold` (absolute, against the full scale 1.0: cfr_threshold makes it of a level over the rms) is
+    taken out of the stream, band-limited by the symmetric low-pass `taps` = h[0 .. H] (default: cfr_lowpass(half_len, cutoff, beta)),
+    `passes` times over; then the gain, then cf32 or sc16.  It lowers the peaks and keeps the correction inside the occupied band; it
+    adds in-band error to every channel.  The operator is stateless and non-causal: execute(x) takes n + 2 halo samples and returns
+    the n in the middle, so a stream may be cut anywhere when each piece brings `halo` samples of its neighbours (zeros at the ends
+    of the stream: pad=True).  With passes > 1 the calls on one handle must be ordered on the device."""
+
+    def __init__(self, threshold, taps=None, half_len=31, cutoff=0.28, beta=5.65, passes=1, gain=1.0, output_format="cf32"):
+        self._h = C.c_void_p()
+        c = cfr_config(threshold, taps, half_len, cutoff, beta, passes, gain, output_format)
+        rc = lib().mcrx_hip_cfr_create(C.byref(self._h), C.addressof(c))
+        if rc != MCRX_OK:
+            self._h = C.c_void_p()
+            self._chk(rc, "mcrx_hip_cfr_create")
+        self.config, self.output_format, self.passes, self.half_len = c, int(c.output_format), int(c.passes), int(c.half_len)
+        self.halo = int(lib().mcrx_hip_cfr_halo(self._h))
+        self.taps = np.array(c.taps[:self.half_len + 1], np.float32)
+
+    @staticmethod
+    def _chk(rc, name):
+        _raise_rc(rc, name, lib().mcrx_hip_cfr_last_error)
+
+    def execute(self, x, out=None, pad=False, stream=None):
+        """x: a contiguous complex64 CUDA tensor of n + 2 halo samples -- the n samples to correct with `halo` of their neighbours on
+        either side -- or, with pad=True, a whole stream of n samples, which gets zeros there.  out (optional): where the n samples
+        go, in the output format; it must not overlap x.  Returns the n samples written.  Asynchronous on `stream` (default: torch's
+        current stream of x's device)."""
+        import torch
+        out16 = self.output_format == OUTPUT_FORMATS["sc16"]
+        if x.dtype != torch.complex64:
+            raise TypeError("cfr takes complex64 device tensors, not %s" % x.dtype)
+        if not x.is_cuda or not x.is_contiguous():
+            raise ValueError("device samples must be contiguous CUDA tensors")
+        if pad:
+            padded = torch.zeros(int(x.numel()) + 2 * self.halo, dtype=torch.complex64, device=x.device)
+            padded[self.halo:self.halo + int(x.numel())].copy_(x.view(-1))
+            x = padded
+        n = int(x.numel()) - 2 * self.halo
+        if n < 0:
+            raise ValueError("x must hold the halo on either side: at least %d samples" % (2 * self.halo))
+        if out is None:
+            out = _empty_samples(n, self.output_format, x.device)
+        else:
+            if out.dtype != (torch.int16 if out16 else torch.complex64):
+                raise TypeError("out must be %s for this handle" % ("int16" if out16 else "complex64"))
+            if not out.is_cuda or not out.is_contiguous() or int(out.numel()) < (2 * n if out16 else n):
+                raise ValueError("out must be a contiguous CUDA tensor with room for %d samples" % n)
+        if n == 0:              # (an empty tensor has no address to pass)
+            return out.view(-1, 2)[:0] if out16 else out.view(-1)[:0]
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        self._chk(lib().mcrx_hip_cfr_execute_device(self._h, _dptr(x), n, _dptr(out), _stream_ptr(stream)), "mcrx_hip_cfr_execute_device")
+        return out.view(-1, 2)[:n] if out16 else out.view(-1)[:n]
+
+    def clipped(self, reset=False):
+        """Samples clipped by the sc16-out calls since the count was last reset (waits for the last such call only); 0 on a cf32 one."""
+        n = C.c_uint64(0)
+        self._chk(lib().mcrx_hip_cfr_clipped(self._h, C.byref(n), 1 if reset else 0), "mcrx_hip_cfr_clipped")
+        return int(n.value)
+
+    def stats(self, reset=False):
+        """(over, peak2) since the last reset: over[p] = samples above the threshold at the input of pass p, among the samples of the
+        outputs only; peak2 = the largest |y|^2 behind the last pass, before the gain.  Waits for the handle's last call."""
+        over, peak2 = (C.c_uint64 * CFR_MAX_PASSES)(), C.c_float(0.0)
+        self._chk(lib().mcrx_hip_cfr_stats(self._h, over, C.byref(peak2), 1 if reset else 0), "mcrx_hip_cfr_stats")
+        return [int(v) for v in over[:self.passes]], float(peak2.value)
+
+    def close(self):
+        if self._h:
+            lib().mcrx_hip_cfr_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
