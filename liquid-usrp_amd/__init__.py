@@ -810,7 +810,84 @@ def chanemu_cfo_step(spacings, M, num_channels):
     return int(round(float(spacings) / (M * 2 * num_channels) * 4294967296.0)) % (1 << 32)
 
 
-class chanemu(object):
+class _StreamOp(object):
+    """What the classes of the stream operators share (chanemu, rfchain, cfr, rfcal): the handle of mcrx_hip_<_op>_create, errors through
+    mcrx_hip_<_op>_last_error, the clip count, close, and what execute checks of x and out.  _what: who takes the samples, and the noun
+    of "this ..." in the messages."""
+    _op, _what, _h = None, None, None
+
+    @classmethod
+    def _call(cls, name, *args):
+        name = "mcrx_hip_%s_%s" % (cls._op, name)
+        cls._chk(getattr(lib(), name)(*args), name)
+
+    @classmethod
+    def _chk(cls, rc, name):
+        _raise_rc(rc, name, getattr(lib(), "mcrx_hip_%s_last_error" % cls._op))
+
+    def _create(self, cfg):
+        self._h = C.c_void_p()
+        try:
+            self._call("create", C.byref(self._h), C.addressof(cfg))
+        except Exception:
+            self._h = C.c_void_p()
+            raise
+
+    def _in(self, x, in16):
+        """The number of samples in x: a contiguous CUDA tensor, complex64 or (in16) int16 pairs."""
+        import torch
+        if in16:
+            n = _sc16_device_samples(x, self._what[1])
+        else:
+            if x.dtype != torch.complex64:
+                raise TypeError("%s takes complex64 device tensors, not %s" % (self._what[0], x.dtype))
+            n = int(x.numel())
+        if not x.is_cuda or not x.is_contiguous():
+            raise ValueError("device samples must be contiguous CUDA tensors")
+        return n
+
+    def _out(self, n, out, out16, device):
+        """(out, view): out as given, or made, with room for n samples of the output format, and its first n samples as execute returns them."""
+        import torch
+        if out is None:
+            out = _empty_samples(n, self.output_format, device)
+        else:
+            if out.dtype != (torch.int16 if out16 else torch.complex64):
+                raise TypeError("out must be %s for this %s" % ("int16" if out16 else "complex64", self._what[1]))
+            if not out.is_cuda or not out.is_contiguous() or int(out.numel()) < (2 * n if out16 else n):
+                raise ValueError("out must be a contiguous CUDA tensor with room for %d samples" % n)
+        return out, (out.view(-1, 2)[:n] if out16 else out.view(-1)[:n])
+
+    def _io(self, x, out, in16, out16):
+        """(n, out, view) of an execute call on x: _in, then _out.  With n == 0 there is no address to pass: execute returns the view."""
+        n = self._in(x, in16)
+        return (n,) + self._out(n, out, out16, x.device)
+
+    @staticmethod
+    def _stream(stream, x):
+        """the stream to pass: the one given, or torch's current stream of x's device"""
+        import torch
+        return _stream_ptr(torch.cuda.current_stream(x.device) if stream is None else stream)
+
+    def clipped(self, reset=False):
+        """Samples clipped by the sc16-out calls since the count was last reset (waits for the last such call only); 0 on a cf32 one."""
+        n = C.c_uint64(0)
+        self._call("clipped", self._h, C.byref(n), 1 if reset else 0)
+        return int(n.value)
+
+    def close(self):
+        if self._h:
+            getattr(lib(), "mcrx_hip_%s_destroy" % self._op)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class chanemu(_StreamOp):
     """Channel emulator on the wideband stream, between multichanneltx and multichannelrx / msresamp (mcrx_hip_chanemu_*):
 
         chanemu(taps=[(delay, complex), ...], cfo_step=0, phase0=0, gain=1.0, noise_std=0.0, seed=0, output_format="cf32")
@@ -826,8 +903,9 @@ class chanemu(object):
     value for all; the gains are updated every 2^log2_block samples and interpolated linearly between.  set_fading(None | dict) changes
     it between any two execute calls; it holds no stream state."""
 
+    _op, _what = "chanemu", ("the emulator", "emulator")
+
     def __init__(self, taps=((0, 1.0),), cfo_step=0, phase0=0, gain=1.0, noise_std=0.0, seed=0, output_format="cf32", fading=None):
-        self._h = C.c_void_p()
         output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
         taps = list(taps)
         if not 1 <= len(taps) <= CHANEMU_MAX_TAPS:
@@ -841,10 +919,7 @@ class chanemu(object):
         c.cfo_step, c.phase0 = int(cfo_step) % (1 << 32), int(phase0) % (1 << 32)
         c.gain, c.noise_std, c.seed, c.output_format = float(gain), float(noise_std), int(seed) % (1 << 64), output_format
         fading = self._fading_struct(len(taps), fading)
-        rc = lib().mcrx_hip_chanemu_create(C.byref(self._h), C.addressof(c))
-        if rc != MCRX_OK:
-            self._h = C.c_void_p()
-            self._chk(rc, "mcrx_hip_chanemu_create")
+        self._create(c)
         self.taps, self.output_format = [(int(d), complex(a)) for d, a in taps], output_format
         if fading is not None:
             self._chk(lib().mcrx_hip_chanfade_set(self._h, C.addressof(fading)), "mcrx_hip_chanfade_set")
@@ -877,35 +952,14 @@ class chanemu(object):
                   "mcrx_hip_chanfade_gains")
         return out[:, :len(self.taps)]
 
-    @staticmethod
-    def _chk(rc, name):
-        _raise_rc(rc, name, lib().mcrx_hip_chanemu_last_error)
-
     def execute(self, x, out=None, stream=None):
         """x: the next samples of the stream, a contiguous torch complex64 CUDA tensor.  out (optional): where they go -- complex64 of
         at least as many elements, or on an sc16 emulator int16 of shape (>= n, 2); it must not overlap x.  Returns the n samples
         written.  Asynchronous on `stream` (default: torch's current stream of x's device)."""
-        import torch
-        if x.dtype != torch.complex64:
-            raise TypeError("the emulator takes complex64 device tensors, not %s" % x.dtype)
-        if not x.is_cuda or not x.is_contiguous():
-            raise ValueError("device samples must be contiguous CUDA tensors")
-        n = int(x.numel())
-        sc16 = self.output_format == OUTPUT_FORMATS["sc16"]
-        if out is None:
-            out = _empty_samples(n, self.output_format, x.device)
-        else:
-            if out.dtype != (torch.int16 if sc16 else torch.complex64):
-                raise TypeError("out must be %s for this emulator" % ("int16" if sc16 else "complex64"))
-            if not out.is_cuda or not out.is_contiguous() or int(out.numel()) < (2 * n if sc16 else n):
-                raise ValueError("out must be a contiguous CUDA tensor with room for %d samples" % n)
-        if n == 0:              # (an empty tensor has no address to pass)
-            return out.view(-1, 2)[:0] if sc16 else out.view(-1)[:0]
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        self._chk(lib().mcrx_hip_chanemu_execute_device(self._h, _dptr(x), n, _dptr(out), _stream_ptr(stream)),
-                  "mcrx_hip_chanemu_execute_device")
-        return out.view(-1, 2)[:n] if sc16 else out.view(-1)[:n]
+        n, out, view = self._io(x, out, False, self.output_format == OUTPUT_FORMATS["sc16"])
+        if n:
+            self._call("execute_device", self._h, _dptr(x), n, _dptr(out), self._stream(stream, x))
+        return view
 
     def reset(self, at=0):
         """Zero history; the stream continues at absolute sample `at` (any 64-bit value): phase and noise follow from it."""
@@ -914,23 +968,6 @@ class chanemu(object):
     def position(self):
         """absolute index of the next input sample"""
         return int(lib().mcrx_hip_chanemu_position(self._h))
-
-    def clipped(self, reset=False):
-        """Samples clipped by the sc16 calls since the count was last reset (waits for the last such call only); 0 on a cf32 emulator."""
-        n = C.c_uint64(0)
-        self._chk(lib().mcrx_hip_chanemu_clipped(self._h, C.byref(n), 1 if reset else 0), "mcrx_hip_chanemu_clipped")
-        return int(n.value)
-
-    def close(self):
-        if self._h:
-            lib().mcrx_hip_chanemu_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 RFCHAIN_MIXER, RFCHAIN_OSCILLATOR, RFCHAIN_AMPLIFIER = 1, 2, 4      # MCRX_RFCHAIN_* stage bits
@@ -1013,7 +1050,7 @@ def rfchain_integers(cfg):
     return [int(v) for v in steps[:S]], [int(v) for v in phases[:S]], float(coef.value)
 
 
-class rfchain(object):
+class rfchain(_StreamOp):
     """RF front end on the wideband stream (mcrx_hip_rfchain_*): the radios at either end of the air.
 
         rfchain(order="tx", mixer=None | dict(alpha, beta, dc=0), phase_noise=None | dict(rms_deg, bandwidth, sinusoids=16,
@@ -1027,48 +1064,22 @@ class rfchain(object):
     The operator is memoryless and stateless: execute(x, first_sample) takes the absolute index of x[0], so a stream may be cut, or
     sharded in time over GPUs, anywhere.  sc16 tensors are contiguous int16 of shape (n, 2)."""
 
-    def __init__(self, order="tx", mixer=None, phase_noise=None, amplifier=None, gain=1.0, input_format="cf32", output_format="cf32"):
-        self._h = C.c_void_p()
-        c = rfchain_config(order, mixer, phase_noise, amplifier, gain, input_format, output_format)
-        rc = lib().mcrx_hip_rfchain_create(C.byref(self._h), C.addressof(c))
-        if rc != MCRX_OK:
-            self._h = C.c_void_p()
-            self._chk(rc, "mcrx_hip_rfchain_create")
-        self.config, self.input_format, self.output_format, self.stages = c, int(c.input_format), int(c.output_format), int(c.stages)
+    _op, _what = "rfchain", ("this front end", "front end")
 
-    @staticmethod
-    def _chk(rc, name):
-        _raise_rc(rc, name, lib().mcrx_hip_rfchain_last_error)
+    def __init__(self, order="tx", mixer=None, phase_noise=None, amplifier=None, gain=1.0, input_format="cf32", output_format="cf32"):
+        c = rfchain_config(order, mixer, phase_noise, amplifier, gain, input_format, output_format)
+        self._create(c)
+        self.config, self.input_format, self.output_format, self.stages = c, int(c.input_format), int(c.output_format), int(c.stages)
 
     def execute(self, x, first_sample=0, out=None, stream=None):
         """x: samples first_sample .. first_sample + n - 1 of the stream, a contiguous CUDA tensor: complex64, or on an sc16-in handle
         int16 of shape (n, 2).  out (optional): where they go, in the output format, with room for n samples; `out is x` (the same
         address) is allowed with equal formats, any other overlap is refused.  Returns the n samples written.  Asynchronous on
         `stream` (default: torch's current stream of x's device)."""
-        import torch
-        in16, out16 = self.input_format == INPUT_FORMATS["sc16"], self.output_format == OUTPUT_FORMATS["sc16"]
-        if in16:
-            n = _sc16_device_samples(x, "front end")
-        else:
-            if x.dtype != torch.complex64:
-                raise TypeError("this front end takes complex64 device tensors, not %s" % x.dtype)
-            n = int(x.numel())
-        if not x.is_cuda or not x.is_contiguous():
-            raise ValueError("device samples must be contiguous CUDA tensors")
-        if out is None:
-            out = _empty_samples(n, self.output_format, x.device)
-        else:
-            if out.dtype != (torch.int16 if out16 else torch.complex64):
-                raise TypeError("out must be %s for this front end" % ("int16" if out16 else "complex64"))
-            if not out.is_cuda or not out.is_contiguous() or int(out.numel()) < (2 * n if out16 else n):
-                raise ValueError("out must be a contiguous CUDA tensor with room for %d samples" % n)
-        if n == 0:              # (an empty tensor has no address to pass)
-            return out.view(-1, 2)[:0] if out16 else out.view(-1)[:0]
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        self._chk(lib().mcrx_hip_rfchain_execute_device(self._h, _dptr(x), int(first_sample) % (1 << 64), n, _dptr(out),
-                                                        _stream_ptr(stream)), "mcrx_hip_rfchain_execute_device")
-        return out.view(-1, 2)[:n] if out16 else out.view(-1)[:n]
+        n, out, view = self._io(x, out, self.input_format == INPUT_FORMATS["sc16"], self.output_format == OUTPUT_FORMATS["sc16"])
+        if n:
+            self._call("execute_device", self._h, _dptr(x), int(first_sample) % (1 << 64), n, _dptr(out), self._stream(stream, x))
+        return view
 
     def phase_rows(self, first_row, rows, stream=None):
         """The oscillator's table rows first_row .. first_row + rows - 1 (grid row b = n >> log2_block), in turns, as a float32 CUDA
@@ -1080,23 +1091,6 @@ class rfchain(object):
         self._chk(lib().mcrx_hip_rfchain_phase_rows(self._h, int(first_row) % (1 << 64), int(rows), _dptr(out), _stream_ptr(stream)),
                   "mcrx_hip_rfchain_phase_rows")
         return out
-
-    def clipped(self, reset=False):
-        """Samples clipped by the sc16-out calls since the count was last reset (waits for the last such call only); 0 on a cf32 one."""
-        n = C.c_uint64(0)
-        self._chk(lib().mcrx_hip_rfchain_clipped(self._h, C.byref(n), 1 if reset else 0), "mcrx_hip_rfchain_clipped")
-        return int(n.value)
-
-    def close(self):
-        if self._h:
-            lib().mcrx_hip_rfchain_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 CFR_MAX_HALF_LEN, CFR_MAX_PASSES = 64, 4      # MCRX_CFR_MAX_HALF_LEN, MCRX_CFR_MAX_PASSES
@@ -1142,7 +1136,7 @@ def cfr_config(threshold, taps=None, half_len=31, cutoff=0.28, beta=5.65, passes
     return c
 
 
-class cfr(object):
+class cfr(_StreamOp):
     """Crest-factor reduction on the wideband stream (mcrx_hip_cfr_*): clip-and-filter between the transmitter and its DAC or amplifier.
 
         cfr(threshold, taps=None, half_len=31, cutoff=0.28, beta=5.65, passes=1, gain=1.0, output_format="cf32")
@@ -1154,20 +1148,14 @@ class cfr(object):
     the n in the middle, so a stream may be cut anywhere when each piece brings `halo` samples of its neighbours (zeros at the ends
     of the stream: pad=True).  With passes > 1 the calls on one handle must be ordered on the device."""
 
+    _op, _what = "cfr", ("cfr", "handle")
+
     def __init__(self, threshold, taps=None, half_len=31, cutoff=0.28, beta=5.65, passes=1, gain=1.0, output_format="cf32"):
-        self._h = C.c_void_p()
         c = cfr_config(threshold, taps, half_len, cutoff, beta, passes, gain, output_format)
-        rc = lib().mcrx_hip_cfr_create(C.byref(self._h), C.addressof(c))
-        if rc != MCRX_OK:
-            self._h = C.c_void_p()
-            self._chk(rc, "mcrx_hip_cfr_create")
+        self._create(c)
         self.config, self.output_format, self.passes, self.half_len = c, int(c.output_format), int(c.passes), int(c.half_len)
         self.halo = int(lib().mcrx_hip_cfr_halo(self._h))
         self.taps = np.array(c.taps[:self.half_len + 1], np.float32)
-
-    @staticmethod
-    def _chk(rc, name):
-        _raise_rc(rc, name, lib().mcrx_hip_cfr_last_error)
 
     def execute(self, x, out=None, pad=False, stream=None):
         """x: a contiguous complex64 CUDA tensor of n + 2 halo samples -- the n samples to correct with `halo` of their neighbours on
@@ -1175,11 +1163,7 @@ class cfr(object):
         go, in the output format; it must not overlap x.  Returns the n samples written.  Asynchronous on `stream` (default: torch's
         current stream of x's device)."""
         import torch
-        out16 = self.output_format == OUTPUT_FORMATS["sc16"]
-        if x.dtype != torch.complex64:
-            raise TypeError("cfr takes complex64 device tensors, not %s" % x.dtype)
-        if not x.is_cuda or not x.is_contiguous():
-            raise ValueError("device samples must be contiguous CUDA tensors")
+        self._in(x, False)
         if pad:
             padded = torch.zeros(int(x.numel()) + 2 * self.halo, dtype=torch.complex64, device=x.device)
             padded[self.halo:self.halo + int(x.numel())].copy_(x.view(-1))
@@ -1187,25 +1171,10 @@ class cfr(object):
         n = int(x.numel()) - 2 * self.halo
         if n < 0:
             raise ValueError("x must hold the halo on either side: at least %d samples" % (2 * self.halo))
-        if out is None:
-            out = _empty_samples(n, self.output_format, x.device)
-        else:
-            if out.dtype != (torch.int16 if out16 else torch.complex64):
-                raise TypeError("out must be %s for this handle" % ("int16" if out16 else "complex64"))
-            if not out.is_cuda or not out.is_contiguous() or int(out.numel()) < (2 * n if out16 else n):
-                raise ValueError("out must be a contiguous CUDA tensor with room for %d samples" % n)
-        if n == 0:              # (an empty tensor has no address to pass)
-            return out.view(-1, 2)[:0] if out16 else out.view(-1)[:0]
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        self._chk(lib().mcrx_hip_cfr_execute_device(self._h, _dptr(x), n, _dptr(out), _stream_ptr(stream)), "mcrx_hip_cfr_execute_device")
-        return out.view(-1, 2)[:n] if out16 else out.view(-1)[:n]
-
-    def clipped(self, reset=False):
-        """Samples clipped by the sc16-out calls since the count was last reset (waits for the last such call only); 0 on a cf32 one."""
-        n = C.c_uint64(0)
-        self._chk(lib().mcrx_hip_cfr_clipped(self._h, C.byref(n), 1 if reset else 0), "mcrx_hip_cfr_clipped")
-        return int(n.value)
+        out, view = self._out(n, out, self.output_format == OUTPUT_FORMATS["sc16"], x.device)
+        if n:
+            self._call("execute_device", self._h, _dptr(x), n, _dptr(out), self._stream(stream, x))
+        return view
 
     def stats(self, reset=False):
         """(over, peak2) since the last reset: over[p] = samples above the threshold at the input of pass p, among the samples of the
@@ -1213,17 +1182,6 @@ class cfr(object):
         over, peak2 = (C.c_uint64 * CFR_MAX_PASSES)(), C.c_float(0.0)
         self._chk(lib().mcrx_hip_cfr_stats(self._h, over, C.byref(peak2), 1 if reset else 0), "mcrx_hip_cfr_stats")
         return [int(v) for v in over[:self.passes]], float(peak2.value)
-
-    def close(self):
-        if self._h:
-            lib().mcrx_hip_cfr_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 RFCAL_DC, RFCAL_IQ = 1, 2      # MCRX_RFCAL_* stage bits
@@ -1280,7 +1238,7 @@ def rfcal_as_mixer(m, w):
     return dict(alpha=1.0 + 0.0j, beta=-w, dc=-m + w * m.conjugate())
 
 
-class rfcal(object):
+class rfcal(_StreamOp):
     """Receiver calibration on the wideband stream (mcrx_hip_rfcal_*): blind DC offset and IQ correction.
 
         rfcal(dc=True, iq=True, period_log2=0, forget_log2=30, gain=1.0, input_format="cf32", output_format="cf32")
@@ -1291,61 +1249,28 @@ class rfcal(object):
     absolute index; 0: by update().  The running means are the cumulative mean of the blocks until 2^-forget_log2 is the larger weight.
     Calls on one handle must be ordered on the device.  sc16 tensors are contiguous int16 of shape (n, 2)."""
 
+    _op, _what = "rfcal", ("this calibration", "calibration")
+
     def __init__(self, dc=True, iq=True, period_log2=0, forget_log2=30, gain=1.0, input_format="cf32", output_format="cf32"):
-        self._h = C.c_void_p()
         c = rfcal_config(dc, iq, period_log2, forget_log2, gain, input_format, output_format)
-        rc = lib().mcrx_hip_rfcal_create(C.byref(self._h), C.addressof(c))
-        if rc != MCRX_OK:
-            self._h = C.c_void_p()
-            self._chk(rc, "mcrx_hip_rfcal_create")
+        self._create(c)
         self.config, self.input_format, self.output_format = c, int(c.input_format), int(c.output_format)
-
-    @staticmethod
-    def _chk(rc, name):
-        _raise_rc(rc, name, lib().mcrx_hip_rfcal_last_error)
-
-    def _samples(self, x):
-        import torch
-        if self.input_format == INPUT_FORMATS["sc16"]:
-            n = _sc16_device_samples(x, "calibration")
-        else:
-            if x.dtype != torch.complex64:
-                raise TypeError("this calibration takes complex64 device tensors, not %s" % x.dtype)
-            n = int(x.numel())
-        if not x.is_cuda or not x.is_contiguous():
-            raise ValueError("device samples must be contiguous CUDA tensors")
-        return n
 
     def execute(self, x, out=None, stream=None):
         """x: the next n samples of the stream, a contiguous CUDA tensor: complex64, or on an sc16-in handle int16 of shape (n, 2).
         out (optional): where the corrected samples go, in the output format, with room for n; `out is x` is allowed with equal
         formats, any other overlap is refused.  Returns the n samples written.  Asynchronous on `stream` (default: torch's current
         stream of x's device)."""
-        import torch
-        out16 = self.output_format == OUTPUT_FORMATS["sc16"]
-        n = self._samples(x)
-        if out is None:
-            out = _empty_samples(n, self.output_format, x.device)
-        else:
-            if out.dtype != (torch.int16 if out16 else torch.complex64):
-                raise TypeError("out must be %s for this calibration" % ("int16" if out16 else "complex64"))
-            if not out.is_cuda or not out.is_contiguous() or int(out.numel()) < (2 * n if out16 else n):
-                raise ValueError("out must be a contiguous CUDA tensor with room for %d samples" % n)
-        if n == 0:              # (an empty tensor has no address to pass)
-            return out.view(-1, 2)[:0] if out16 else out.view(-1)[:0]
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        self._chk(lib().mcrx_hip_rfcal_execute_device(self._h, _dptr(x), n, _dptr(out), _stream_ptr(stream)), "mcrx_hip_rfcal_execute_device")
-        return out.view(-1, 2)[:n] if out16 else out.view(-1)[:n]
+        n, out, view = self._io(x, out, self.input_format == INPUT_FORMATS["sc16"], self.output_format == OUTPUT_FORMATS["sc16"])
+        if n:
+            self._call("execute_device", self._h, _dptr(x), n, _dptr(out), self._stream(stream, x))
+        return view
 
     def measure(self, x, stream=None):
         """The next n samples of the stream, measured only (nothing is written); returns n."""
-        import torch
-        n = self._samples(x)
+        n = self._in(x, self.input_format == INPUT_FORMATS["sc16"])
         if n:
-            if stream is None:
-                stream = torch.cuda.current_stream(x.device)
-            self._chk(lib().mcrx_hip_rfcal_execute_device(self._h, _dptr(x), n, None, _stream_ptr(stream)), "mcrx_hip_rfcal_execute_device")
+            self._call("execute_device", self._h, _dptr(x), n, None, self._stream(stream, x))
         return n
 
     @staticmethod
@@ -1383,23 +1308,6 @@ class rfcal(object):
 
     def position(self):
         return int(lib().mcrx_hip_rfcal_position(self._h))
-
-    def clipped(self, reset=False):
-        """Samples clipped by the sc16-out calls since the count was last reset (waits for the last such call only); 0 on a cf32 one."""
-        n = C.c_uint64(0)
-        self._chk(lib().mcrx_hip_rfcal_clipped(self._h, C.byref(n), 1 if reset else 0), "mcrx_hip_rfcal_clipped")
-        return int(n.value)
-
-    def close(self):
-        if self._h:
-            lib().mcrx_hip_rfcal_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 USERCHAN_MAX_RAYS, USERCHAN_MAX_DELAY, USERCHAN_MAX_CHANNELS = 4, 255, 1024      # MCRX_USERCHAN_MAX_RAYS, _MAX_DELAY, _MAX_CHANNELS

@@ -27,8 +27,9 @@
 #include <string>
 #include "../../include/mcrx_hip.h"
 #include "cfr_plan.hpp"
-#include "devscope.hpp"
+#include "ophost.hpp"
 #include "sc16.hpp"
+#include "stream_call.hpp"
 
 namespace mcrx {
 
@@ -248,7 +249,6 @@ __global__ __launch_bounds__(256) void cfr_kernel(CfrArgs a)
 using namespace mcrx;
 
 static thread_local std::string g_cfr_err;
-#define CFRCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_cfr_err = std::string(#x) + ": " + hipGetErrorString(e_); return MCRX_EHIP; } } while (0)
 
 // what the kernels add to: over[p][slot] a cache line apart, then peak2
 struct CfrStats {
@@ -263,7 +263,7 @@ struct mcrx_hip_cfr_s {
     CfrStats *stats = nullptr;  // device
     hipEvent_t stats_ev = nullptr; bool stats_pending = false;
     uint64_t over_base[MCRX_CFR_MAX_PASSES] = {};   // already reported and reset
-    float2 *scratch[2] = { nullptr, nullptr }; uint64_t scratch_samples = 0;    // P > 1: between the passes (grown on demand, never shrunk)
+    DevBuffer scratch[2];       // P > 1: between the passes
 };
 
 extern "C" const char *mcrx_hip_cfr_last_error(void) { return g_cfr_err.c_str(); }
@@ -300,7 +300,7 @@ extern "C" int mcrx_hip_cfr_destroy(mcrx_hip_cfr_t q)
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) return MCRX_OK;
     (void)hipDeviceSynchronize();
-    for (float2 *s : q->scratch) if (s) (void)hipFree(s);
+    for (DevBuffer &s : q->scratch) s.release();
     if (q->stats) (void)hipFree(q->stats);
     if (q->stats_ev) (void)hipEventDestroy(q->stats_ev);
     q->clip.release();
@@ -315,28 +315,15 @@ extern "C" int mcrx_hip_cfr_execute_device(mcrx_hip_cfr_t q, const void *d_in, s
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_cfr_err = "null handle"; return MCRX_EINVAL; }
-    if (!d_in || !d_out) { g_cfr_err = "null buffer"; return MCRX_EINVAL; }
     const mcrx_hip_cfr_config &c = q->cfg;
     const bool out16 = c.output_format == IQ_SC16;
-    const uintptr_t pi = reinterpret_cast<uintptr_t>(d_in), po = reinterpret_cast<uintptr_t>(d_out);
-    if (pi & 7u) { g_cfr_err = "d_in must be 8-byte aligned"; return MCRX_EINVAL; }
-    if (po & (out16 ? 3u : 7u)) { g_cfr_err = out16 ? "d_out must be 4-byte aligned" : "d_out must be 8-byte aligned"; return MCRX_EINVAL; }
-    if (!cfr_fits(&c, (uint64_t)n)) { g_cfr_err = "n + 2 * halo must not exceed 2^32 samples"; return MCRX_EINVAL; }
+    if (const char *bad = stream_call_check(reinterpret_cast<uintptr_t>(d_in), reinterpret_cast<uintptr_t>(d_out), n, 8u, out16 ? 4u : 8u, 2ull * cfr_halo(&c),
+                                            false, false, "d_in and d_out overlap: the operator reads neighbours, in-place use is refused")) { g_cfr_err = bad; return MCRX_EINVAL; }
     if (n == 0) return MCRX_OK;
-    const uint64_t nin = (uint64_t)n + 2ull * cfr_halo(&c);
-    if (pi < po + (uint64_t)n * (out16 ? 4u : 8u) && po < pi + nin * 8u) {
-        g_cfr_err = "d_in and d_out overlap: the operator reads neighbours, in-place use is refused";
-        return MCRX_EINVAL;
-    }
     hipStream_t st = (hipStream_t)stream;
-    const uint64_t want = cfr_scratch_samples(&c, n);
-    if (want > q->scratch_samples) {                                    // grow (hipFree waits for the calls in flight); steady state: never
-        for (float2 *&s : q->scratch) if (s) { CFRCHK(hipFree(s)); s = nullptr; }
-        q->scratch_samples = 0;
-        CFRCHK(hipMalloc((void **)&q->scratch[0], want * sizeof(float2)));
-        if (c.passes > 2u) CFRCHK(hipMalloc((void **)&q->scratch[1], want * sizeof(float2)));
-        q->scratch_samples = want;
-    }
+    const size_t want = (size_t)cfr_scratch_samples(&c, n) * sizeof(float2);
+    MCRX_OP_CHK(g_cfr_err, q->scratch[0].ensure(want));
+    if (c.passes > 2u) MCRX_OP_CHK(g_cfr_err, q->scratch[1].ensure(want));
     CfrArgs a = {};
     a.peak2 = &q->stats->peak2; a.clip = q->clip.device();
     a.H = c.half_len; a.always = cfr_may_skip(&c) ? 0u : 1u; a.A = c.threshold; a.A2 = cfr_threshold2(c.threshold); a.gain = c.gain;
@@ -344,8 +331,8 @@ extern "C" int mcrx_hip_cfr_execute_device(mcrx_hip_cfr_t q, const void *d_in, s
     for (uint32_t p = 0; p < c.passes; p++) {
         const CfrPass ps = cfr_pass(&c, n, p);
         const bool last = p + 1u == c.passes;
-        a.in = p == 0 ? static_cast<const float2 *>(d_in) : q->scratch[(p - 1u) & 1u];
-        a.out = last ? d_out : static_cast<void *>(q->scratch[p & 1u]);
+        a.in = p == 0 ? static_cast<const float2 *>(d_in) : q->scratch[(p - 1u) & 1u].as<float2>();
+        a.out = last ? d_out : q->scratch[p & 1u].ptr;
         a.over = &q->stats->over[p][0][0];
         a.m = ps.outputs; a.count_lo = ps.count_lo; a.count_hi = ps.count_hi;
         const bool odd = (((reinterpret_cast<uintptr_t>(a.in) >> 3) + c.half_len) & 1u) != 0;     // the lanes' first samples against 16 bytes
@@ -355,31 +342,26 @@ extern "C" int mcrx_hip_cfr_execute_device(mcrx_hip_cfr_t q, const void *d_in, s
         else if (out16) CFR_LAUNCH(IQ_SC16, true);
         else CFR_LAUNCH(IQ_CF32, true);
 #undef CFR_LAUNCH
-        CFRCHK(hipGetLastError());
+        MCRX_OP_CHK(g_cfr_err, hipGetLastError());
     }
-    CFRCHK(hipEventRecord(q->stats_ev, st));
+    MCRX_OP_CHK(g_cfr_err, hipEventRecord(q->stats_ev, st));
     q->stats_pending = true;
-    if (out16) CFRCHK(q->clip.mark(st));
+    if (out16) MCRX_OP_CHK(g_cfr_err, q->clip.mark(st));
     return MCRX_OK;
 }
 
 extern "C" int mcrx_hip_cfr_clipped(mcrx_hip_cfr_t q, uint64_t *samples, int reset)
 {
-    DevScope dev_scope_(q ? q->device : -1);
-    if (!q) { g_cfr_err = "null handle"; return MCRX_EINVAL; }
-    uint64_t n = 0;
-    CFRCHK(q->clip.read(&n, reset != 0));
-    if (samples) *samples = n;
-    return MCRX_OK;
+    return op_clipped(q, g_cfr_err, samples, reset);
 }
 
 extern "C" int mcrx_hip_cfr_stats(mcrx_hip_cfr_t q, uint64_t over[MCRX_CFR_MAX_PASSES], float *peak2, int reset)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_cfr_err = "null handle"; return MCRX_EINVAL; }
-    if (q->stats_pending) { CFRCHK(hipEventSynchronize(q->stats_ev)); q->stats_pending = false; }
+    if (q->stats_pending) { MCRX_OP_CHK(g_cfr_err, hipEventSynchronize(q->stats_ev)); q->stats_pending = false; }
     static thread_local CfrStats host;
-    CFRCHK(hipMemcpy(&host, q->stats, sizeof(host), hipMemcpyDeviceToHost));
+    MCRX_OP_CHK(g_cfr_err, hipMemcpy(&host, q->stats, sizeof(host), hipMemcpyDeviceToHost));
     for (uint32_t p = 0; p < (uint32_t)MCRX_CFR_MAX_PASSES; p++) {
         uint64_t sum = 0;
         for (uint32_t s = 0; s < (uint32_t)CFR_SLOTS; s++) sum += host.over[p][s][0];
@@ -388,8 +370,8 @@ extern "C" int mcrx_hip_cfr_stats(mcrx_hip_cfr_t q, uint64_t over[MCRX_CFR_MAX_P
     }
     if (peak2) { float v; memcpy(&v, &host.peak2, sizeof(v)); *peak2 = v; }
     if (reset) {                                                        // (the counts reset by their base; the maximum has none)
-        CFRCHK(hipMemset(&q->stats->peak2, 0, sizeof(host.peak2)));
-        CFRCHK(hipStreamSynchronize(nullptr));
+        MCRX_OP_CHK(g_cfr_err, hipMemset(&q->stats->peak2, 0, sizeof(host.peak2)));
+        MCRX_OP_CHK(g_cfr_err, hipStreamSynchronize(nullptr));
     }
     return MCRX_OK;
 }

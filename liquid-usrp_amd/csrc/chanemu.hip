@@ -35,9 +35,11 @@
 #include <string>
 #include "../../include/mcrx_hip.h"
 #include "devmath.h"
-#include "devscope.hpp"
 #include "fadegen.hpp"
-#include "sc16.hpp"
+#include "iqpair.hpp"
+#include "ophost.hpp"
+#include "span_plan.hpp"
+#include "stream_call.hpp"
 
 namespace mcrx {
 
@@ -130,18 +132,15 @@ __device__ __forceinline__ float2 chanemu_sample(const ChanemuArgs &a, float2 s,
 template <bool ROT, bool NOISE, int FMT, bool FADE>
 __global__ __launch_bounds__(256) void chanemu_kernel(ChanemuArgs a)
 {
-    // lane g owns absolute samples base + 2 g, + 1 with base = pos & ~1: relative to in[0] that is m0 = 2 g - (pos & 1), m0 + 1
     const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const uint32_t odd = (uint32_t)(a.pos & 1u);
-    const long long m0 = (long long)(2 * g) - (long long)odd;
-    const bool ok0 = m0 >= 0 && m0 < (long long)a.n, ok1 = m0 + 1 < (long long)a.n;      // (m0 + 1 >= 0 always)
+    const IqPair p = iq_pair(a.pos, a.n, g);                            // lane g owns the index-aligned pair g (iqpair.hpp)
     uint32_t nclip = 0;
-    if (ok0 || ok1) {
+    if (p.ok0 || p.ok1) {
         float2 x0[MCRX_CHANEMU_MAX_TAPS], x1[MCRX_CHANEMU_MAX_TAPS];
 #pragma unroll
         for (int i = 0; i < MCRX_CHANEMU_MAX_TAPS; i++)                 // every tap's loads first: T pairs in flight
-            if (i < (int)a.T) chanemu_fetch_pair(a, m0 - (long long)a.delay[i], x0[i], x1[i]);
-        const uint64_t nabs = (a.pos - odd) + 2 * g;                    // even; wraps with the 64-bit position
+            if (i < (int)a.T) chanemu_fetch_pair(a, p.m0 - (long long)a.delay[i], x0[i], x1[i]);
+        const uint64_t nabs = iq_pair_index(a.pos, g);
         float2 s0 = make_float2(0.f, 0.f), s1 = s0;
         // FADE: the pair's grid row (2^L is even: a pair never straddles one) relative to the table's first, and its two fractions
         const float2 *grow = nullptr;
@@ -171,18 +170,7 @@ __global__ __launch_bounds__(256) void chanemu_kernel(ChanemuArgs a)
         if (NOISE) w = chanemu_pair_words(a.seed, nabs);
         const float2 v0 = chanemu_sample<ROT, NOISE>(a, s0, nabs, w.w[0], w.w[1]);
         const float2 v1 = chanemu_sample<ROT, NOISE>(a, s1, nabs + 1, w.w[2], w.w[3]);
-        if (FMT == IQ_SC16) {
-            uint32_t *o = reinterpret_cast<uint32_t *>(a.out) + m0;
-            uint32_t c0 = 0, c1 = 0;
-            const uint32_t q0 = sc16_sample(v0.x, v0.y, c0), q1 = sc16_sample(v1.x, v1.y, c1);
-            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(o) & 7u) == 0) *reinterpret_cast<uint2 *>(o) = make_uint2(q0, q1);
-            else { if (ok0) o[0] = q0; if (ok1) o[1] = q1; }
-            nclip = (ok0 ? c0 : 0u) + (ok1 ? c1 : 0u);
-        } else {
-            float2 *o = reinterpret_cast<float2 *>(a.out) + m0;
-            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) *reinterpret_cast<float4 *>(o) = make_float4(v0.x, v0.y, v1.x, v1.y);
-            else { if (ok0) o[0] = v0; if (ok1) o[1] = v1; }
-        }
+        nclip = store_pair<FMT>(a.out, p, v0, v1);
     }
     if (FMT == IQ_SC16) sc16_clip_commit(a.clip, nclip);               // every lane of every wave gets here
 }
@@ -200,7 +188,6 @@ __global__ __launch_bounds__(256) void chanemu_history_kernel(ChanemuArgs a, flo
 using namespace mcrx;
 
 static thread_local std::string g_ce_err;
-#define CECHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_ce_err = std::string(#x) + ": " + hipGetErrorString(e_); return MCRX_EHIP; } } while (0)
 
 struct mcrx_hip_chanemu_s {
     int device = -1;            // the HIP device the handle was created on: every entry point runs with it current (devscope.hpp)
@@ -213,7 +200,7 @@ struct mcrx_hip_chanemu_s {
     bool fade = false;          // fading on: ft holds the sinusoids of rays 0 .. num_taps - 1
     FadeTables ft = {};
     uint32_t fade_L = 0, fade_cap = 0;              // log2 of the update interval; the most rows of the table a span may use
-    float2 *gtab = nullptr; uint32_t gtab_rows = 0; // the gain table and the rows allocated (grown on demand, never shrunk)
+    DevBuffer gtab;             // the gain table, float2 [row][MCRX_CHANEMU_MAX_TAPS]
 };
 
 // 2^18 rows = 16 MB at most, and only what a call needs: at L = 10 that is one span for 2.7e8 samples (the 512-channel slab is 2.1e8),
@@ -227,12 +214,8 @@ static const char *fading_check(const mcrx_hip_chanemu_fading *f, unsigned ray0,
     if (f->num_sinusoids < 1 || f->num_sinusoids > MCRX_CHANEMU_MAX_SINUSOIDS) return "num_sinusoids must be 1 .. 16";
     if (f->table_rows == 1) return "table_rows must be 0 (default) or at least 2";
     const double B = (double)(1u << f->log2_block);
-    for (unsigned i = ray0; i < ray1; i++) {
-        if (!std::isfinite(f->doppler[i]) || !std::isfinite(f->los_doppler[i])) return "a Doppler is not finite";
-        if (f->doppler[i] < 0.0) return "doppler must not be negative";
-        if (f->doppler[i] * B > 0.125 || std::fabs(f->los_doppler[i]) * B > 0.125) return "a Doppler times the update interval exceeds 1/8: the grid does not sample the gain";
-        if (!std::isfinite(f->rice_k[i]) || f->rice_k[i] < 0.f) return "rice_k must be finite and not negative";
-    }
+    for (unsigned i = ray0; i < ray1; i++)
+        if (const char *bad = fade_ray_check(B, f->doppler[i], f->los_doppler[i], f->rice_k[i])) return bad;
     return nullptr;
 }
 
@@ -320,7 +303,7 @@ extern "C" int mcrx_hip_chanemu_destroy(mcrx_hip_chanemu_t q)
     if (!q) return MCRX_OK;
     (void)hipDeviceSynchronize();
     for (float2 *p : q->hist) if (p) (void)hipFree(p);
-    if (q->gtab) (void)hipFree(q->gtab);
+    q->gtab.release();
     q->clip.release();
     delete q;
     return MCRX_OK;
@@ -346,36 +329,24 @@ static void chanemu_launch(const ChanemuArgs &a, bool rot, bool noise, dim3 grid
                else       hipLaunchKernelGGL((chanemu_kernel<false, false, FMT, FADE>), grid, dim3(256), 0, st, a); }
 }
 
-// rows of the gain table the samples pos .. pos + n - 1 read (n >= 1): their own grid rows and the one behind the last
-static uint64_t fade_rows(uint64_t pos, uint64_t n, uint32_t L) { return (((pos & (((uint64_t)1 << L) - 1)) + n - 1) >> L) + 2; }
-
 extern "C" int mcrx_hip_chanemu_execute_device(mcrx_hip_chanemu_t q, const void *d_in, size_t n, void *d_out, void *stream)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_ce_err = "null handle"; return MCRX_EINVAL; }
-    if (!d_in || !d_out) { g_ce_err = "null buffer"; return MCRX_EINVAL; }
     const bool sc16 = q->cfg.output_format == IQ_SC16;
-    const uintptr_t pi = reinterpret_cast<uintptr_t>(d_in), po = reinterpret_cast<uintptr_t>(d_out);
-    if (pi & 7u) { g_ce_err = "d_in must be 8-byte aligned"; return MCRX_EINVAL; }
-    if (po & (sc16 ? 3u : 7u)) { g_ce_err = sc16 ? "d_out must be 4-byte aligned" : "d_out must be 8-byte aligned"; return MCRX_EINVAL; }
-    if (n > ((size_t)1 << 32)) { g_ce_err = "at most 2^32 samples a call"; return MCRX_EINVAL; }      // (a lane per pair, 2^31 lanes a launch)
-    const size_t bi = n * 8u, bo = n * (sc16 ? 4u : 8u);
-    if (pi < po + bo && po < pi + bi) { g_ce_err = "d_in and d_out overlap: the taps read behind the write front, in-place use is not possible"; return MCRX_EINVAL; }
+    if (const char *bad = stream_call_check(reinterpret_cast<uintptr_t>(d_in), reinterpret_cast<uintptr_t>(d_out), n, 8u, sc16 ? 4u : 8u, 0, false, false,
+                                            "d_in and d_out overlap: the taps read behind the write front, in-place use is not possible")) { g_ce_err = bad; return MCRX_EINVAL; }
     if (n == 0) return MCRX_OK;
     hipStream_t st = (hipStream_t)stream;
     const mcrx_hip_chanemu_config &c = q->cfg;
     const bool fade = q->fade;
-    uint32_t cap = 0;                                                   // fading: the rows of the table a span may use
+    const uint32_t L = q->fade_L;
+    const size_t row_bytes = MCRX_CHANEMU_MAX_TAPS * sizeof(float2);
+    uint64_t cap = 0;                                                   // fading: the rows of the table a span may use (span_plan.hpp)
     if (fade) {
-        const uint64_t want = fade_rows(q->pos, n, q->fade_L);
-        cap = (uint32_t)(want < q->fade_cap ? want : q->fade_cap);
-        if (cap > q->gtab_rows) {                                       // grow (hipFree waits for the calls in flight); steady state: never
-            const uint64_t twice = 2ull * q->gtab_rows < q->fade_cap ? 2ull * q->gtab_rows : q->fade_cap;
-            const uint32_t rows = (uint32_t)(twice > cap ? twice : cap);
-            if (q->gtab) { CECHK(hipFree(q->gtab)); q->gtab = nullptr; q->gtab_rows = 0; }
-            CECHK(hipMalloc((void **)&q->gtab, (size_t)rows * MCRX_CHANEMU_MAX_TAPS * sizeof(float2)));
-            q->gtab_rows = rows;
-        }
+        cap = span_cap(span_rows(span_frac(q->pos, L), n, L), q->fade_cap);
+        const uint64_t have = q->gtab.bytes / row_bytes;
+        if (cap > have) MCRX_OP_CHK(g_ce_err, q->gtab.ensure((size_t)span_grow(have, q->fade_cap, cap) * row_bytes));
     }
     ChanemuArgs a = {};
     a.clip = q->clip.device(); a.D = q->D; a.T = c.num_taps;
@@ -387,31 +358,30 @@ extern "C" int mcrx_hip_chanemu_execute_device(mcrx_hip_chanemu_t q, const void 
     for (size_t off = 0; off < n; ) {
         size_t m = n - off;
         if (fade) {
-            const uint64_t avail = ((uint64_t)(cap - 1) << q->fade_L) - (q->pos & (((uint64_t)1 << q->fade_L) - 1));
-            m = m < avail ? m : (size_t)avail;
-            a.L = q->fade_L; a.row0 = q->pos >> q->fade_L; a.rows = (uint32_t)fade_rows(q->pos, m, q->fade_L); a.gtab = q->gtab;
-            a.finv = std::ldexp(1.0f, -(int)q->fade_L);
-            hipLaunchKernelGGL(chanemu_gain_kernel, dim3((a.rows + 255) / 256, c.num_taps), dim3(256), 0, st, q->ft, q->gtab, a.row0, a.rows, a.L);
-            CECHK(hipGetLastError());
+            const Span<uint64_t> s = span_next(q->pos, m, L, cap);
+            m = (size_t)s.m;
+            a.L = L; a.row0 = s.row0; a.rows = (uint32_t)s.rows; a.gtab = q->gtab.as<float2>();
+            a.finv = std::ldexp(1.0f, -(int)L);
+            hipLaunchKernelGGL(chanemu_gain_kernel, dim3((a.rows + 255) / 256, c.num_taps), dim3(256), 0, st, q->ft, q->gtab.as<float2>(), a.row0, a.rows, L);
+            MCRX_OP_CHK(g_ce_err, hipGetLastError());
         }
         a.in = static_cast<const float2 *>(d_in) + off;
         a.out = sc16 ? static_cast<void *>(static_cast<uint32_t *>(d_out) + off) : static_cast<void *>(static_cast<float2 *>(d_out) + off);
         a.hist = q->hist[q->cur]; a.pos = q->pos; a.n = m; a.hist_len = q->hist_len;
-        const uint64_t pairs = ((q->pos & 1u) + m + 1) >> 1;
-        const dim3 grid((unsigned)((pairs + 255) / 256));
+        const dim3 grid((unsigned)((iq_pairs(q->pos, m) + 255) / 256));
         if (fade) { if (sc16) chanemu_launch<IQ_SC16, true>(a, rot, noise, grid, st); else chanemu_launch<IQ_CF32, true>(a, rot, noise, grid, st); }
         else      { if (sc16) chanemu_launch<IQ_SC16, false>(a, rot, noise, grid, st); else chanemu_launch<IQ_CF32, false>(a, rot, noise, grid, st); }
-        CECHK(hipGetLastError());
+        MCRX_OP_CHK(g_ce_err, hipGetLastError());
         if (q->D) {
             hipLaunchKernelGGL(chanemu_history_kernel, dim3((q->D + 255) / 256), dim3(256), 0, st, a, q->hist[q->cur ^ 1]);
-            CECHK(hipGetLastError());
+            MCRX_OP_CHK(g_ce_err, hipGetLastError());
             q->cur ^= 1;
             q->hist_len = (uint32_t)((uint64_t)q->hist_len + m < q->D ? q->hist_len + m : q->D);
         }
         q->pos += m;
         off += m;
     }
-    if (sc16) CECHK(q->clip.mark(st));
+    if (sc16) MCRX_OP_CHK(g_ce_err, q->clip.mark(st));
     return MCRX_OK;
 }
 
@@ -425,16 +395,11 @@ extern "C" int mcrx_hip_chanfade_gains(mcrx_hip_chanemu_t q, uint64_t first_row,
     if (rows == 0) return MCRX_OK;
     hipLaunchKernelGGL(chanemu_gain_kernel, dim3((rows + 255) / 256, q->cfg.num_taps), dim3(256), 0, (hipStream_t)stream, q->ft,
                        static_cast<float2 *>(d_table), first_row, rows, q->fade_L);
-    CECHK(hipGetLastError());
+    MCRX_OP_CHK(g_ce_err, hipGetLastError());
     return MCRX_OK;
 }
 
 extern "C" int mcrx_hip_chanemu_clipped(mcrx_hip_chanemu_t q, uint64_t *samples, int reset)
 {
-    DevScope dev_scope_(q ? q->device : -1);
-    if (!q) { g_ce_err = "null handle"; return MCRX_EINVAL; }
-    uint64_t n = 0;
-    CECHK(q->clip.read(&n, reset != 0));
-    if (samples) *samples = n;
-    return MCRX_OK;
+    return op_clipped(q, g_ce_err, samples, reset);
 }

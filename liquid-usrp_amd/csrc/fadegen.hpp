@@ -22,6 +22,16 @@ __host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
     return o;
 }
 
+// one fading ray against the update interval of B samples: nullptr, or what is wrong with it
+static inline const char *fade_ray_check(double B, double doppler, double los_doppler, float rice_k)
+{
+    if (!std::isfinite(doppler) || !std::isfinite(los_doppler)) return "a Doppler is not finite";
+    if (doppler < 0.0) return "doppler must not be negative";
+    if (doppler * B > 0.125 || std::fabs(los_doppler) * B > 0.125) return "a Doppler times the update interval exceeds 1/8: the grid does not sample the gain";
+    if (!std::isfinite(rice_k) || rice_k < 0.f) return "rice_k must be finite and not negative";
+    return nullptr;
+}
+
 // One fading ray's sinusoids: entry 0 the line-of-sight term, then the S scattered ones.  The words of counter (k, ray, c2, c3) under
 // key `seed` give the stratified arrival angle alpha_k = 2 pi (k + w0 2^-32) / S and the phase Phi_k = w1; steps are 2^64 * cycles per
 // sample, coef = { c_los, c_sc } with E|g|^2 = 1.  c2 / c3 keep the emulators' streams apart: chanemu (1, 0), userchan (2, user id).

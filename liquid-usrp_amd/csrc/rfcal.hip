@@ -22,9 +22,10 @@
 #include <stdint.h>
 #include <string>
 #include "../../include/mcrx_hip.h"
-#include "devscope.hpp"
+#include "iqpair.hpp"
+#include "ophost.hpp"
 #include "rfcal_plan.hpp"
-#include "sc16.hpp"
+#include "stream_call.hpp"
 
 namespace mcrx {
 
@@ -53,9 +54,7 @@ template <int FIN, int FOUT, bool APPLY, bool MEASURE>
 __global__ __launch_bounds__(RFCAL_WG) void rfcal_kernel(RfcalArgs a)
 {
     typedef typename RfcalSum<FIN>::type sum_t;
-    // pair g owns absolute samples base + 2 g, + 1 with base = pos & ~1: relative to in[0] that is m0 = 2 g - (pos & 1), m0 + 1
-    const uint32_t odd = (uint32_t)(a.pos & 1u);
-    const uint64_t pairs = (odd + a.n + 1) >> 1, stride = (uint64_t)gridDim.x * RFCAL_WG;
+    const uint64_t pairs = iq_pairs(a.pos, a.n), stride = (uint64_t)gridDim.x * RFCAL_WG;      // the index-aligned pairs (iqpair.hpp)
     float mr = 0.f, mi = 0.f, wr = 0.f, wi = 0.f;
     if (APPLY) {
         const float4 cf = *reinterpret_cast<const float4 *>(a.state);      // the same address in every lane
@@ -64,14 +63,11 @@ __global__ __launch_bounds__(RFCAL_WG) void rfcal_kernel(RfcalArgs a)
     sum_t s1r = 0, s1i = 0, srr = 0, sii = 0, sri = 0;                  // sum re, im, re^2, im^2, re im of this lane's samples
     uint32_t nclip = 0;
     for (uint64_t g = (uint64_t)blockIdx.x * RFCAL_WG + threadIdx.x; g < pairs; g += stride) {
-        const long long m0 = (long long)(2 * g) - (long long)odd;
-        const bool ok0 = m0 >= 0, ok1 = m0 + 1 < (long long)a.n;       // (g < pairs: m0 < n and m0 + 1 >= 0 always)
+        const IqPair p = iq_pair(a.pos, a.n, g);
         float2 x0 = make_float2(0.f, 0.f), x1 = x0;                     // (the masked half of an edge pair is a zero: it adds nothing)
         if (FIN == IQ_SC16) {
-            const uint32_t *p = reinterpret_cast<const uint32_t *>(a.in) + m0;
-            uint32_t w0 = 0, w1 = 0;
-            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(p) & 7u) == 0) { const uint2 w = *reinterpret_cast<const uint2 *>(p); w0 = w.x; w1 = w.y; }
-            else { if (ok0) w0 = p[0]; if (ok1) w1 = p[1]; }
+            uint32_t w0, w1;
+            load_pair_words(a.in, p, w0, w1);
             if (MEASURE) {
                 const int r0 = (int16_t)(w0 & 0xffffu), i0 = (int32_t)w0 >> 16, r1 = (int16_t)(w1 & 0xffffu), i1 = (int32_t)w1 >> 16;
                 s1r += (sum_t)(r0 + r1); s1i += (sum_t)(i0 + i1);
@@ -80,11 +76,7 @@ __global__ __launch_bounds__(RFCAL_WG) void rfcal_kernel(RfcalArgs a)
             }
             if (FOUT != RFCAL_NONE) { x0 = sc16_unpack(w0); x1 = sc16_unpack(w1); }
         } else {
-            const float2 *p = reinterpret_cast<const float2 *>(a.in) + m0;
-            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
-                const float4 v = *reinterpret_cast<const float4 *>(p);
-                x0 = make_float2(v.x, v.y); x1 = make_float2(v.z, v.w);
-            } else { if (ok0) x0 = p[0]; if (ok1) x1 = p[1]; }
+            load_pair<IQ_CF32>(a.in, p, x0, x1);
             if (MEASURE) {          // fp64 products of fp32 values are exact, so fma(a, b, s) IS s + a * b: one instruction instead of two
                 const double r0 = x0.x, i0 = x0.y, r1 = x1.x, i1 = x1.y;
                 s1r += (sum_t)r0; s1r += (sum_t)r1; s1i += (sum_t)i0; s1i += (sum_t)i1;
@@ -100,18 +92,7 @@ __global__ __launch_bounds__(RFCAL_WG) void rfcal_kernel(RfcalArgs a)
                 v1 = make_float2(fmaf(-wr, t1r, fmaf(-wi, t1i, t1r)), fmaf(wr, t1i, fmaf(-wi, t1r, t1i)));
             }
             if (a.gain != 1.0f) { v0 = make_float2(a.gain * v0.x, a.gain * v0.y); v1 = make_float2(a.gain * v1.x, a.gain * v1.y); }
-            if (FOUT == IQ_SC16) {
-                uint32_t *o = reinterpret_cast<uint32_t *>(a.out) + m0;
-                uint32_t c0 = 0, c1 = 0;
-                const uint32_t q0 = sc16_sample(v0.x, v0.y, c0), q1 = sc16_sample(v1.x, v1.y, c1);
-                if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(o) & 7u) == 0) *reinterpret_cast<uint2 *>(o) = make_uint2(q0, q1);
-                else { if (ok0) o[0] = q0; if (ok1) o[1] = q1; }
-                nclip += (ok0 ? c0 : 0u) + (ok1 ? c1 : 0u);
-            } else {
-                float2 *o = reinterpret_cast<float2 *>(a.out) + m0;
-                if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) *reinterpret_cast<float4 *>(o) = make_float4(v0.x, v0.y, v1.x, v1.y);
-                else { if (ok0) o[0] = v0; if (ok1) o[1] = v1; }
-            }
+            nclip += store_pair<FOUT>(a.out, p, v0, v1);
         }
     }
     if (FOUT == IQ_SC16) sc16_clip_commit(a.clip, nclip);               // every lane of every wave gets here
@@ -211,7 +192,6 @@ __global__ __launch_bounds__(64) void rfcal_set_kernel(mcrx_hip_rfcal_state *st,
 using namespace mcrx;
 
 static thread_local std::string g_cal_err;
-#define CALCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_cal_err = std::string(#x) + ": " + hipGetErrorString(e_); return MCRX_EHIP; } } while (0)
 
 struct mcrx_hip_rfcal_s {
     int device = -1;            // the HIP device the handle was created on: every entry point runs with it current (devscope.hpp)
@@ -336,25 +316,21 @@ extern "C" int mcrx_hip_rfcal_execute_device(mcrx_hip_rfcal_t q, const void *d_i
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_cal_err = "null handle"; return MCRX_EINVAL; }
-    if (!d_in) { g_cal_err = "null buffer"; return MCRX_EINVAL; }
     const mcrx_hip_rfcal_config &c = q->cfg;
     const bool in16 = c.input_format == IQ_SC16, out16 = c.output_format == IQ_SC16;
-    const uintptr_t pi = reinterpret_cast<uintptr_t>(d_in), po = reinterpret_cast<uintptr_t>(d_out);
-    if (pi & (in16 ? 3u : 7u)) { g_cal_err = in16 ? "d_in must be 4-byte aligned" : "d_in must be 8-byte aligned"; return MCRX_EINVAL; }
-    if (d_out && (po & (out16 ? 3u : 7u))) { g_cal_err = out16 ? "d_out must be 4-byte aligned" : "d_out must be 8-byte aligned"; return MCRX_EINVAL; }
+    const uint32_t si = in16 ? 4u : 8u, so = out16 ? 4u : 8u;
     const bool measure = !q->held;
-    if (const char *bad = rfcal_call_check(&c, q->pos, n, q->since, measure)) { g_cal_err = bad; return MCRX_EINVAL; }
-    const size_t si = in16 ? 4u : 8u, so = out16 ? 4u : 8u;
-    if (d_out && pi < po + n * so && po < pi + n * si && !(pi == po && in16 == out16)) {
-        g_cal_err = "d_in and d_out overlap: in-place use takes d_in == d_out and equal formats";
-        return MCRX_EINVAL;
-    }
+    static const char *const overlap = "d_in and d_out overlap: in-place use takes d_in == d_out and equal formats";
+    const char *bad = stream_call_check(reinterpret_cast<uintptr_t>(d_in), reinterpret_cast<uintptr_t>(d_out), n, si, so, 0, true, true, overlap);
+    if (!bad || bad == overlap)                                         // the guard of the sc16 moments is judged in front of the overlap
+        if (const char *guard = rfcal_call_check(&c, q->pos, n, q->since, measure)) bad = guard;
+    if (bad) { g_cal_err = bad; return MCRX_EINVAL; }
     if (n == 0) return MCRX_OK;
     hipStream_t st = (hipStream_t)stream;
     if (!measure && !d_out) { q->pos += n; return MCRX_OK; }            // held and nothing to write
     if (q->reset_pending && !measure) {                                 // no fold in this call to carry the reset
         hipLaunchKernelGGL(rfcal_set_kernel, dim3(1), dim3(64), 0, st, q->state, 1u, 0u, 0.f, 0.f, 0.f, 0.f);
-        CALCHK(hipGetLastError());
+        MCRX_OP_CHK(g_cal_err, hipGetLastError());
         q->reset_pending = false;
     }
     RfcalArgs a = {};
@@ -374,15 +350,15 @@ extern "C" int mcrx_hip_rfcal_execute_device(mcrx_hip_rfcal_t q, const void *d_i
             else      hipLaunchKernelGGL((rfcal_kernel<IQ_CF32, RFCAL_NONE, false, true>), grid, dim3(RFCAL_WG), 0, st, a);
         } else if (in16) { if (out16) rfcal_launch<IQ_SC16, IQ_SC16>(apply, measure, a, grid, st); else rfcal_launch<IQ_SC16, IQ_CF32>(apply, measure, a, grid, st); }
         else             { if (out16) rfcal_launch<IQ_CF32, IQ_SC16>(apply, measure, a, grid, st); else rfcal_launch<IQ_CF32, IQ_CF32>(apply, measure, a, grid, st); }
-        CALCHK(hipGetLastError());
+        MCRX_OP_CHK(g_cal_err, hipGetLastError());
         q->pos += m;
         off += (size_t)m;
         if (measure) {
             q->since += m;
-            CALCHK(rfcal_fold(q, grid.x, m, ends, st));
+            MCRX_OP_CHK(g_cal_err, rfcal_fold(q, grid.x, m, ends, st));
         }
     }
-    if (d_out && out16) CALCHK(q->clip.mark(st));
+    if (d_out && out16) MCRX_OP_CHK(g_cal_err, q->clip.mark(st));
     return MCRX_OK;
 }
 
@@ -392,7 +368,7 @@ extern "C" int mcrx_hip_rfcal_update(mcrx_hip_rfcal_t q, void *stream)
     if (!q) { g_cal_err = "null handle"; return MCRX_EINVAL; }
     if (q->cfg.period_log2 != 0u) { g_cal_err = "the handle updates by itself (period_log2 != 0)"; return MCRX_EINVAL; }
     if (q->held) return MCRX_OK;                                        // while held the update changes nothing
-    CALCHK(rfcal_fold(q, 0u, 0u, true, (hipStream_t)stream));
+    MCRX_OP_CHK(g_cal_err, rfcal_fold(q, 0u, 0u, true, (hipStream_t)stream));
     return MCRX_OK;
 }
 
@@ -402,7 +378,7 @@ extern "C" int mcrx_hip_rfcal_set(mcrx_hip_rfcal_t q, float m_re, float m_im, fl
     if (!q) { g_cal_err = "null handle"; return MCRX_EINVAL; }
     if (!std::isfinite(m_re) || !std::isfinite(m_im) || !std::isfinite(w_re) || !std::isfinite(w_im)) { g_cal_err = "the coefficients must be finite"; return MCRX_EINVAL; }
     hipLaunchKernelGGL(rfcal_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, q->state, q->reset_pending ? 1u : 0u, 1u, m_re, m_im, w_re, w_im);
-    CALCHK(hipGetLastError());
+    MCRX_OP_CHK(g_cal_err, hipGetLastError());
     q->reset_pending = false; q->calibrated = true;
     return MCRX_OK;
 }
@@ -415,20 +391,15 @@ extern "C" int mcrx_hip_rfcal_read(mcrx_hip_rfcal_t q, mcrx_hip_rfcal_state *out
     hipStream_t st = (hipStream_t)stream;
     if (q->reset_pending) {
         hipLaunchKernelGGL(rfcal_set_kernel, dim3(1), dim3(64), 0, st, q->state, 1u, 0u, 0.f, 0.f, 0.f, 0.f);
-        CALCHK(hipGetLastError());
+        MCRX_OP_CHK(g_cal_err, hipGetLastError());
         q->reset_pending = false;
     }
-    CALCHK(hipMemcpyAsync(out, q->state, sizeof(*out), hipMemcpyDeviceToHost, st));
-    CALCHK(hipStreamSynchronize(st));
+    MCRX_OP_CHK(g_cal_err, hipMemcpyAsync(out, q->state, sizeof(*out), hipMemcpyDeviceToHost, st));
+    MCRX_OP_CHK(g_cal_err, hipStreamSynchronize(st));
     return MCRX_OK;
 }
 
 extern "C" int mcrx_hip_rfcal_clipped(mcrx_hip_rfcal_t q, uint64_t *samples, int reset)
 {
-    DevScope dev_scope_(q ? q->device : -1);
-    if (!q) { g_cal_err = "null handle"; return MCRX_EINVAL; }
-    uint64_t n = 0;
-    CALCHK(q->clip.read(&n, reset != 0));
-    if (samples) *samples = n;
-    return MCRX_OK;
+    return op_clipped(q, g_cal_err, samples, reset);
 }

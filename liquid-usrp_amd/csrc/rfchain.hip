@@ -27,10 +27,12 @@
 #include <string>
 #include "../../include/mcrx_hip.h"
 #include "devmath.h"
-#include "devscope.hpp"
 #include "fadegen.hpp"
+#include "iqpair.hpp"
+#include "ophost.hpp"
 #include "rfchain_plan.hpp"
-#include "sc16.hpp"
+#include "span_plan.hpp"
+#include "stream_call.hpp"
 
 namespace mcrx {
 
@@ -124,30 +126,15 @@ __device__ __forceinline__ float2 rfchain_sample(const RfchainArgs &a, float2 z,
 template <int STAGES, int FIN, int FOUT>
 __global__ __launch_bounds__(256) void rfchain_kernel(RfchainArgs a)
 {
-    // lane g owns absolute samples base + 2 g, + 1 with base = pos & ~1: relative to in[0] that is m0 = 2 g - (pos & 1), m0 + 1
     const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const uint32_t odd = (uint32_t)(a.pos & 1u);
-    const long long m0 = (long long)(2 * g) - (long long)odd;
-    const bool ok0 = m0 >= 0 && m0 < (long long)a.n, ok1 = m0 + 1 < (long long)a.n;      // (m0 + 1 >= 0 always)
+    const IqPair p = iq_pair(a.pos, a.n, g);                            // lane g owns the index-aligned pair g (iqpair.hpp)
     uint32_t nclip = 0;
-    if (ok0 || ok1) {
-        float2 x0 = make_float2(0.f, 0.f), x1 = x0;                     // (the masked half of an edge pair computes on a zero)
-        if (FIN == IQ_SC16) {
-            const uint32_t *p = reinterpret_cast<const uint32_t *>(a.in) + m0;
-            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
-                const uint2 w = *reinterpret_cast<const uint2 *>(p);
-                x0 = sc16_unpack(w.x); x1 = sc16_unpack(w.y);
-            } else { if (ok0) x0 = sc16_unpack(p[0]); if (ok1) x1 = sc16_unpack(p[1]); }
-        } else {
-            const float2 *p = reinterpret_cast<const float2 *>(a.in) + m0;
-            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
-                const float4 v = *reinterpret_cast<const float4 *>(p);
-                x0 = make_float2(v.x, v.y); x1 = make_float2(v.z, v.w);
-            } else { if (ok0) x0 = p[0]; if (ok1) x1 = p[1]; }
-        }
+    if (p.ok0 || p.ok1) {
+        float2 x0, x1;                                                  // (the masked half of an edge pair computes on a zero)
+        load_pair<FIN>(a.in, p, x0, x1);
         float th0 = 0.f, th1 = 0.f;
         if (STAGES & RF_OSC) {
-            const uint64_t nabs = (a.pos - odd) + 2 * g;                // even; wraps with the 64-bit position
+            const uint64_t nabs = iq_pair_index(a.pos, g);
             const uint64_t row = ((nabs >> a.L) - a.row0) & (~(uint64_t)0 >> a.L);
             const float *trow = a.tab + (size_t)(row < a.rows - 1u ? row : a.rows - 2u);      // (row + 1 < rows for every pair of the span)
             const float T0 = trow[0], dT = trow[1] - T0;
@@ -156,18 +143,7 @@ __global__ __launch_bounds__(256) void rfchain_kernel(RfchainArgs a)
         }
         const float2 v0 = rfchain_sample<STAGES>(a, x0, th0);
         const float2 v1 = rfchain_sample<STAGES>(a, x1, th1);
-        if (FOUT == IQ_SC16) {
-            uint32_t *o = reinterpret_cast<uint32_t *>(a.out) + m0;
-            uint32_t c0 = 0, c1 = 0;
-            const uint32_t q0 = sc16_sample(v0.x, v0.y, c0), q1 = sc16_sample(v1.x, v1.y, c1);
-            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(o) & 7u) == 0) *reinterpret_cast<uint2 *>(o) = make_uint2(q0, q1);
-            else { if (ok0) o[0] = q0; if (ok1) o[1] = q1; }
-            nclip = (ok0 ? c0 : 0u) + (ok1 ? c1 : 0u);
-        } else {
-            float2 *o = reinterpret_cast<float2 *>(a.out) + m0;
-            if (ok0 && ok1 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) *reinterpret_cast<float4 *>(o) = make_float4(v0.x, v0.y, v1.x, v1.y);
-            else { if (ok0) o[0] = v0; if (ok1) o[1] = v1; }
-        }
+        nclip = store_pair<FOUT>(a.out, p, v0, v1);
     }
     if (FOUT == IQ_SC16) sc16_clip_commit(a.clip, nclip);               // every lane of every wave gets here
 }
@@ -177,7 +153,6 @@ __global__ __launch_bounds__(256) void rfchain_kernel(RfchainArgs a)
 using namespace mcrx;
 
 static thread_local std::string g_rf_err;
-#define RFCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_rf_err = std::string(#x) + ": " + hipGetErrorString(e_); return MCRX_EHIP; } } while (0)
 
 struct mcrx_hip_rfchain_s {
     int device = -1;            // the HIP device the handle was created on: every entry point runs with it current (devscope.hpp)
@@ -185,7 +160,7 @@ struct mcrx_hip_rfchain_s {
     Sc16ClipCount clip;         // sc16-out handles only (allocated at creation): clipped samples since the handle was made
     RfchainPhase pt = {};       // oscillator on: its sinusoids
     uint32_t cap = 0;           // the most rows of the table a span may use
-    float *tab = nullptr; uint32_t tab_rows = 0;    // Theta's table and the rows allocated (grown on demand, never shrunk)
+    DevBuffer tab;              // Theta's table, one float a row
 };
 
 // 2^18 rows = 1 MB at most (chanemu's row count): at L = 10 one span for 2.7e8 samples, at L = 6 spans of 1.7e7 samples
@@ -232,7 +207,7 @@ extern "C" int mcrx_hip_rfchain_destroy(mcrx_hip_rfchain_t q)
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) return MCRX_OK;
     (void)hipDeviceSynchronize();
-    if (q->tab) (void)hipFree(q->tab);
+    q->tab.release();
     q->clip.release();
     delete q;
     return MCRX_OK;
@@ -251,40 +226,24 @@ static void rfchain_launch(uint32_t stages, const RfchainArgs &a, dim3 grid, hip
     }
 }
 
-// rows of the table the samples pos .. pos + n - 1 read (n >= 1): their own grid rows and the one behind the last
-static uint64_t rfchain_rows(uint64_t pos, uint64_t n, uint32_t L) { return (((pos & (((uint64_t)1 << L) - 1)) + n - 1) >> L) + 2; }
-
 extern "C" int mcrx_hip_rfchain_execute_device(mcrx_hip_rfchain_t q, const void *d_in, uint64_t first_sample, size_t n, void *d_out, void *stream)
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_rf_err = "null handle"; return MCRX_EINVAL; }
-    if (!d_in || !d_out) { g_rf_err = "null buffer"; return MCRX_EINVAL; }
     const mcrx_hip_rfchain_config &c = q->cfg;
     const bool in16 = c.input_format == IQ_SC16, out16 = c.output_format == IQ_SC16;
-    const uintptr_t pi = reinterpret_cast<uintptr_t>(d_in), po = reinterpret_cast<uintptr_t>(d_out);
-    if (pi & (in16 ? 3u : 7u)) { g_rf_err = in16 ? "d_in must be 4-byte aligned" : "d_in must be 8-byte aligned"; return MCRX_EINVAL; }
-    if (po & (out16 ? 3u : 7u)) { g_rf_err = out16 ? "d_out must be 4-byte aligned" : "d_out must be 8-byte aligned"; return MCRX_EINVAL; }
-    if (n > ((size_t)1 << 32)) { g_rf_err = "at most 2^32 samples a call"; return MCRX_EINVAL; }      // (a lane per pair, 2^31 lanes a launch)
-    const size_t si = in16 ? 4u : 8u, so = out16 ? 4u : 8u;
-    if (pi < po + n * so && po < pi + n * si && !(pi == po && in16 == out16)) {
-        g_rf_err = "d_in and d_out overlap: in-place use takes d_in == d_out and equal formats";
-        return MCRX_EINVAL;
-    }
+    const uint32_t si = in16 ? 4u : 8u, so = out16 ? 4u : 8u;
+    if (const char *bad = stream_call_check(reinterpret_cast<uintptr_t>(d_in), reinterpret_cast<uintptr_t>(d_out), n, si, so, 0, true, false,
+                                            "d_in and d_out overlap: in-place use takes d_in == d_out and equal formats")) { g_rf_err = bad; return MCRX_EINVAL; }
     if (n == 0) return MCRX_OK;
     hipStream_t st = (hipStream_t)stream;
     const bool osc = (c.stages & MCRX_RFCHAIN_OSCILLATOR) != 0;
     const uint32_t L = c.pn_log2_block;
-    uint32_t cap = 0;                                                   // oscillator: the rows of the table a span may use
+    uint64_t cap = 0;                                                   // oscillator: the rows of the table a span may use (span_plan.hpp)
     if (osc) {
-        const uint64_t want = rfchain_rows(first_sample, n, L);
-        cap = (uint32_t)(want < q->cap ? want : q->cap);
-        if (cap > q->tab_rows) {                                        // grow (hipFree waits for the calls in flight); steady state: never
-            const uint64_t twice = 2ull * q->tab_rows < q->cap ? 2ull * q->tab_rows : q->cap;
-            const uint32_t rows = (uint32_t)(twice > cap ? twice : cap);
-            if (q->tab) { RFCHK(hipFree(q->tab)); q->tab = nullptr; q->tab_rows = 0; }
-            RFCHK(hipMalloc((void **)&q->tab, (size_t)rows * sizeof(float)));
-            q->tab_rows = rows;
-        }
+        cap = span_cap(span_rows(span_frac(first_sample, L), n, L), q->cap);
+        const uint64_t have = q->tab.bytes / sizeof(float);
+        if (cap > have) MCRX_OP_CHK(g_rf_err, q->tab.ensure((size_t)span_grow(have, q->cap, cap) * sizeof(float)));
     }
     RfchainArgs a = {};
     a.clip = q->clip.device(); a.order = c.order;
@@ -297,25 +256,24 @@ extern "C" int mcrx_hip_rfchain_execute_device(mcrx_hip_rfchain_t q, const void 
     for (size_t off = 0; off < n; ) {
         size_t m = n - off;
         if (osc) {
-            const uint64_t avail = ((uint64_t)(cap - 1) << L) - (pos & (((uint64_t)1 << L) - 1));
-            m = m < avail ? m : (size_t)avail;
-            a.L = L; a.row0 = pos >> L; a.rows = (uint32_t)rfchain_rows(pos, m, L); a.tab = q->tab;
+            const Span<uint64_t> s = span_next(pos, m, L, cap);
+            m = (size_t)s.m;
+            a.L = L; a.row0 = s.row0; a.rows = (uint32_t)s.rows; a.tab = q->tab.as<float>();
             a.finv = std::ldexp(1.0f, -(int)L);
-            hipLaunchKernelGGL(rfchain_phase_kernel, dim3((a.rows + 255) / 256), dim3(256), 0, st, q->pt, q->tab, a.row0, a.rows, L);
-            RFCHK(hipGetLastError());
+            hipLaunchKernelGGL(rfchain_phase_kernel, dim3((a.rows + 255) / 256), dim3(256), 0, st, q->pt, q->tab.as<float>(), a.row0, a.rows, L);
+            MCRX_OP_CHK(g_rf_err, hipGetLastError());
         }
         a.in = static_cast<const char *>(d_in) + off * si;
         a.out = static_cast<char *>(d_out) + off * so;
         a.pos = pos; a.n = m;
-        const uint64_t pairs = ((pos & 1u) + m + 1) >> 1;
-        const dim3 grid((unsigned)((pairs + 255) / 256));
+        const dim3 grid((unsigned)((iq_pairs(pos, m) + 255) / 256));
         if (in16) { if (out16) rfchain_launch<IQ_SC16, IQ_SC16>(c.stages, a, grid, st); else rfchain_launch<IQ_SC16, IQ_CF32>(c.stages, a, grid, st); }
         else      { if (out16) rfchain_launch<IQ_CF32, IQ_SC16>(c.stages, a, grid, st); else rfchain_launch<IQ_CF32, IQ_CF32>(c.stages, a, grid, st); }
-        RFCHK(hipGetLastError());
+        MCRX_OP_CHK(g_rf_err, hipGetLastError());
         pos += m;
         off += m;
     }
-    if (out16) RFCHK(q->clip.mark(st));
+    if (out16) MCRX_OP_CHK(g_rf_err, q->clip.mark(st));
     return MCRX_OK;
 }
 
@@ -329,16 +287,11 @@ extern "C" int mcrx_hip_rfchain_phase_rows(mcrx_hip_rfchain_t q, uint64_t first_
     if (rows == 0) return MCRX_OK;
     hipLaunchKernelGGL(rfchain_phase_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, q->pt,
                        static_cast<float *>(d_table), first_row, rows, q->cfg.pn_log2_block);
-    RFCHK(hipGetLastError());
+    MCRX_OP_CHK(g_rf_err, hipGetLastError());
     return MCRX_OK;
 }
 
 extern "C" int mcrx_hip_rfchain_clipped(mcrx_hip_rfchain_t q, uint64_t *samples, int reset)
 {
-    DevScope dev_scope_(q ? q->device : -1);
-    if (!q) { g_rf_err = "null handle"; return MCRX_EINVAL; }
-    uint64_t n = 0;
-    RFCHK(q->clip.read(&n, reset != 0));
-    if (samples) *samples = n;
-    return MCRX_OK;
+    return op_clipped(q, g_rf_err, samples, reset);
 }

@@ -51,9 +51,10 @@
 #include <vector>
 #include "../../include/mcrx_hip.h"
 #include "devmath.h"
-#include "devscope.hpp"
 #include "fadegen.hpp"
 #include "design.hpp"
+#include "ophost.hpp"
+#include "span_plan.hpp"
 
 namespace mcrx {
 
@@ -287,7 +288,6 @@ __global__ __launch_bounds__(256) void userclock_kernel(UserclockArgs a)
 using namespace mcrx;
 
 static thread_local std::string g_uc_err;
-#define UCCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_uc_err = std::string(#x) + ": " + hipGetErrorString(e_); return MCRX_EHIP; } } while (0)
 
 struct mcrx_hip_userchan_s {
     int device = -1;            // the HIP device the handle was created on: every entry point runs with it current (devscope.hpp)
@@ -300,13 +300,13 @@ struct mcrx_hip_userchan_s {
     uint32_t fade_L = 0, fade_S = 0;
     uint64_t fade_cap = 0;      // the most rows of the gain table a span may use
     void *fplanes = nullptr;    // one allocation: step[1 + S][4 C] (64-bit) | phase[1 + S][4 C] | coef[4 C]
-    float4 *gtab = nullptr; uint64_t gtab_rows = 0;     // the gain table and the rows allocated (grown on demand, never shrunk)
+    DevBuffer gtab;             // the gain table, float4 [row][channel][2]
     bool clock = false;         // a clock on: cplanes holds every user's integers and W
     uint32_t clk_max = 0;       // the configured max_delay
     uint64_t clk_span = 0;      // the most blocks of z a span computes (a multiple of 8)
     std::vector<mcrx_hip_userclock_user> clk_users;     // what a call's two ends are checked against
     void *cplanes = nullptr;    // one allocation: par[C][2] (16-byte words) | W[65][32]
-    float2 *zbuf = nullptr; uint64_t zbuf_blocks = 0;   // z of a span, in the tiles' layout, and the blocks allocated (grown on demand)
+    DevBuffer zbuf;             // z of a span, in the tiles' layout
 };
 
 static const size_t USERCHAN_MAX_GRANULES = (size_t)1 << 28;       // (lanes of a launch and the kernel's 32-bit block arithmetic)
@@ -373,9 +373,9 @@ extern "C" int mcrx_hip_userchan_destroy(mcrx_hip_userchan_t q)
     (void)hipDeviceSynchronize();
     if (q->table) (void)hipFree(q->table);
     if (q->fplanes) (void)hipFree(q->fplanes);
-    if (q->gtab) (void)hipFree(q->gtab);
+    q->gtab.release();
     if (q->cplanes) (void)hipFree(q->cplanes);
-    if (q->zbuf) (void)hipFree(q->zbuf);
+    q->zbuf.release();
     delete q;
     return MCRX_OK;
 }
@@ -387,9 +387,6 @@ extern "C" unsigned mcrx_hip_userchan_lead_blocks(mcrx_hip_userchan_t q)
     if (!q) return 0u;
     return q->clock ? round_up8(q->D + q->clk_max + 16u) : q->lead;
 }
-
-// rows of the gain table the blocks at fraction `frac` of a grid interval, n >= 1 of them, read: their own grid rows and the one behind the last
-static uint64_t userfade_rows(uint64_t frac, uint64_t n, uint32_t L) { return ((frac + n - 1) >> L) + 2; }
 
 // table[r][channel][4] = G[first_row + r], r < rows (rows >= 1), on `st`
 static void userfade_launch_gains(mcrx_hip_userchan_t q, long long first_row, uint32_t rows, float2 *table, hipStream_t st)
@@ -436,37 +433,30 @@ static int userchan_run(mcrx_hip_userchan_t q, const void *d_in, long long first
         const dim3 grid((a.total + 255u) / 256u);
         if (q->rot) hipLaunchKernelGGL((userchan_kernel<true, false>), grid, dim3(256), 0, st, a);
         else        hipLaunchKernelGGL((userchan_kernel<false, false>), grid, dim3(256), 0, st, a);
-        UCCHK(hipGetLastError());
+        MCRX_OP_CHK(g_uc_err, hipGetLastError());
         return MCRX_OK;
     }
-    // fading: spans of at most cap - 1 grid intervals, gain kernel -> main kernel each.  The operator is a function of the absolute
-    // block index, so the spans are invisible in the output; a span ends on a grid row or with the call, both multiples of 8 blocks.
+    // fading: spans of at most cap - 1 grid intervals (span_plan.hpp, on the signed block index), gain kernel -> main kernel each.  The
+    // operator is a function of the absolute block index, so the spans are invisible in the output; a span ends on a grid row or with
+    // the call, both multiples of 8 blocks.
     const uint32_t L = q->fade_L;
-    const uint64_t mask = ((uint64_t)1 << L) - 1;
-    const uint64_t want = userfade_rows((uint64_t)first_block & mask, nblocks, L);
-    const uint64_t cap = want < q->fade_cap ? want : q->fade_cap;
-    if (cap > q->gtab_rows) {                                           // grow (hipFree waits for the calls in flight); steady state: never
-        const uint64_t twice = 2 * q->gtab_rows < q->fade_cap ? 2 * q->gtab_rows : q->fade_cap;
-        const uint64_t rows = twice > cap ? twice : cap;
-        if (q->gtab) { UCCHK(hipFree(q->gtab)); q->gtab = nullptr; q->gtab_rows = 0; }
-        UCCHK(hipMalloc((void **)&q->gtab, (size_t)rows * q->C * 2u * sizeof(float4)));
-        q->gtab_rows = rows;
-    }
-    a.gtab = q->gtab; a.L = L; a.finv = std::ldexp(1.0f, -(int)L);
+    const size_t row_bytes = (size_t)q->C * 2u * sizeof(float4);
+    const uint64_t cap = span_cap(span_rows(span_frac(first_block, L), nblocks, L), q->fade_cap), have = q->gtab.bytes / row_bytes;
+    if (cap > have) MCRX_OP_CHK(g_uc_err, q->gtab.ensure((size_t)span_grow(have, q->fade_cap, cap) * row_bytes));
+    a.gtab = q->gtab.as<float4>(); a.L = L; a.finv = std::ldexp(1.0f, -(int)L);
     for (size_t off = 0; off < nblocks; ) {
         const long long pos = first_block + (long long)off;
-        const uint64_t frac = (uint64_t)pos & mask;
-        const uint64_t avail = ((cap - 1) << L) - frac;
-        const size_t m = nblocks - off < avail ? nblocks - off : (size_t)avail;
-        userfade_launch_gains(q, pos >> L, (uint32_t)userfade_rows(frac, m, L), reinterpret_cast<float2 *>(q->gtab), st);
-        UCCHK(hipGetLastError());
+        const Span<long long> s = span_next(pos, nblocks - off, L, cap);
+        const size_t m = (size_t)s.m;
+        userfade_launch_gains(q, s.row0, (uint32_t)s.rows, q->gtab.as<float2>(), st);
+        MCRX_OP_CHK(g_uc_err, hipGetLastError());
         a.in = static_cast<const float2 *>(d_in) + off * q->C; a.out = static_cast<float4 *>(d_out) + off * q->C / 2u;
         a.total = (uint32_t)(m / 8 * q->C * 4u);
-        a.first_lo = (uint32_t)(uint64_t)pos; a.frac0 = (uint32_t)frac;
+        a.first_lo = (uint32_t)(uint64_t)pos; a.frac0 = (uint32_t)s.frac;
         const dim3 grid((a.total + 255u) / 256u);
         if (q->rot) hipLaunchKernelGGL((userchan_kernel<true, true>), grid, dim3(256), 0, st, a);
         else        hipLaunchKernelGGL((userchan_kernel<false, true>), grid, dim3(256), 0, st, a);
-        UCCHK(hipGetLastError());
+        MCRX_OP_CHK(g_uc_err, hipGetLastError());
         off += m;
     }
     return MCRX_OK;
@@ -493,16 +483,12 @@ extern "C" int mcrx_hip_userchan_apply_tiles(mcrx_hip_userchan_t q, const void *
     if (!userclock_check_range(q, first_block, nblocks, q->D)) return MCRX_EINVAL;
     const size_t lz = q->lead, lead_in = lead_blocks - lz;                 // (lead_blocks >= D + max_delay + 16: z of block first - D has its window)
     const uint64_t span = nblocks < q->clk_span ? nblocks : q->clk_span;
-    if (lz + span > q->zbuf_blocks) {                                       // grow (hipFree waits for the calls in flight); steady state: never
-        if (q->zbuf) { UCCHK(hipFree(q->zbuf)); q->zbuf = nullptr; q->zbuf_blocks = 0; }
-        UCCHK(hipMalloc((void **)&q->zbuf, (size_t)(lz + span) * q->C * sizeof(float2)));
-        q->zbuf_blocks = lz + span;
-    }
+    MCRX_OP_CHK(g_uc_err, q->zbuf.ensure((size_t)(lz + span) * q->C * sizeof(float2)));
     for (size_t off = 0; off < nblocks; ) {
         const size_t m = nblocks - off < span ? nblocks - off : (size_t)span;
         const long long pos = first_block + (long long)off;
-        int rc = userclock_launch(q, static_cast<const float2 *>(d_in) + off * q->C, pos - (long long)lz, lz + m, lead_in, (uint32_t)lz - q->D, q->zbuf, st);
-        if (rc == MCRX_OK) rc = userchan_run(q, q->zbuf, pos, m, lz, static_cast<float2 *>(d_out) + off * q->C, st);
+        int rc = userclock_launch(q, static_cast<const float2 *>(d_in) + off * q->C, pos - (long long)lz, lz + m, lead_in, (uint32_t)lz - q->D, q->zbuf.as<float2>(), st);
+        if (rc == MCRX_OK) rc = userchan_run(q, q->zbuf.ptr, pos, m, lz, static_cast<float2 *>(d_out) + off * q->C, st);
         if (rc != MCRX_OK) return rc;
         off += m;
     }
@@ -525,12 +511,8 @@ static const char *userfade_check_user(const mcrx_hip_userfade_config *f, const 
 {
     if (!u->enabled) return nullptr;
     const double B = (double)(1u << f->log2_block);
-    for (unsigned i = ray0; i < ray1; i++) {
-        if (!std::isfinite(u->doppler[i]) || !std::isfinite(u->los_doppler[i])) return "a Doppler is not finite";
-        if (u->doppler[i] < 0.0) return "doppler must not be negative";
-        if (u->doppler[i] * B > 0.125 || std::fabs(u->los_doppler[i]) * B > 0.125) return "a Doppler times the update interval exceeds 1/8: the grid does not sample the gain";
-        if (!std::isfinite(u->rice_k[i]) || u->rice_k[i] < 0.f) return "rice_k must be finite and not negative";
-    }
+    for (unsigned i = ray0; i < ray1; i++)
+        if (const char *bad = fade_ray_check(B, u->doppler[i], u->los_doppler[i], u->rice_k[i])) return bad;
     return nullptr;
 }
 
@@ -564,7 +546,7 @@ extern "C" int mcrx_hip_userfade_set(mcrx_hip_userchan_t q, const mcrx_hip_userf
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_uc_err = "null handle"; return MCRX_EINVAL; }
     if (!f) {                                                           // off: the planes and the table go with the handle
-        UCCHK(hipDeviceSynchronize());
+        MCRX_OP_CHK(g_uc_err, hipDeviceSynchronize());
         q->fade = false;
         return MCRX_OK;
     }
@@ -589,9 +571,9 @@ extern "C" int mcrx_hip_userfade_set(mcrx_hip_userchan_t q, const mcrx_hip_userf
             for (uint32_t k = 0; k < terms; k++) { step[k * lanes + lane] = (uint64_t)st[k]; phase[k * lanes + lane] = ph[k]; }
             coef[lane * 2] = co[0]; coef[lane * 2 + 1] = co[1];
         }
-    UCCHK(hipDeviceSynchronize());                                      // calls in flight read the planes about to go
+    MCRX_OP_CHK(g_uc_err, hipDeviceSynchronize());                                      // calls in flight read the planes about to go
     void *planes = nullptr;
-    UCCHK(hipMalloc(&planes, bytes));
+    MCRX_OP_CHK(g_uc_err, hipMalloc(&planes, bytes));
     hipError_t e = hipMemcpy(planes, host.data(), bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(planes); g_uc_err = std::string("fading planes: ") + hipGetErrorString(e); return MCRX_EHIP; }
     if (q->fplanes) (void)hipFree(q->fplanes);
@@ -612,7 +594,7 @@ extern "C" int mcrx_hip_userfade_gains(mcrx_hip_userchan_t q, long long first_ro
     if (!d_table || (reinterpret_cast<uintptr_t>(d_table) & 15u)) { g_uc_err = "d_table must be a 16-byte aligned device buffer"; return MCRX_EINVAL; }
     if (rows == 0) return MCRX_OK;
     userfade_launch_gains(q, first_row, rows, static_cast<float2 *>(d_table), (hipStream_t)stream);
-    UCCHK(hipGetLastError());
+    MCRX_OP_CHK(g_uc_err, hipGetLastError());
     return MCRX_OK;
 }
 
@@ -699,7 +681,7 @@ static int userclock_launch(mcrx_hip_userchan_t q, const float2 *in, long long f
     a.lead = (uint32_t)lead_blocks; a.in_rows = (uint32_t)((lead_blocks + nblocks) / 8); a.skip = skip;
     const dim3 grid((unsigned)((nblocks + UCLK_BLOCKS - 1u) / UCLK_BLOCKS), (q->C + UCLK_CH - 1u) / UCLK_CH);
     hipLaunchKernelGGL(userclock_kernel, grid, dim3(256), 0, st, a);
-    UCCHK(hipGetLastError());
+    MCRX_OP_CHK(g_uc_err, hipGetLastError());
     return MCRX_OK;
 }
 
@@ -738,7 +720,7 @@ extern "C" int mcrx_hip_userclock_set(mcrx_hip_userchan_t q, const mcrx_hip_user
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_uc_err = "null handle"; return MCRX_EINVAL; }
     if (!f) {                                                           // off: the planes and the buffer go with the handle
-        UCCHK(hipDeviceSynchronize());
+        MCRX_OP_CHK(g_uc_err, hipDeviceSynchronize());
         q->clock = false;
         return MCRX_OK;
     }
@@ -760,9 +742,9 @@ extern "C" int mcrx_hip_userclock_set(mcrx_hip_userchan_t q, const mcrx_hip_user
         else           { w[0] = (uint64_t)MCRX_USERCLOCK_MIN_DELAY << 32; w[1] = w[2] = w[3] = 0; }
     }
     std::memcpy(host.data() + words, userclock_table(), wn * sizeof(float));
-    UCCHK(hipDeviceSynchronize());                                      // calls in flight read the planes about to go
+    MCRX_OP_CHK(g_uc_err, hipDeviceSynchronize());                                      // calls in flight read the planes about to go
     void *planes = nullptr;
-    UCCHK(hipMalloc(&planes, bytes));
+    MCRX_OP_CHK(g_uc_err, hipMalloc(&planes, bytes));
     hipError_t e = hipMemcpy(planes, host.data(), bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(planes); g_uc_err = std::string("clock planes: ") + hipGetErrorString(e); return MCRX_EHIP; }
     if (q->cplanes) (void)hipFree(q->cplanes);

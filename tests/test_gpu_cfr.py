@@ -316,6 +316,23 @@ def test_cuts(product, fout, P):
     one.close(); pieces.close()
 
 
+def test_the_scratch_buffers_grow_and_are_reused(product):
+    """passes = 3 (both scratch buffers), half_len = 8: 300 samples in the first allocation, 20 000 that force both to grow, 300 again in
+    the grown ones -- each call the bits of a fresh handle's"""
+    torch = _torch()
+    H, P = 8, 3
+    d_x = torch.from_numpy(noise(20000 + 2 * P * H, "10%", 91)).cuda()
+    kw = dict(taps=taps_for(product, H), passes=P)
+    cf = product.cfr(A_MODEL, **kw)
+    for n in (300, 20000, 300):
+        fresh = product.cfr(A_MODEL, **kw)
+        got, want = cf.execute(d_x[:n + 2 * P * H]), fresh.execute(d_x[:n + 2 * P * H])
+        assert int(got.shape[0]) == n and fresh.stats()[0][0] > 0
+        assert torch.equal(torch.view_as_real(got).view(torch.int32), torch.view_as_real(want).view(torch.int32)), n
+        fresh.close()
+    cf.close()
+
+
 # ---------------------------------------------------------------------------------------------- 5. sc16 is Q of cf32
 @pytest.mark.parametrize("P", [1, 2])
 def test_sc16_is_q_of_cf32(product, P):

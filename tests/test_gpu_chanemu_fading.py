@@ -130,8 +130,26 @@ def test_cut_anywhere(product, fmt):
     assert torch.equal(bits(ones[0][0]), bits(ones[1][0])) and ones[0][1] == ones[1][1]       # spans are invisible
 
 
+def test_the_gain_table_grows_and_is_reused(product):
+    """L = 1, the default table, from an odd position: 130 samples in the first allocation (67 rows), 5 000 that force the table to grow,
+    130 again in the grown one -- each call the bits of a fresh handle's"""
+    torch = base._torch()
+    x, d_x = base.samples(5000)
+    cfg = dict(taps=[(0, 1.0), (3, 0.5j)], cfo_step=CFO_STEP, phase0=PHASE0, gain=GAIN, noise_std=NOISE_STD, seed=SEED, fading=dict(FADE_C, table_rows=0))
+    ce = product.chanemu(**cfg)
+    for n in (130, 5000, 130):
+        fresh = product.chanemu(**cfg)
+        ce.reset(at=1001); fresh.reset(at=1001)
+        got, want = ce.execute(d_x[:n]), fresh.execute(d_x[:n])
+        assert int(got.shape[0]) == n and ce.position() == 1001 + n
+        assert torch.equal(bits(got), bits(want)), n
+        fresh.close()
+    assert float(got.abs().max()) > 0.0
+    ce.close()
+
+
 # ---------------------------------------------------------------------------------------------- 3. far positions
-FAR = [("2^40 + 3", 2 ** 40 + 3), ("across 2^33", 2 ** 33 - 1000), ("across 2^64", 2 ** 64 - 5000)]
+FAR =[("2^40 + 3", 2 ** 40 + 3), ("across 2^33", 2 ** 33 - 1000), ("across 2^64", 2 ** 64 - 5000)]
 
 
 @pytest.mark.parametrize("name,p", FAR, ids=["2p40", "2p33", "wrap"])

@@ -312,6 +312,22 @@ def test_cuts_spans_and_in_place(product, fin, fout):
     rf.close()
 
 
+def test_the_phase_table_grows_and_is_reused(product):
+    """L = 1, the default table, from an odd position: 130 samples in the first allocation (67 rows), 5 000 that force the table to grow,
+    130 again in the grown one -- each call the bits of a fresh handle's"""
+    torch = _torch()
+    x, d_x = samples(5000, seed=17)
+    kw = dict(chain_kw(product, 7), phase_noise=dict(PN, log2_block=1, table_rows=0))
+    rf = product.rfchain(**kw)
+    for n in (130, 5000, 130):
+        fresh = product.rfchain(**kw)
+        got, want = rf.execute(d_x[:n], first_sample=1001), fresh.execute(d_x[:n], first_sample=1001)
+        assert int(got.shape[0]) == n and torch.equal(bits(got), bits(want)), n
+        fresh.close()
+    assert not torch.equal(bits(got), bits(d_x[:130]))
+    rf.close()
+
+
 # ---------------------------------------------------------------------------------------------- 5. sc16 is Q of cf32
 @pytest.mark.parametrize("mask", range(8))
 def test_sc16_is_q_of_cf32(product, mask):

@@ -199,6 +199,25 @@ def test_spans_of_the_gain_table(product):
     assert torch.equal(bits(outs[0]), bits(outs[1])) and torch.equal(bits(outs[2]), bits(outs[1]))
 
 
+def test_the_gain_table_grows_and_is_reused(product):
+    """L = 3, 8 channels, the default table: 64 blocks in the first allocation (10 rows), 1 024 that force the table to grow, 64 again in
+    the grown one -- each call the bits of a fresh handle's"""
+    torch = _torch()
+    C_, total = 8, 1024
+    chans = table(C_)
+    fade = fading(chans, 3, 8)
+    lead = model.lead_of(chans)
+    d_x = device_tiles(samples(C_, lead + total))
+    uc = product.userchan(channels=chans, fading=fade)
+    for n in (64, 1024, 64):
+        fresh = product.userchan(channels=chans, fading=fade)
+        got, want = uc.apply(d_x, 8 * 999, n), fresh.apply(d_x, 8 * 999, n)
+        assert int(got.numel()) == n * C_ and float(got.abs().max()) > 1.0
+        assert torch.equal(bits(got), bits(want)), n
+        fresh.close()
+    uc.close()
+
+
 # ---------------------------------------------------------------------------------------------- 6. shards
 def test_shards_keep_their_users(product):
     C_ = 8
