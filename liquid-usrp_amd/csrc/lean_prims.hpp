@@ -20,10 +20,14 @@ __device__ __forceinline__ v2f cmulc_pk(v2f a, v2f tw)
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]" : "=v"(r) : "v"(a), "v"(tw), "v"(t));
     return r;
 }
-// a e^{-j 2 pi rev} on the transcendental unit
+// a e^{-j 2 pi rev} on the transcendental unit.  cos and sin go straight into cmulc_pk's assembly, which the compiler does not look
+// into: the wait state a VALU instruction needs behind the transcendental unit is tied to the pair here (devmath.h: trans_settle --
+// an s_nop, no VALU slot).  Without it the packed multiply is safe only while the scheduler happens to emit the sine between the
+// cosine and the multiply, which reads the cosine alone.
 __device__ __forceinline__ v2f rot_down_pk(v2f a, float rev)
 {
     v2f cs; cs.x = __builtin_amdgcn_cosf(rev); cs.y = __builtin_amdgcn_sinf(rev);
+    asm("s_nop 0" : "+v"(cs));
     return cmulc_pk(a, cs);
 }
 // sg x + p, sg = the low (HI = 0) or high (HI = 1) half of `sgp` for both components
@@ -36,8 +40,57 @@ __device__ __forceinline__ v2f bfly_pk(v2f x, v2f sgp, v2f p)
     return r;
 }
 
+// ---- the frame oscillator carried per lane.  Sample k of a window has the phase th_ws + k dth (32-bit turns).  One symbol on, the window
+// starts at th_ws + step, step = (L - cb) dth + cb dnew, and the step per sample is dnew = dth + delta: the new phase of sample k is the
+// old one + step + k delta (mod 2^32) -- no product with dth.  dth, dnew and step are wave-uniform and stay in SGPRs; delta is the pilot
+// loop's trim itself, rint(dphi * 683565.2755...) with dphi wrapped into [-pi, pi] (dphi - 2 pi rint(dphi / 2 pi); a dphi that is not
+// finite wraps to NaN, which converts to 0): |delta| <= 2 147 484 < 2^23, a signed 24-bit number, and k <= 511.  v_mad_i32_i24 multiplies
+// the sign-extended low 24 bits of its factors and keeps the low 32 bits of product + addend: exactly k delta + addend modulo 2^32, at
+// full rate where v_mul_lo_u32 is a slow-rate instruction.
+__device__ __forceinline__ uint32_t phase_step(uint32_t ph, uint32_t step, int k, int32_t delta)
+{
+    const uint32_t b = ph + step;
+    uint32_t r;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(k), "s"(delta), "v"(b));
+    return r;
+}
+// the trim as an SGPR: converted on the vector unit, then read.  (Left to itself the compiler reads the first lane in FRONT of the
+// convert, whose result -- and every sum with it: the oscillator's step -- then lives in a VGPR.)
+__device__ __forceinline__ int32_t trim_sgpr(float dphi)
+{
+    int d = __float2int_rn(dphi * (1e-3f * 683565275.5764316f));
+    asm("" : "+v"(d));
+    return __builtin_amdgcn_readfirstlane(d);
+}
+
+// t * m for t = 0 .. 7 without the slow-rate 32-bit multiply (a window's lane offset: tiles in front of the lane's sample, times the
+// tile stride; exact modulo 2^32 like the product)
+__device__ __forceinline__ uint32_t small_times(uint32_t t, uint32_t m)
+{
+    return ((t & 1u) ? m : 0u) + ((t & 2u) ? 2u * m : 0u) + ((t & 4u) ? 4u * m : 0u);
+}
+// Global memory at a wave-uniform base + a 32-bit lane offset, the base taken as it stands in an SGPR pair: the scalar-base form of
+// global_load / global_store, no vector address instruction.  (Without the barrier the loop-invariant lane part is hoisted as a
+// 64-bit vector pointer and every access pays a v_lshl_add_u64 for the scalar part that moves; the lane offset passes the same barrier
+// so that it is widened next to the access, where instruction selection sees a 32-bit offset.  An integer that becomes a pointer
+// again has lost its address space: it is named.)
+template <typename T>
+__device__ __forceinline__ T gload_s(const void *base, uint32_t off)
+{
+    uint64_t v = reinterpret_cast<uint64_t>(base);
+    asm("" : "+s"(v), "+v"(off));
+    return *(const __attribute__((address_space(1))) T *)(v + off);
+}
+template <typename T>
+__device__ __forceinline__ void gstore_s(void *base, uint32_t off, T val)
+{
+    uint64_t v = reinterpret_cast<uint64_t>(base);
+    asm("" : "+s"(v), "+v"(off));
+    *(__attribute__((address_space(1))) T *)(v + off) = val;
+}
+
 template <int H>
-__device__ __forceinline__ float xch(float v, int bp32)         // v of lane l ^ H, through the LDS crossbar
+__device__ __forceinline__ float xch(float v, int bp32)        // v of lane l ^ H, through the LDS crossbar
 {
     if constexpr (H == 32) return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bp32, __builtin_bit_cast(int, v)));
     else return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (H << 10) | 0x1F));

@@ -25,8 +25,26 @@
 #include "demod_pk.hpp"
 namespace lean {
 
-// the symbols of one frame.  Everything passed by value is wave-uniform unless it says "lane"
-template <int MOD, int XB, int MM = 64>
+// A frame for symbols<.., FIX>: every window -- and one behind the last, so that no symbol has to ask whether there is a next -- lies
+// inside the buffer, and the window's phase inside the tiles alternates (2 L a whole number of tiles).  Wave-uniform; the same
+// expressions as symbols' own.
+__device__ __forceinline__ bool frame_inside(const SyncArgs &a, const PayloadJob *job)
+{
+    const SyncConsts &c = a.c;
+    const int L = c.L, cb = c.cp - c.backoff, Md = c.M_data;
+    const uint32_t mod_len = rfl(job->s.mod_len);
+    const uint32_t nsym = (mod_len + (uint32_t)Md - 1u) / (uint32_t)Md;
+    const int64_t ws0 = job->s.cur + (int64_t)job->s.timer - 1 - L + 1 + cb;
+    const int32_t r_ws = (int32_t)rfl((uint32_t)(ws0 - a.buf_first));
+    const int32_t r_max = (int32_t)(a.end - a.buf_first) - 1;
+    return ((2 * L) & (MCRX_TILE_S - 1)) == 0 && nsym > 0 && r_ws >= 0 && (int64_t)r_ws + (int64_t)nsym * L + (WV - 1) <= (int64_t)r_max;
+}
+
+// the symbols of one frame.  Everything passed by value is wave-uniform unless it says "lane".
+// FIX: the configuration every default receiver runs -- at most 8 pilots, soft decisions, equalised symbols kept -- as compile-time
+// constants (the three are loop-invariant, and as run-time values each is a branch inside the symbol loop), for a frame that is
+// frame_inside: payload_lean_body asks both before it picks the instantiation.  64-sample windows, BPSK / QPSK.
+template <int MOD, int XB, int MM = 64, bool FIX = false>
 __device__ __forceinline__ uint32_t symbols(const SyncArgs &a, const PayloadJob *job, const uint32_t ch, const uint32_t j,
                                             const uint32_t *qsg, const uint32_t *qnb, const int *qsrc)
 {
@@ -54,7 +72,7 @@ __device__ __forceinline__ uint32_t symbols(const SyncArgs &a, const PayloadJob 
         if (st & 1) sgp[st >> 1].y = up ? -1.f : 1.f; else sgp[st >> 1].x = up ? -1.f : 1.f;
     }
     const int Mp = c.M_pilot;
-    const bool p8 = Mp <= 8;                                            // both projections in one row: pf0 in lanes 0..7, pf1 in lanes 8..15
+    const bool p8 = FIX ? true : Mp <= 8;                               // both projections in one row: pf0 in lanes 0..7, pf1 in lanes 8..15
     const float pf0 = (l < Mp) ? c.Pfit[l] : 0.f, pf1 = (l < Mp) ? c.Pfit[Mp + l] : 0.f;
     const float pfc = p8 ? ((l < 8) ? pf0 : ((l < 16 && l - 8 < Mp) ? c.Pfit[Mp + l - 8] : 0.f)) : pf0;
     const int psrc = qsrc[l < Mp ? l : 0] << 2;                          // ds_bpermute address of the lane that holds pilot l
@@ -67,32 +85,43 @@ __device__ __forceinline__ uint32_t symbols(const SyncArgs &a, const PayloadJob 
     const int64_t t_ev0 = job->s.cur + (int64_t)job->s.timer - 1;
     const int64_t ws0 = t_ev0 - L + 1 + cb;
     uint32_t dth = rfl(job->s.nco_dtheta);
-    uint32_t th_ws = rfl(job->s.nco_theta_ref + (uint32_t)(ws0 - job->s.nco_t_ref) * job->s.nco_dtheta);
+    const uint32_t th_ws0 = rfl(job->s.nco_theta_ref + (uint32_t)(ws0 - job->s.nco_t_ref) * job->s.nco_dtheta);
+    uint32_t ph_l = th_ws0 + (uint32_t)l * dth;                          // lane: the oscillator's phase at this lane's sample (lean_prims.hpp: phase_step)
     uint32_t pc4 = rfl(job->s.pilot_count) * 4u;                         // byte offset into the polarity table
     float phi_prime = job->s.phi_prime, p1_prime = job->s.p1_prime;
     int32_t r_ws = (int32_t)rfl((uint32_t)(ws0 - a.buf_first));
     const float2 *chb = a.chan + ((size_t)a.chan_off + ch) * MCRX_TILE_S;
     const uint32_t tstride = a.chan_stride * (uint32_t)MCRX_TILE_S;      // elements between a channel's consecutive tiles
     const int32_t r_max = (int32_t)(a.end - a.buf_first) - 1;
-    const bool soft_mode = c.payload_soft != 0;
-    const bool keep_syms = a.no_syms == 0;                              // (skip_framesyms = 2: the caller never reads stats.framesyms -- not even stored)
+    const bool soft_mode = FIX ? true : c.payload_soft != 0;
+    const bool keep_syms = FIX ? true : a.no_syms == 0;                 // (skip_framesyms = 2: the caller never reads stats.framesyms -- not even stored)
     uint8_t *soft = a.jsoft + (size_t)j * 8 * c.max_enc_len;
     const uint64_t syms_off = job->syms_off;
     uint8_t *syms = a.sarena + (((uint64_t)rfl((uint32_t)(syms_off >> 32)) << 32) | rfl((uint32_t)syms_off));
     const uint32_t l4 = (uint32_t)l * 4u;
 
-    // the window's phase inside the tiles and the lane offset that goes with it: the two most recent ones are kept (L = 72 over
-    // 16-sample tiles alternates between two phases), so the symbol loop never recomputes them
+    // a window at phase ph inside the tiles: lane l reads sample q = ph + l, tile q >> 4 = (l >> 4) + the carry of ph + (l & 15) -- the
+    // lane's own tiles are a product made once per frame, the carry is one tile more.  (L = 54, the 48-subcarrier default, changes
+    // phase with every symbol: this runs per symbol there.)
+    const uint32_t lt_off = (uint32_t)(l >> MCRX_TILE_SH) * tstride;
+    auto lane_off = [&](int ph) -> uint32_t {
+        const uint32_t q = (uint32_t)ph + (uint32_t)(l & (MCRX_TILE_S - 1));
+        return (lt_off + ((q >> MCRX_TILE_SH) ? tstride : 0u) + (q & (uint32_t)(MCRX_TILE_S - 1))) * 8u;
+    };
+    auto win_base = [&](int32_t rw) -> const char * {                    // scalar: the tile the window starts in
+        return reinterpret_cast<const char *>(chb + (size_t)(uint32_t)(rw >> MCRX_TILE_SH) * tstride);
+    };
+    // the general window load: the phase inside the tiles and the lane offset that goes with it, the two most recent ones kept (L = 72
+    // over 16-sample tiles alternates between two phases); a window that leaves the buffer is clamped sample by sample
     int q0 = -1, q1 = -1; uint32_t offl = 0, offl1 = 0;
     auto load_win = [&](int32_t rw) -> v2f {
         if (rw >= 0 && rw + (WV - 1) <= r_max) {
             const int ph = rw & (MCRX_TILE_S - 1);
             if (ph != q0) {
                 const int tq = q0; const uint32_t to = offl; q0 = q1; offl = offl1; q1 = tq; offl1 = to;      // swap: the other cached phase
-                if (ph != q0) { q0 = ph; const uint32_t q = (uint32_t)ph + (uint32_t)l; offl = ((q >> MCRX_TILE_SH) * tstride + (q & (uint32_t)(MCRX_TILE_S - 1))) * 8u; }
+                if (ph != q0) { q0 = ph; offl = lane_off(ph); }
             }
-            const char *base = reinterpret_cast<const char *>(chb + (size_t)(uint32_t)(rw >> MCRX_TILE_SH) * tstride);
-            v2f v = *reinterpret_cast<const v2f *>(base + offl);
+            v2f v = *reinterpret_cast<const v2f *>(win_base(rw) + offl);
             if constexpr (MM < WV) { if (l >= MM) { v.x = 0.f; v.y = 0.f; } }      // (a window is MM samples: the lanes behind it hold zeros)
             return v;
         }
@@ -109,40 +138,38 @@ __device__ __forceinline__ uint32_t symbols(const SyncArgs &a, const PayloadJob 
     // next window requested right behind them, everything the next wait covers is a whole symbol old.
     // (only a frame's last symbol can be partly filled -- mod_len = ceil(nbits / bps), so every earlier one ends below nbits --
     //  and the last one is stored behind the loop: the stores inside it take the first branch without asking)
+    // ssym / ssoft: scalar bases of the symbol's row; the lane adds its 32-bit so_sym / so_soft
+    auto store_whole = [&](uint8_t *ssym, uint8_t *ssoft, v2f Z, uint64_t sw) {
+        if (isdata) {
+#if PL_NT_STORE
+            if (keep_syms) __builtin_nontemporal_store(Z, reinterpret_cast<v2f *>(ssym + so_sym));
+#else
+            if (keep_syms) *reinterpret_cast<v2f *>(ssym + so_sym) = Z;
+#endif
+            uint8_t *dst = ssoft + so_soft;
+            if constexpr (bps == 1) dst[0] = (uint8_t)sw;
+            else if constexpr (bps == 2) *reinterpret_cast<uint16_t *>(dst) = (uint16_t)sw;
+            else {                                                      // (4 or 6 bytes at a multiple of 2)
+                *reinterpret_cast<uint16_t *>(dst) = (uint16_t)sw;
+                *reinterpret_cast<uint16_t *>(dst + 2) = (uint16_t)(sw >> 16);
+                if constexpr (bps == 6) *reinterpret_cast<uint16_t *>(dst + 4) = (uint16_t)(sw >> 32);
+            }
+        }
+    };
     auto store_symbol = [&](uint32_t ps, v2f Z, uint64_t sw, bool inner) {
         uint8_t *ssym = syms + (size_t)ps * 8, *ssoft = soft + (size_t)ps * bps;
-        if (inner || (ps + (uint32_t)Md <= mod_len && (ps + (uint32_t)Md) * bps <= nbits)) {
-            if (isdata) {
-#if PL_NT_STORE
-                if (keep_syms) __builtin_nontemporal_store(Z, reinterpret_cast<v2f *>(ssym + so_sym));
-#else
-                if (keep_syms) *reinterpret_cast<v2f *>(ssym + so_sym) = Z;
-#endif
-                uint8_t *dst = ssoft + so_soft;
-                if constexpr (bps == 1) dst[0] = (uint8_t)sw;
-                else if constexpr (bps == 2) *reinterpret_cast<uint16_t *>(dst) = (uint16_t)sw;
-                else {                                                  // (4 or 6 bytes at a multiple of 2)
-                    *reinterpret_cast<uint16_t *>(dst) = (uint16_t)sw;
-                    *reinterpret_cast<uint16_t *>(dst + 2) = (uint16_t)(sw >> 16);
-                    if constexpr (bps == 6) *reinterpret_cast<uint16_t *>(dst + 4) = (uint16_t)(sw >> 32);
-                }
-            }
-        } else if (isdata && ps + (uint32_t)dr < mod_len) {              // the frame's last symbol: part of the subcarriers, part of their bits
+        if (inner || (ps + (uint32_t)Md <= mod_len && (ps + (uint32_t)Md) * bps <= nbits)) store_whole(ssym, ssoft, Z, sw);
+        else if (isdata && ps + (uint32_t)dr < mod_len) {                // the frame's last symbol: part of the subcarriers, part of their bits
             if (keep_syms) *reinterpret_cast<v2f *>(ssym + so_sym) = Z;
             const uint32_t b0 = (ps + (uint32_t)dr) * bps;
 #pragma unroll
             for (unsigned kb = 0; kb < bps; kb++) if (b0 + kb < nbits) ssoft[so_soft + kb] = (uint8_t)(sw >> (8 * kb));
         }
     };
-    v2f cur = load_win(r_ws);
     v2f Zp = {0.f, 0.f}; uint64_t swp = 0;                               // the previous symbol's results, not stored yet
     uint32_t psi = 0;
-    for (uint32_t n = 0; n < nsym; n++) {
-        const uint32_t sgn = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(qsg) + (pc4 + (l < 16 ? l4 : 0u)));
-        // ---- oscillator (the window's registers are free after it), the previous symbol's stores, the next window
-        v2f x = rot_down_pk(cur, u32rev(th_ws + (uint32_t)l * dth));
-        if (n + 1 < nsym) cur = load_win(r_ws + L);
-        if (n > 0) store_symbol(psi - (uint32_t)Md, Zp, swp, true);
+    // a symbol behind its oscillator: transform, equaliser, pilots, de-rotation, soft bits, trim; steps every counter one symbol on
+    auto finish = [&](v2f x, uint32_t sgn) {
         // ---- MM-point DIF transform, equaliser
         if constexpr (MM == 64) x = fft64<XB>(x, tw, sgp, bp32);
         else x = fft48<XB>(x, tw, sgp, r3, bp32, l);
@@ -171,23 +198,70 @@ __device__ __forceinline__ uint32_t symbols(const SyncArgs &a, const PayloadJob 
             p1 = row_total_dpp(pf1 * y);
         }
         pc4 += (uint32_t)Mp * 4u; pc4 = pc4 >= 255u * 4u ? pc4 - 255u * 4u : pc4;
-        p1 = 0.3f * p1 + (1.0f - 0.3f) * p1_prime;
+        {   // two rounded products and their sum, in every instantiation: left to the compiler, some copies of this loop fuse one product into
+            // the sum and others do not (the loops before the FIX split never did), and the slope's last bit moves
+#pragma clang fp contract(off)
+            p1 = 0.3f * p1 + (1.0f - 0.3f) * p1_prime;
+        }
         p1_prime = p1;
         // ---- de-rotate, soft bits (stored at the top of the next turn)
         Zp = rot_down_pk(x, fmaf(p1, fxr, p0 * 0.15915494309189535f));
         swp = demod_pk<MOD>(reinterpret_cast<const uint8_t *>(qnb), Zp, soft_mode);
         psi += (uint32_t)Md;
-        // ---- oscillator trim (liquid ofdmframesync: the phase at the next window start uses the old step up to this event)
+        // ---- oscillator trim (liquid ofdmframesync: the phase at the next window start uses the old step up to this event).
+        // Scalars; the lanes' phases take the window's step and their sample index times the trim (lean_prims.hpp: phase_step)
         float dphi = p0 - phi_prime;
         dphi -= TWO_PI_F * rintf(dphi * 0.15915494309189535f);
         phi_prime = p0;
-        const uint32_t dnew = dth + rfl((uint32_t)__float2int_rn(dphi * (1e-3f * 683565275.5764316f)));
-        th_ws += (uint32_t)(L - cb) * dth + (uint32_t)cb * dnew;
+        const int32_t delta = trim_sgpr(dphi);
+        const uint32_t dnew = dth + (uint32_t)delta;
+        ph_l = phase_step(ph_l, (uint32_t)(L - cb) * dth + (uint32_t)cb * dnew, l, delta);
         dth = dnew;
         r_ws += L;
+    };
+
+    // FIX (the caller has asked frame_inside): the two window phases' lane offsets sit in fixed registers, the loop runs two symbols per
+    // turn, loads and stores take a scalar base and a 32-bit lane offset.  Any other frame is the general loop's (the instantiation
+    // without FIX: its registers are not this loop's).
+    if constexpr (FIX) {
+        static_assert(MM == WV && bps <= 2, "the two-symbol loop: 64-sample windows, BPSK / QPSK");
+        v2f cur = gload_s<v2f>(win_base(r_ws), lane_off(r_ws & (MCRX_TILE_S - 1)));
+        const uint32_t off_even = lane_off(r_ws & (MCRX_TILE_S - 1)), off_odd = lane_off((r_ws + L) & (MCRX_TILE_S - 1));       // windows 0, 2, .. / 1, 3, ..
+        uint8_t *ssym = syms, *ssoft = soft;                            // scalar: the row of the symbol whose results wait in Zp / swp
+        auto symbol = [&](auto has_prev, const uint32_t off_next) {
+            const uint32_t sgn = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(qsg) + (pc4 + (l < 16 ? l4 : 0u)));
+            const v2f x = rot_down_pk(cur, u32rev(ph_l));
+            cur = gload_s<v2f>(win_base(r_ws + L), off_next);
+            if constexpr (decltype(has_prev)::value) {
+                if (isdata) {                                           // (bases in SGPRs: lean_prims.hpp, gstore_s)
+                    if (keep_syms) gstore_s<v2f>(ssym, so_sym, Zp);
+                    if constexpr (bps == 1) gstore_s<uint8_t>(ssoft, so_soft, (uint8_t)swp);
+                    else gstore_s<uint16_t>(ssoft, so_soft, (uint16_t)swp);
+                }
+                ssym += (size_t)Md * 8; ssoft += (size_t)Md * bps;
+            }
+            finish(x, sgn);
+        };
+        symbol(std::false_type{}, off_odd);
+        uint32_t n = 1;
+        for (; n + 2 <= nsym; n += 2) { symbol(std::true_type{}, off_even); symbol(std::true_type{}, off_odd); }
+        if (n < nsym) symbol(std::true_type{}, off_even);
+        store_symbol(psi - (uint32_t)Md, Zp, swp, false);
+        return dth;
+    } else {
+    // ---- the general loop: any L, windows at the buffer's ends
+    v2f cur = load_win(r_ws);
+    for (uint32_t n = 0; n < nsym; n++) {
+        const uint32_t sgn = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(qsg) + (pc4 + (l < 16 ? l4 : 0u)));
+        // ---- oscillator (the window's registers are free after it), the previous symbol's stores, the next window
+        const v2f x = rot_down_pk(cur, u32rev(ph_l));
+        if (n + 1 < nsym) cur = load_win(r_ws + L);
+        if (n > 0) store_symbol(psi - (uint32_t)Md, Zp, swp, true);
+        finish(x, sgn);
     }
     if (nsym > 0) store_symbol(psi - (uint32_t)Md, Zp, swp, false);
     return dth;
+    }
 }
 
 }  // namespace lean
@@ -227,10 +301,15 @@ __device__ __forceinline__ void payload_lean_body(SyncArgs &a)
         if (ch >= a.nch || job->arena_off == ~0ull) continue;
         const uint32_t mod = rfl(job->s.mod_scheme);
         if (((mod == 39 || mod == 40) ? 0 : 1) != CLS) continue;
-        uint32_t dth;
+        uint32_t dth = 0;
         if constexpr (CLS == 0) {
-            if (mod == 39) dth = lean::symbols<39, XB, MM>(a, job, ch, j, qsg, qnb, qsrc);
-            else           dth = lean::symbols<40, XB, MM>(a, job, ch, j, qsg, qnb, qsrc);
+            // the usual receiver's frame inside the buffer: the loop's invariants as constants, two symbols per turn (symbols: FIX)
+            bool fix = false;
+            if constexpr (MM == 64) fix = c.M_pilot <= 8 && c.payload_soft != 0 && a.no_syms == 0 && lean::frame_inside(a, job);
+            if constexpr (MM == 64) {
+                if (fix) dth = mod == 39 ? lean::symbols<39, XB, MM, true>(a, job, ch, j, qsg, qnb, qsrc) : lean::symbols<40, XB, MM, true>(a, job, ch, j, qsg, qnb, qsrc);
+            }
+            if (!fix) dth = mod == 39 ? lean::symbols<39, XB, MM>(a, job, ch, j, qsg, qnb, qsrc) : lean::symbols<40, XB, MM>(a, job, ch, j, qsg, qnb, qsrc);
         } else {
             wave_sync_lds();
             if (mod == 27) { if (l < 16) qnb[l] = reinterpret_cast<const uint32_t *>(c.cod.qam16_nb)[l]; }

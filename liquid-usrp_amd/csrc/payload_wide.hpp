@@ -68,7 +68,8 @@ __device__ __forceinline__ uint32_t symbols_wide(const SyncArgs &a, const Payloa
     const int64_t t_ev0 = job->s.cur + (int64_t)job->s.timer - 1;
     const int64_t ws0 = t_ev0 - L + 1 + cb;
     uint32_t dth = rfl(job->s.nco_dtheta);
-    uint32_t th_ws = rfl(job->s.nco_theta_ref + (uint32_t)(ws0 - job->s.nco_t_ref) * job->s.nco_dtheta);
+    const uint32_t th_ws0 = rfl(job->s.nco_theta_ref + (uint32_t)(ws0 - job->s.nco_t_ref) * job->s.nco_dtheta);
+    uint32_t ph_l = th_ws0 + (uint32_t)l * dth;                          // lane: the oscillator's phase at element 0's sample (lean_prims.hpp: phase_step); element e is 64 e samples on
     uint32_t pc4 = rfl(job->s.pilot_count) * 4u;                         // byte offset into the polarity table
     float phi_prime = job->s.phi_prime, p1_prime = job->s.p1_prime;
     int32_t r_ws = (int32_t)rfl((uint32_t)(ws0 - a.buf_first));
@@ -90,7 +91,7 @@ __device__ __forceinline__ uint32_t symbols_wide(const SyncArgs &a, const Payloa
     auto load_win = [&](int32_t rw, v2f (&w)[E]) {
         if (rw >= 0 && rw + (WV * E - 1) <= r_max) {
             const int ph = rw & (MCRX_TILE_S - 1);
-            if (ph != q0) { q0 = ph; const uint32_t q = (uint32_t)ph + (uint32_t)l; offl = ((q >> MCRX_TILE_SH) * tstride + (q & (uint32_t)(MCRX_TILE_S - 1))) * 8u; }
+            if (ph != q0) { q0 = ph; const uint32_t q = (uint32_t)ph + (uint32_t)l; offl = (small_times(q >> MCRX_TILE_SH, tstride) + (q & (uint32_t)(MCRX_TILE_S - 1))) * 8u; }
             const char *base = reinterpret_cast<const char *>(chb + (size_t)(uint32_t)(rw >> MCRX_TILE_SH) * tstride) + offl;
 #pragma unroll
             for (int e = 0; e < E; e++) w[e] = *reinterpret_cast<const v2f *>(base + (size_t)e * estep);
@@ -140,7 +141,7 @@ __device__ __forceinline__ uint32_t symbols_wide(const SyncArgs &a, const Payloa
         // ---- oscillator, the previous symbol's stores, the next window
         v2f x[E];
 #pragma unroll
-        for (int e = 0; e < E; e++) x[e] = rot_down_pk(cur[e], u32rev(th_ws + (uint32_t)(l + WV * e) * dth));
+        for (int e = 0; e < E; e++) x[e] = rot_down_pk(cur[e], u32rev(ph_l + (uint32_t)(WV * e) * dth));       // (64 e dth: scalar)
         if (n + 1 < nsym) load_win(r_ws + L, cur);
         if (n > 0) store_symbol(psi - (uint32_t)Md, Zp, swp, true);
         // ---- M-point DIF transform: the in-lane stages, then 64 points per element; equaliser
@@ -189,12 +190,14 @@ __device__ __forceinline__ uint32_t symbols_wide(const SyncArgs &a, const Payloa
             swp[e] = demod_pk<MOD>(reinterpret_cast<const uint8_t *>(qnb), Zp[e], soft_mode);
         }
         psi += (uint32_t)Md;
-        // ---- oscillator trim (liquid ofdmframesync: the phase at the next window start uses the old step up to this event)
+        // ---- oscillator trim (liquid ofdmframesync: the phase at the next window start uses the old step up to this event).
+        // Scalars; the lanes' phases take the window's step and their sample index times the trim (lean_prims.hpp: phase_step)
         float dphi = p0 - phi_prime;
         dphi -= TWO_PI_F * rintf(dphi * 0.15915494309189535f);
         phi_prime = p0;
-        const uint32_t dnew = dth + rfl((uint32_t)__float2int_rn(dphi * (1e-3f * 683565275.5764316f)));
-        th_ws += (uint32_t)(L - cb) * dth + (uint32_t)cb * dnew;
+        const int32_t delta = trim_sgpr(dphi);
+        const uint32_t dnew = dth + (uint32_t)delta;
+        ph_l = phase_step(ph_l, (uint32_t)(L - cb) * dth + (uint32_t)cb * dnew, l, delta);
         dth = dnew;
         r_ws += L;
     }
