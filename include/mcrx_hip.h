@@ -982,6 +982,95 @@ int      mcrx_hip_cfr_stats(mcrx_hip_cfr_t q, uint64_t over[MCRX_CFR_MAX_PASSES]
 int      mcrx_hip_cfr_design(uint32_t half_len, double cutoff, double beta, float *h);
 const char *mcrx_hip_cfr_last_error(void);
 
+/* ---- Digital predistortion on the wideband stream: learn the amplifier, invert its table ----
+ * The stage between crest-factor reduction and the amplifier: a complex gain F(|x|), looked up by amplitude and interpolated, that
+ * undoes the amplifier's compression (AM/AM) and phase shift (AM/PM) BELOW saturation -- it cannot undo saturation, so the peaks must
+ * already lie below it: mcrx_hip_cfr_* comes first.  The table is learned on the device from what went into the amplifier (u) and
+ * what came out of it (z).  cf32 in, cf32 or sc16 out; the feedback is cf32.
+ * Configuration: table_log2 in 5 .. 10, K = 2^table_log2 intervals and K + 1 entries F[0 .. K]; full_scale, the amplitude of entry
+ * K; target_gain g0, the linear gain the amplifier shall appear to have (as a rule its amp_gain); min_count >= 1; forget_shift in
+ * 0 .. 8; gain; output_format.  The host makes, in double, inv_step = fp32(K / full_scale) and step = full_scale / K (kept double);
+ * e is the least integer with 2^e >= full_scale, E = 2^e.  F = 1 + 0i in every entry until an update or a set_table.
+ * APPLY, fp32, memoryless and stateless in position:
+ *     t = fmaf(x.re, x.re, x.im * x.im);  a = sqrtf(t)                        correctly rounded
+ *     s = fminf(a * inv_step, (float)K);  k = min((int)s, K - 1);  f = s - (float)k      (exact; a NaN amplitude gives s = K)
+ *     G.re = fmaf(f, F[k+1].re - F[k].re, F[k].re)                            likewise G.im; the difference is one fp32 subtraction
+ *     y.re = fmaf(G.re, x.re, -(G.im * x.im));  y.im = fmaf(G.re, x.im, G.im * x.re)
+ *     v = gain * y            (skipped when gain == 1)
+ *     out = v (cf32) or Q(v) (sc16: the shared quantiser with the shared clip count)
+ *   Above full_scale the last entry holds.  The integers of an sc16 handle are Q of a cf32 handle's floats exactly.  Until a handle
+ *   has had an update or a set_table its launches carry no apply code (known on the host, no readback): such a handle is load,
+ *   [gain,] convert, store and keeps NaN payloads and -0.0.  In-place use (d_in == d_out, equal formats) is allowed: a lane writes
+ *   only what it read.  A stream may be cut into calls anywhere.
+ * MEASURE: two aligned cf32 streams of n samples; u is what went into the amplifier (this handle's cf32 output), z what came out of
+ *   it, aligned and scaled by the caller.  Per sample, in fp32,
+ *     tu = fmaf(u.re, u.re, u.im * u.im);  tz likewise of z;  j = (int)rintf(sqrtf(tu) * inv_step)         (ties to even)
+ *   The sample is ELIGIBLE when tu and tz are finite, rintf(...) <= K and tz <= fp32(16 E^2) (that bound is +inf where 16 E^2 is no
+ *   fp32).  An eligible sample adds to four int64 accumulators of bin j:
+ *     cnt += 1
+ *     Sre += llrint(fma(z.re, u.re, z.im * u.im) * 2^(32 - 2e))
+ *     Sim += llrint(fma(z.im, u.re, -(z.re * u.im)) * 2^(32 - 2e))
+ *     Suu += llrint(fma(u.re, u.re, u.im * u.im) * 2^(32 - 2e))
+ *   the products formed in fp64 from the fp32 components (exact), the sum of two rounded once, the scaling exact, llrint to nearest
+ *   even.  Every other sample adds 1 to `skipped`.  The sums are integers: order, cuts, grid and launch geometry cannot change a
+ *   bit.  Integer atomics only, no floating-point atomic anywhere.  A term is below 2^34.1 in magnitude; the host keeps a count of
+ *   the samples offered since the last reset (eligible or not), which follows an update as ceil(count / 2^forget_shift), and refuses
+ *   a call that would take it above 2^28 -- such a call measures nothing.
+ * UPDATE: one lane on the device in fp64, + - * / sqrt only, nothing contracted; no host synchronisation.  With r_j = j * step:
+ *   bin j is VALID when cnt >= min_count and Suu > 0; then A_j = ((double)Sre / (double)Suu, (double)Sim / (double)Suu).
+ *   An invalid bin takes the A of the nearest valid bin below it; the bins below the first valid one take the first valid one's.
+ *   No valid bin: the table stays and `degenerate` goes up.  Otherwise
+ *     |A| = sqrt(A.re * A.re + A.im * A.im);  o_0 = |A_0| r_0;  o_j = max(o_{j-1}, |A_j| r_j)       the AM/AM curve made monotone
+ *   and the entries i = 1 .. K in this order, with one pointer j that starts at 1 and only moves up:
+ *     d = g0 * r_i;  j = the least index with o_j >= d
+ *     fr = (d - o_{j-1}) / (o_j - o_{j-1}), or 0 where that denominator is not positive
+ *     r_in = r_{j-1} + fr * step;  A_in = A_{j-1} + fr * (A_j - A_{j-1})     per component
+ *     where even o_K < d:  r_in = r_K, A_in = A_K
+ *     q = r_in / r_i;  F_i = ((q * A_in.re) / |A_in|, -((q * A_in.im) / |A_in|));  F_i = (q, 0) where |A_in| is not positive
+ *   F_0 = F_1; F is stored rounded to fp32.  Last -- after a degenerate update too -- every accumulator is shifted right
+ *   arithmetically by forget_shift, and `updates` goes up.  What the amplifier does at amplitude r does not depend on the table, so
+ *   the sums stay valid across updates: a further update adds the bins that the expanded drive reaches for the first time.
+ * Calls on ONE handle must be ordered on the device (one stream, or events of the caller's): they share its table and accumulators. */
+typedef struct mcrx_hip_dpd_s *mcrx_hip_dpd_t;
+typedef struct {
+    uint32_t struct_size, table_log2;                   /* sizeof(mcrx_hip_dpd_config); 5 .. 10 */
+    float    full_scale, target_gain;                   /* the amplitude of entry K; g0 */
+    uint32_t min_count, forget_shift;                   /* >= 1; 0 .. 8 */
+    float    gain;
+    uint32_t output_format;                             /* 0 = cf32, 1 = sc16 */
+} mcrx_hip_dpd_config;
+typedef struct {
+    uint64_t updates, skipped, degenerate;              /* updates run; ineligible samples; updates that left the table as it was */
+} mcrx_hip_dpd_state;
+/* MCRX_EINVAL before a device is looked for, *out cleared: null pointers, a wrong struct_size, table_log2 outside 5 .. 10, a
+ * full_scale or target_gain that is not finite and positive, a full_scale whose inv_step is not a finite positive fp32, min_count 0,
+ * forget_shift above 8, a gain that is not finite, an output format that is not 0 or 1. */
+int      mcrx_hip_dpd_create(mcrx_hip_dpd_t *out, const mcrx_hip_dpd_config *cfg);
+int      mcrx_hip_dpd_destroy(mcrx_hip_dpd_t q);
+/* n cf32 samples at d_in -> n samples at d_out (the handle's output format), asynchronously on `stream`.  n == 0: MCRX_OK, nothing
+ * done.  MCRX_EINVAL, nothing written: a null handle or buffer, a cf32 buffer not 8-byte aligned, an sc16 output not 4-byte aligned,
+ * more than 2^32 samples, ranges that overlap other than d_in == d_out with equal formats. */
+int      mcrx_hip_dpd_execute_device(mcrx_hip_dpd_t q, const void *d_in, size_t n, void *d_out, void *stream);
+/* n aligned cf32 pairs (d_u[i], d_z[i]) into the accumulators.  MCRX_EINVAL, nothing measured, the count as before: a null handle or
+ * buffer, a buffer not 8-byte aligned, a call that would take the samples offered since the last reset above 2^28. */
+int      mcrx_hip_dpd_measure_device(mcrx_hip_dpd_t q, const void *d_u, const void *d_z, size_t n, void *stream);
+int      mcrx_hip_dpd_update(mcrx_hip_dpd_t q, void *stream);
+/* F: the K + 1 entries as 2 (K + 1) floats (re, im) in host memory, all finite (MCRX_EINVAL otherwise); read before the call returns */
+int      mcrx_hip_dpd_set_table(mcrx_hip_dpd_t q, const float *F, void *stream);
+/* waits for the handle's work on `stream`.  F: 2 (K + 1) floats; acc: 4 (K + 1) int64, bin j at acc[4 j ..]: cnt, Sre, Sim, Suu.  Any
+ * of the three pointers may be null. */
+int      mcrx_hip_dpd_read(mcrx_hip_dpd_t q, mcrx_hip_dpd_state *state, float *F, int64_t *acc, void *stream);
+/* table := 1, accumulators, counters and the host's count cleared -- without synchronising the device: the next kernel of the handle
+ * that touches them clears them.  Launches carry no apply code again.  The clip count stays. */
+int      mcrx_hip_dpd_reset(mcrx_hip_dpd_t q);
+int      mcrx_hip_dpd_clipped(mcrx_hip_dpd_t q, uint64_t *samples, int reset);      /* mctx_hip_clipped's semantics */
+unsigned mcrx_hip_dpd_output_format(mcrx_hip_dpd_t q);                               /* 0 for a null handle */
+/* host, no GPU: checks cfg as create does; *inv_step, *step and *e of it (each may be null); and for the n pairs (u[2 i], u[2 i + 1]),
+ * (z[2 i], z[2 i + 1]) bin[i] = j, or -1 where the pair is not eligible (n == 0: u, z and bin are not looked at). */
+int      mcrx_hip_dpd_selftest(const mcrx_hip_dpd_config *cfg, float *inv_step, double *step, int *e, const float *u, const float *z,
+                               size_t n, int32_t *bin);
+const char *mcrx_hip_dpd_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

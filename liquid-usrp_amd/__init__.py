@@ -230,6 +230,19 @@ _EXPORTS = {
     "mcrx_hip_cfr_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.c_int]),
     "mcrx_hip_cfr_design": (C.c_int, [C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_float)]),
     "mcrx_hip_cfr_last_error": (C.c_char_p, []),
+    "mcrx_hip_dpd_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcrx_hip_dpd_destroy": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_dpd_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_dpd_measure_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mcrx_hip_dpd_update": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mcrx_hip_dpd_set_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_dpd_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_dpd_reset": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_dpd_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
+    "mcrx_hip_dpd_output_format": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_dpd_selftest": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]),
+    "mcrx_hip_dpd_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -1308,6 +1321,141 @@ class rfcal(_StreamOp):
 
     def position(self):
         return int(lib().mcrx_hip_rfcal_position(self._h))
+
+
+DPD_MIN_LOG2, DPD_MAX_LOG2, DPD_MAX_FORGET, DPD_GUARD_LOG2 = 5, 10, 8, 28
+
+
+class DpdConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("table_log2", C.c_uint32), ("full_scale", C.c_float), ("target_gain", C.c_float),
+                ("min_count", C.c_uint32), ("forget_shift", C.c_uint32), ("gain", C.c_float), ("output_format", C.c_uint32)]
+
+
+class DpdState(C.Structure):
+    _fields_ = [("updates", C.c_uint64), ("skipped", C.c_uint64), ("degenerate", C.c_uint64)]
+
+
+def dpd_config(table_log2=7, full_scale=None, target_gain=None, min_count=8, forget_shift=0, gain=1.0, output_format="cf32"):
+    """The mcrx_hip_dpd_config of dpd's arguments.  ValueError for a malformed or missing argument and for every value the library
+    refuses (mcrx_hip_dpd_selftest judges them on the host: no device is looked for)."""
+    def whole(v, name):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < (1 << 32):
+            raise ValueError("%s must be a whole number, 0 .. 2^32 - 1" % name)
+        return int(v)
+    if full_scale is None or target_gain is None:
+        raise ValueError("full_scale and target_gain must be given")
+    c = DpdConfig()
+    c.struct_size = C.sizeof(DpdConfig)
+    c.output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
+    c.table_log2, c.min_count, c.forget_shift = whole(table_log2, "table_log2"), whole(min_count, "min_count"), whole(forget_shift, "forget_shift")
+    c.full_scale, c.target_gain, c.gain = float(full_scale), float(target_gain), float(gain)
+    _raise_rc(lib().mcrx_hip_dpd_selftest(C.addressof(c), None, None, None, None, None, 0, None), "mcrx_hip_dpd_selftest",
+              lib().mcrx_hip_dpd_last_error)
+    return c
+
+
+def dpd_constants(cfg):
+    """(inv_step, step, e) of a DpdConfig: the library's own fp32 K / full_scale, its double full_scale / K and the exponent of the
+    least power of two that is at least full_scale (mcrx_hip_dpd_selftest; host only)."""
+    inv_step, step, e = C.c_float(), C.c_double(), C.c_int()
+    _raise_rc(lib().mcrx_hip_dpd_selftest(C.addressof(cfg), C.byref(inv_step), C.byref(step), C.byref(e), None, None, 0, None),
+              "mcrx_hip_dpd_selftest", lib().mcrx_hip_dpd_last_error)
+    return float(inv_step.value), float(step.value), int(e.value)
+
+
+def dpd_bins(cfg, u, z):
+    """The bin of every pair (u[i], z[i]) as the measuring kernel finds it, -1 where the pair is not eligible (int32 array; host only)."""
+    u, z = np.ascontiguousarray(u, np.complex64), np.ascontiguousarray(z, np.complex64)
+    if u.ndim != 1 or u.shape != z.shape:
+        raise ValueError("u and z are one-dimensional and equally long")
+    out = np.zeros(len(u), np.int32)
+    if len(u):
+        _raise_rc(lib().mcrx_hip_dpd_selftest(C.addressof(cfg), None, None, None, u.ctypes.data, z.ctypes.data, len(u), out.ctypes.data),
+                  "mcrx_hip_dpd_selftest", lib().mcrx_hip_dpd_last_error)
+    return out
+
+
+class dpd(_StreamOp):
+    """Digital predistortion on the wideband stream (mcrx_hip_dpd_*): between cfr and the amplifier.
+
+        dpd(table_log2=7, full_scale=, target_gain=, min_count=8, forget_shift=0, gain=1.0, output_format="cf32")
+
+    A complex gain looked up by amplitude in a table of 2^table_log2 intervals up to `full_scale` and interpolated; it makes the
+    amplifier behind it look like the linear gain `target_gain` below saturation.  It cannot undo saturation: put cfr in front, so
+    that the peaks lie below it.  The table is learned on the device: measure(u, z) adds what went into the amplifier (u: this
+    handle's cf32 output) and what came out (z, aligned and scaled by the caller) to integer sums per amplitude bin, update() makes
+    the table of them; set_table writes one.  Until the first of either, execute copies.  Memoryless: a stream may be cut anywhere,
+    and `out is x` is allowed on a cf32 handle.  Calls on one handle must be ordered on the device."""
+
+    _op, _what = "dpd", ("this predistorter", "predistorter")
+
+    def __init__(self, table_log2=7, full_scale=None, target_gain=None, min_count=8, forget_shift=0, gain=1.0, output_format="cf32"):
+        c = dpd_config(table_log2, full_scale, target_gain, min_count, forget_shift, gain, output_format)
+        self._create(c)
+        self.config, self.output_format, self.K = c, int(c.output_format), 1 << int(c.table_log2)
+
+    @staticmethod
+    def _current(stream):
+        import torch
+        return _stream_ptr(torch.cuda.current_stream() if stream is None else stream)
+
+    def execute(self, x, out=None, stream=None):
+        """x: n samples, a contiguous complex64 CUDA tensor.  out (optional): where they go, in the output format, with room for n;
+        `out is x` is allowed with equal formats, any other overlap is refused.  Returns the n samples written.  Asynchronous on
+        `stream` (default: torch's current stream of x's device)."""
+        n, out, view = self._io(x, out, False, self.output_format == OUTPUT_FORMATS["sc16"])
+        if n:
+            self._call("execute_device", self._h, _dptr(x), n, _dptr(out), self._stream(stream, x))
+        return view
+
+    def measure(self, u, z, stream=None):
+        """u, z: equally many samples into and out of the amplifier (contiguous complex64 CUDA tensors); returns their number.
+        ValueError, nothing measured, where it would take the samples offered since the last reset above 2^28."""
+        n = self._in(u, False)
+        if self._in(z, False) != n:
+            raise ValueError("u and z must hold equally many samples")
+        if n:
+            self._call("measure_device", self._h, _dptr(u), _dptr(z), n, self._stream(stream, u))
+        return n
+
+    def update(self, stream=None):
+        """Make the table of what has been measured (on the device, no synchronisation)."""
+        self._call("update", self._h, self._current(stream))
+
+    def set_table(self, F, stream=None):
+        """Write the table: K + 1 finite complex gains F[0 .. K]."""
+        F = np.ascontiguousarray(F, np.complex64)
+        if F.shape != (self.K + 1,):
+            raise ValueError("the table holds %d complex entries" % (self.K + 1))
+        self._call("set_table", self._h, F.ctypes.data, self._current(stream))
+
+    def read(self, stream=None):
+        """The handle's state as a dict (waits for the handle's work on `stream`): F (complex64 [K + 1]), cnt, Sre, Sim, Suu (int64
+        [K + 1] each), updates, skipped, degenerate."""
+        s, F, acc = DpdState(), np.zeros(self.K + 1, np.complex64), np.zeros((self.K + 1, 4), np.int64)
+        self._call("read", self._h, C.addressof(s), F.ctypes.data, acc.ctypes.data, self._current(stream))
+        return dict(F=F, cnt=acc[:, 0].copy(), Sre=acc[:, 1].copy(), Sim=acc[:, 2].copy(), Suu=acc[:, 3].copy(), updates=int(s.updates),
+                    skipped=int(s.skipped), degenerate=int(s.degenerate))
+
+    def reset(self):
+        """Table := 1, sums and counters cleared, execute copies again (no synchronisation)."""
+        self._call("reset", self._h)
+
+    def learn(self, x, amplifier, rounds=3, first_sample=0, stream=None):
+        """`rounds` times: execute(x) -> amplifier.execute (an rfchain with cf32 in and out) -> measure -> update.  Returns the
+        amplifier's output of the last round, which the table of the round before it shaped."""
+        if self.output_format != OUTPUT_FORMATS["cf32"]:
+            raise ValueError("learn needs a cf32 predistorter: the feedback is the handle's cf32 output")
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        z = None
+        for _ in range(int(rounds)):
+            u = self.execute(x, stream=stream)
+            z = amplifier.execute(u, first_sample, stream=stream)
+            self.measure(u, z, stream=stream)
+            self.update(stream=stream)
+        return z
 
 
 USERCHAN_MAX_RAYS, USERCHAN_MAX_DELAY, USERCHAN_MAX_CHANNELS = 4, 255, 1024      # MCRX_USERCHAN_MAX_RAYS, _MAX_DELAY, _MAX_CHANNELS
