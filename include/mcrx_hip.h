@@ -1071,6 +1071,114 @@ int      mcrx_hip_dpd_selftest(const mcrx_hip_dpd_config *cfg, float *inv_step, 
                                size_t n, int32_t *bin);
 const char *mcrx_hip_dpd_last_error(void);
 
+/* ---- Predistortion with memory: branch tables learned by least squares ----
+ * The stage between crest-factor reduction and an amplifier that is NOT memoryless: a diagonal memory polynomial.  M branches, branch m
+ * a complex gain G_m(|x|) looked up by the amplitude of the sample delay[m] samples back and multiplied with that sample; the output is
+ * the sum of the branches.  G_m is a polynomial of P coefficients in the amplitude, tabulated; the L = M P coefficients are the least
+ * squares solution that maps what came out of the amplifier (z / g0) back onto what went in (u) -- indirect learning: the
+ * post-inverse, used in front.  cf32 in, cf32 or sc16 out; the feedback is cf32.  With M = 1 apply is mcrx_hip_dpd_*'s, bit for bit.
+ * Configuration: branches M in 1 .. 4; delay[0] = 0 < delay[1] < ... <= 16, lead = delay[M - 1] (delay[m >= M] is not looked at);
+ * order P in 1 .. 5 (branch m has the powers k = 0 .. P - 1; coefficient l = m P + k); table_log2 in 5 .. 10 with
+ * M 2^table_log2 <= 2048; full_scale, target_gain g0, gain, output_format, forget_shift as mcrx_hip_dpd_config's; min_rows >= L;
+ * ridge_log2 in 10 .. 40.  K, inv_step, step, e and E = 2^e are made exactly as for mcrx_hip_dpd_*; inv_g0 = fp32(1 / g0), the
+ * quotient made in double.  M tables F_m[0 .. K] of complex fp32; F_0 = 1 + 0i and F_m = 0 (m >= 1) until an update or a set_tables.
+ * APPLY, fp32: the input is n + lead samples, the history in front; in[lead + i] is the sample of output i.  For m = 0 .. M - 1:
+ *     x = in[lead + i - delay[m]]
+ *     t = fmaf(x.re, x.re, x.im * x.im);  a = sqrtf(t)
+ *     s = fminf(a * inv_step, (float)K);  k = min((int)s, K - 1);  f = s - (float)k
+ *     G.re = fmaf(f, F_m[k+1].re - F_m[k].re, F_m[k].re)                      likewise G.im; the difference is one fp32 subtraction
+ *     p_m.re = fmaf(G.re, x.re, -(G.im * x.im));  p_m.im = fmaf(G.re, x.im, G.im * x.re)
+ *   y = p_0;  then for m = 1 .. M - 1 in this order:  y.re = y.re + p_m.re;  y.im = y.im + p_m.im        (fp32 additions)
+ *   v = gain * y  (skipped when gain == 1);  out = v (cf32) or Q(v) (sc16: the shared quantiser with the shared clip count).
+ *   Until a handle has had an update or a set_tables its launches carry no apply code: load in[lead + i], [gain,] convert, store; NaN
+ *   payloads and -0.0 are kept.  Input and output must not overlap at all (a lane reads its neighbours' samples).  A stream cut into
+ *   calls that each carry their lead gives the bits of one call.
+ * MEASURE: two aligned cf32 streams of n samples, u what went into the amplifier, z what came out of it.  The first lead samples of
+ *   a call are history only; the ROWS are i = lead .. n - 1 (n <= lead: MCRX_OK, nothing measured).  Per sample z[j], in fp32:
+ *     w = z[j] * inv_g0                          per component
+ *     zeta = ldexpf(w, -e)                       w / E
+ *     t = fmaf(zeta.re, zeta.re, zeta.im * zeta.im);  a = sqrtf(t)
+ *     phi_0 = zeta;  phi_k = phi_{k-1} * a       per component, k = 1 .. P - 1
+ *     Z_k = (llrint(phi_k.re * 2^17), llrint(phi_k.im * 2^17))          ties to even; z[j] is GOOD when t <= 1 (false for a NaN)
+ *   and per sample u[i]:  ups = ldexpf(u[i], -e) per component;  tu = fmaf(ups.re, ups.re, ups.im * ups.im);
+ *     U = (llrint(ups.re * 2^17), llrint(ups.im * 2^17));  u[i] is GOOD when tu <= 4.
+ *   Row i is ELIGIBLE when u[i] and every z[i - delay[m]] are good; any other row adds 1 to `skipped`.  Its regressors are
+ *   B_l = Z_k of z[i - delay[m]], l = m P + k; with V = (B_0 .. B_{L-1}, U) an eligible row adds, to int64 sums,
+ *     rows += 1;   S_pq += conj(V_p) * V_q  for 0 <= p <= q <= L:
+ *         S_pq.re += V_p.re * V_q.re + V_p.im * V_q.im;   S_pq.im += V_p.re * V_q.im - V_p.im * V_q.re
+ *   so A_pq = S_pq (q < L), b_p = S_pL, Suu = S_LL.re; the diagonal's imaginary part stays 0.  The sums are integers: order, cuts that
+ *   keep the same rows, grid and stream position cannot change a bit.  Integer atomics only.  A term is below 2^36.01; the host counts
+ *   the rows offered since the last reset (eligible or not), follows an update with ceil(count / 2^forget_shift), and refuses a call
+ *   that would take the count above 2^26 -- such a call measures nothing.
+ * UPDATE: on the device in fp64, + - * / sqrt only, nothing contracted, no host synchronisation.  In this order:
+ *     rows < min_rows: DEGENERATE.
+ *     A_pq, b_p, Suu = (double) of the sums (the conversion rounds);  tr = 0;  tr = tr + A_ll.re, l ascending
+ *     lambda = (tr / (double)L) * 2^-ridge_log2;  A_ll.re = A_ll.re + lambda
+ *     Cholesky A = R^H R, R upper triangular, column j = 0 .. L - 1, in it i = 0 .. j:
+ *         s = A_ij;  for p = 0 .. i - 1:  s.re = s.re - (R_pi.re * R_pj.re + R_pi.im * R_pj.im)
+ *                                         s.im = s.im - (R_pi.re * R_pj.im - R_pi.im * R_pj.re)
+ *         i < j:  R_ij = (s.re / R_ii.re, s.im / R_ii.re)
+ *         i = j:  the pivot s.re must be > 0, else DEGENERATE;  R_jj = (sqrt(s.re), 0)
+ *     forward, i = 0 .. L - 1:   s = b_i;  for p = 0 .. i - 1:  s.re = s.re - (R_pi.re * y_p.re + R_pi.im * y_p.im)
+ *                                                              s.im = s.im - (R_pi.re * y_p.im - R_pi.im * y_p.re);   y_i = s / R_ii.re
+ *     backward, i = L - 1 .. 0:  s = y_i;  for p = i + 1 .. L - 1:  s.re = s.re - (R_ip.re * c_p.re - R_ip.im * c_p.im)
+ *                                                                  s.im = s.im - (R_ip.re * c_p.im + R_ip.im * c_p.re);   c_i = s / R_ii.re
+ *     q = 0;  q = q + (c_l.re * b_l.re + c_l.im * b_l.im), l ascending;  res = Suu - q
+ *     a c_l component or res not finite: DEGENERATE.
+ *     tables, for m and j = 0 .. K:  rho = ((double)j * step) * 2^-e;  G = c_{m,P-1};  for k = P - 2 .. 0:
+ *         G.re = G.re * rho + c_{m,k}.re;  G.im = G.im * rho + c_{m,k}.im       (a multiplication, then an addition)
+ *         F_m[j] = (fp32(G.re), fp32(G.im));  an entry not finite: DEGENERATE.
+ *   A degenerate update keeps tables, c and res and adds 1 to `degenerate`.  Last, always: every sum and `rows` are shifted right
+ *   arithmetically by forget_shift and `updates` goes up.
+ * Calls on ONE handle must be ordered on the device (one stream, or events of the caller's). */
+typedef struct mcrx_hip_mpd_s *mcrx_hip_mpd_t;
+typedef struct {
+    uint32_t struct_size, branches;                     /* sizeof(mcrx_hip_mpd_config); M: 1 .. 4 */
+    uint32_t delay[4];                                  /* delay[0] = 0, strictly increasing, <= 16 */
+    uint32_t order, table_log2;                         /* P: 1 .. 5; 5 .. 10, M 2^table_log2 <= 2048 */
+    float    full_scale, target_gain;                   /* the amplitude of entry K; g0 */
+    uint32_t min_rows, ridge_log2, forget_shift;        /* >= M P; 10 .. 40; 0 .. 8 */
+    float    gain;
+    uint32_t output_format;                             /* 0 = cf32, 1 = sc16 */
+} mcrx_hip_mpd_config;
+typedef struct {
+    uint64_t updates, skipped, degenerate;              /* updates run; ineligible rows; updates that left the tables as they were */
+    int64_t  rows;                                      /* eligible rows in the sums (shifted with them) */
+    double   res;                                       /* Suu - Re(c^H b) of the last update that was not degenerate */
+} mcrx_hip_mpd_state;
+/* MCRX_EINVAL before a device is looked for, *out cleared: null pointers, a wrong struct_size, and every value outside the ranges
+ * above (full_scale, target_gain, gain as mcrx_hip_dpd_create judges them; 1 / target_gain must be a finite positive fp32). */
+int      mcrx_hip_mpd_create(mcrx_hip_mpd_t *out, const mcrx_hip_mpd_config *cfg);
+int      mcrx_hip_mpd_destroy(mcrx_hip_mpd_t q);
+unsigned mcrx_hip_mpd_lead(mcrx_hip_mpd_t q);                                        /* 0 for a null handle */
+unsigned mcrx_hip_mpd_output_format(mcrx_hip_mpd_t q);                               /* 0 for a null handle */
+/* n + lead cf32 samples at d_in -> n samples at d_out (the handle's output format), asynchronously on `stream`.  n == 0: MCRX_OK,
+ * nothing done.  MCRX_EINVAL, nothing written: a null handle or buffer, a cf32 buffer not 8-byte aligned, an sc16 output not 4-byte
+ * aligned, n + lead above 2^32, ranges that overlap in any way. */
+int      mcrx_hip_mpd_execute_device(mcrx_hip_mpd_t q, const void *d_in, size_t n, void *d_out, void *stream);
+/* n aligned cf32 pairs (d_u[i], d_z[i]); rows lead .. n - 1 into the sums.  MCRX_EINVAL, nothing measured, the count as before: a
+ * null handle or buffer, a buffer not 8-byte aligned, more than 2^32 samples, a call that would take the rows offered since the last
+ * reset above 2^26. */
+int      mcrx_hip_mpd_measure_device(mcrx_hip_mpd_t q, const void *d_u, const void *d_z, size_t n, void *stream);
+int      mcrx_hip_mpd_update(mcrx_hip_mpd_t q, void *stream);
+/* F: the M tables one after the other, M (K + 1) entries as (re, im) floats in host memory, all finite (MCRX_EINVAL otherwise); read
+ * before the call returns */
+int      mcrx_hip_mpd_set_tables(mcrx_hip_mpd_t q, const float *F, void *stream);
+/* waits for the handle's work on `stream`.  F: 2 M (K + 1) floats; c: 2 L doubles (re, im; (1, 0), (0, 0) ... before the first
+ * update); sums: 2 (L + 1)(L + 2) / 2 int64, S_pq as (re, im) at entry p (L + 1) - p (p - 1) / 2 + (q - p), that is row by row of
+ * the upper triangle.  Any of the four pointers may be null. */
+int      mcrx_hip_mpd_read(mcrx_hip_mpd_t q, mcrx_hip_mpd_state *state, float *F, double *c, int64_t *sums, void *stream);
+/* tables, c, res, sums, counters and the host's count as after create -- without synchronising the device: the next kernel of the
+ * handle that touches them clears them.  Launches carry no apply code again.  The clip count stays. */
+int      mcrx_hip_mpd_reset(mcrx_hip_mpd_t q);
+int      mcrx_hip_mpd_clipped(mcrx_hip_mpd_t q, uint64_t *samples, int reset);      /* mctx_hip_clipped's semantics */
+/* host, no GPU: checks cfg as create does; *inv_step, *step, *e and *inv_g0 of it (each may be null); and for the n sample pairs
+ * (u[2 i], u[2 i + 1]), (z[2 i], z[2 i + 1]): Z[(i P + k) 2 ..] = Z_k of z[i] (zeros where z[i] is not good), U[2 i ..] = U of u[i]
+ * (likewise), good[i] = 1 (z[i] good) + 2 (u[i] good).  n == 0: u, z, Z, U and good are not looked at. */
+int      mcrx_hip_mpd_selftest(const mcrx_hip_mpd_config *cfg, float *inv_step, double *step, int *e, float *inv_g0, const float *u,
+                               const float *z, size_t n, int32_t *Z, int32_t *U, int32_t *good);
+const char *mcrx_hip_mpd_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

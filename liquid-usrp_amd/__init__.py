@@ -243,6 +243,20 @@ _EXPORTS = {
     "mcrx_hip_dpd_selftest": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.c_void_p]),
     "mcrx_hip_dpd_last_error": (C.c_char_p, []),
+    "mcrx_hip_mpd_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcrx_hip_mpd_destroy": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_mpd_lead": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_mpd_output_format": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_mpd_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_mpd_measure_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mcrx_hip_mpd_update": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mcrx_hip_mpd_set_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_mpd_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_mpd_reset": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_mpd_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
+    "mcrx_hip_mpd_selftest": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_mpd_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -1452,6 +1466,178 @@ class dpd(_StreamOp):
         z = None
         for _ in range(int(rounds)):
             u = self.execute(x, stream=stream)
+            z = amplifier.execute(u, first_sample, stream=stream)
+            self.measure(u, z, stream=stream)
+            self.update(stream=stream)
+        return z
+
+
+MPD_MAX_BRANCHES, MPD_MAX_DELAY, MPD_MAX_ORDER, MPD_QB, MPD_GUARD_LOG2, MPD_MAX_WGS = 4, 16, 5, 17, 26, 1024
+
+
+class MpdConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("branches", C.c_uint32), ("delay", C.c_uint32 * MPD_MAX_BRANCHES), ("order", C.c_uint32),
+                ("table_log2", C.c_uint32), ("full_scale", C.c_float), ("target_gain", C.c_float), ("min_rows", C.c_uint32),
+                ("ridge_log2", C.c_uint32), ("forget_shift", C.c_uint32), ("gain", C.c_float), ("output_format", C.c_uint32)]
+
+
+class MpdState(C.Structure):
+    _fields_ = [("updates", C.c_uint64), ("skipped", C.c_uint64), ("degenerate", C.c_uint64), ("rows", C.c_int64), ("res", C.c_double)]
+
+
+def mpd_config(branches=None, delays=None, order=5, table_log2=7, full_scale=None, target_gain=None, min_rows=None, ridge_log2=30,
+               forget_shift=0, gain=1.0, output_format="cf32"):
+    """The mcrx_hip_mpd_config of mpd's arguments (min_rows: default 64 rows a coefficient).  ValueError for a malformed or missing
+    argument and for every value the library refuses (mcrx_hip_mpd_selftest judges them on the host: no device is looked for)."""
+    def whole(v, name):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < (1 << 32):
+            raise ValueError("%s must be a whole number, 0 .. 2^32 - 1" % name)
+        return int(v)
+    if branches is None or delays is None or full_scale is None or target_gain is None:
+        raise ValueError("branches, delays, full_scale and target_gain must be given")
+    c = MpdConfig()
+    c.struct_size = C.sizeof(MpdConfig)
+    c.output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
+    c.branches, c.order, c.table_log2 = whole(branches, "branches"), whole(order, "order"), whole(table_log2, "table_log2")
+    delays = [whole(d, "a delay") for d in delays]
+    if len(delays) != c.branches or not 1 <= len(delays) <= MPD_MAX_BRANCHES:
+        raise ValueError("delays: one for each of the 1 .. %d branches" % MPD_MAX_BRANCHES)
+    for m, d in enumerate(delays):
+        c.delay[m] = d
+    c.min_rows = whole(64 * c.branches * c.order if min_rows is None else min_rows, "min_rows")
+    c.ridge_log2, c.forget_shift = whole(ridge_log2, "ridge_log2"), whole(forget_shift, "forget_shift")
+    c.full_scale, c.target_gain, c.gain = float(full_scale), float(target_gain), float(gain)
+    _raise_rc(lib().mcrx_hip_mpd_selftest(C.addressof(c), None, None, None, None, None, None, 0, None, None, None), "mcrx_hip_mpd_selftest",
+              lib().mcrx_hip_mpd_last_error)
+    return c
+
+
+def mpd_constants(cfg):
+    """(inv_step, step, e, inv_g0) of an MpdConfig as the library makes them (mcrx_hip_mpd_selftest; host only)."""
+    inv_step, step, e, inv_g0 = C.c_float(), C.c_double(), C.c_int(), C.c_float()
+    _raise_rc(lib().mcrx_hip_mpd_selftest(C.addressof(cfg), C.byref(inv_step), C.byref(step), C.byref(e), C.byref(inv_g0), None, None, 0, None,
+                                          None, None), "mcrx_hip_mpd_selftest", lib().mcrx_hip_mpd_last_error)
+    return float(inv_step.value), float(step.value), int(e.value), float(inv_g0.value)
+
+
+def mpd_integers(cfg, u, z):
+    """(Z, U, good) as the measuring kernel makes them of the samples u[i] and z[i]: Z int32 [n, P, 2], the regressors of z[i]; U int32
+    [n, 2]; good int32 [n] = 1 (z[i] good) + 2 (u[i] good).  Host only."""
+    u, z = np.ascontiguousarray(u, np.complex64), np.ascontiguousarray(z, np.complex64)
+    if u.ndim != 1 or u.shape != z.shape:
+        raise ValueError("u and z are one-dimensional and equally long")
+    n, P = len(u), int(cfg.order)
+    Z, U, good = np.zeros((n, P, 2), np.int32), np.zeros((n, 2), np.int32), np.zeros(n, np.int32)
+    if n:
+        _raise_rc(lib().mcrx_hip_mpd_selftest(C.addressof(cfg), None, None, None, None, u.ctypes.data, z.ctypes.data, n, Z.ctypes.data,
+                                              U.ctypes.data, good.ctypes.data), "mcrx_hip_mpd_selftest", lib().mcrx_hip_mpd_last_error)
+    return Z, U, good
+
+
+class mpd(_StreamOp):
+    """Predistortion with memory on the wideband stream (mcrx_hip_mpd_*): between cfr and an amplifier that is not memoryless.
+
+        mpd(branches, delays, order=5, table_log2=7, full_scale=, target_gain=, min_rows=None, ridge_log2=30, forget_shift=0, gain=1.0,
+            output_format="cf32")
+
+    A diagonal memory polynomial: branch m is a complex gain looked up by the amplitude of the sample delays[m] back (a table of
+    2^table_log2 intervals up to `full_scale`) times that sample; the output is the sum of the branches.  The branch gains are
+    polynomials of `order` coefficients in the amplitude, learned on the device: measure(u, z) adds what went into the amplifier (u:
+    this handle's cf32 output) and what came out (z, aligned by the caller) to exact integer sums, update() solves the least squares
+    problem in fp64 and tabulates; set_tables writes tables.  Until the first of either, execute copies.  execute takes lead =
+    delays[-1] samples of history in front of the n it returns (pad=True: zeros).  Calls on one handle must be ordered on the device."""
+
+    _op, _what = "mpd", ("this predistorter", "predistorter")
+
+    def __init__(self, branches=None, delays=None, order=5, table_log2=7, full_scale=None, target_gain=None, min_rows=None, ridge_log2=30,
+                 forget_shift=0, gain=1.0, output_format="cf32"):
+        c = mpd_config(branches, delays, order, table_log2, full_scale, target_gain, min_rows, ridge_log2, forget_shift, gain, output_format)
+        self._create(c)
+        self.config, self.output_format, self.K = c, int(c.output_format), 1 << int(c.table_log2)
+        self.M, self.P = int(c.branches), int(c.order)
+        self.L = self.M * self.P
+        self.lead = int(lib().mcrx_hip_mpd_lead(self._h))
+
+    @staticmethod
+    def _current(stream):
+        import torch
+        return _stream_ptr(torch.cuda.current_stream() if stream is None else stream)
+
+    def execute(self, x, out=None, pad=False, stream=None):
+        """x: a contiguous complex64 CUDA tensor of lead + n samples, the history in front -- or, with pad=True, n samples, which get
+        `lead` zeros in front.  out (optional): where the n samples go, in the output format; it must not overlap x.  Returns the n
+        samples written.  Asynchronous on `stream` (default: torch's current stream of x's device)."""
+        import torch
+        self._in(x, False)
+        if pad and self.lead:
+            padded = torch.zeros(int(x.numel()) + self.lead, dtype=torch.complex64, device=x.device)
+            padded[self.lead:].copy_(x.view(-1))
+            x = padded
+        n = int(x.numel()) - self.lead
+        if n < 0:
+            raise ValueError("x must hold the history in front: at least %d samples" % self.lead)
+        out, view = self._out(n, out, self.output_format == OUTPUT_FORMATS["sc16"], x.device)
+        if n:
+            self._call("execute_device", self._h, _dptr(x), n, _dptr(out), self._stream(stream, x))
+        return view
+
+    def measure(self, u, z, stream=None):
+        """u, z: equally many samples into and out of the amplifier (contiguous complex64 CUDA tensors); the first `lead` are history
+        only.  Returns the number of rows offered.  ValueError, nothing measured, where that would take the rows offered since the
+        last reset above 2^26."""
+        n = self._in(u, False)
+        if self._in(z, False) != n:
+            raise ValueError("u and z must hold equally many samples")
+        if n:
+            self._call("measure_device", self._h, _dptr(u), _dptr(z), n, self._stream(stream, u))
+        return max(n - self.lead, 0)
+
+    def update(self, stream=None):
+        """Solve for the coefficients of what has been measured and tabulate them (on the device, no synchronisation)."""
+        self._call("update", self._h, self._current(stream))
+
+    def set_tables(self, F, stream=None):
+        """Write the tables: finite complex gains F[m, 0 .. K]."""
+        F = np.ascontiguousarray(F, np.complex64)
+        if F.shape != (self.M, self.K + 1):
+            raise ValueError("the tables hold %d x %d complex entries" % (self.M, self.K + 1))
+        self._call("set_tables", self._h, F.ctypes.data, self._current(stream))
+
+    def read(self, stream=None):
+        """The handle's state as a dict (waits for the handle's work on `stream`): F (complex64 [M, K + 1]), c (complex128 [M, P]), res,
+        rows, updates, skipped, degenerate, and the raw sums: sums (int64 [(L + 1)(L + 2) / 2, 2], the upper triangle row by row) and,
+        made of them, A (L x L Python-int complex pairs as int64 [L, L, 2], upper triangle), b (int64 [L, 2]), Suu (int)."""
+        L = self.L
+        ne = (L + 1) * (L + 2) // 2
+        s, F, c, sums = MpdState(), np.zeros((self.M, self.K + 1), np.complex64), np.zeros((self.M, self.P), np.complex128), np.zeros((ne, 2), np.int64)
+        self._call("read", self._h, C.addressof(s), F.ctypes.data, c.ctypes.data, sums.ctypes.data, self._current(stream))
+        A, b, ent = np.zeros((L, L, 2), np.int64), np.zeros((L, 2), np.int64), 0
+        for p in range(L + 1):
+            for q in range(p, L + 1):
+                if q < L:
+                    A[p, q] = sums[ent]
+                elif p < L:
+                    b[p] = sums[ent]
+                ent += 1
+        return dict(F=F, c=c, res=float(s.res), rows=int(s.rows), updates=int(s.updates), skipped=int(s.skipped), degenerate=int(s.degenerate),
+                    sums=sums, A=A, b=b, Suu=int(sums[ne - 1, 0]))
+
+    def reset(self):
+        """Tables, coefficients, sums and counters as after construction; execute copies again (no synchronisation)."""
+        self._call("reset", self._h)
+
+    def learn(self, x, amplifier, rounds=3, first_sample=0, stream=None):
+        """`rounds` times: execute(x, pad=True) -> amplifier.execute(u, first_sample, stream=) -> measure -> update; `amplifier` is any
+        object with such an execute that returns as many cf32 samples as it gets.  Returns the amplifier's output of the last round,
+        which the tables of the round before it shaped."""
+        if self.output_format != OUTPUT_FORMATS["cf32"]:
+            raise ValueError("learn needs a cf32 predistorter: the feedback is the handle's cf32 output")
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        z = None
+        for _ in range(int(rounds)):
+            u = self.execute(x, pad=True, stream=stream)
             z = amplifier.execute(u, first_sample, stream=stream)
             self.measure(u, z, stream=stream)
             self.update(stream=stream)
