@@ -287,7 +287,29 @@ int    msresamp_hip_reset(msresamp_hip_t q);
  * half-band stages in front of or behind the arbitrary one: one per halving of the rate below 1/2, per doubling above 2).
  * A running stream needs no such call: the phase arithmetic is periodic and never overflows, however long the stream. */
 int    msresamp_hip_reset_at(msresamp_hip_t q, uint64_t input_position);
+/* The delay of the chain IN INPUT SAMPLES OF THE HANDLE: a slow tone leaves as if the resampler had read input sample n - delay where
+ * an ideal one reads sample n.  rate <= 1: d = 7 for the arbitrary stage, d = 2 d + 13 per half-band decimator in front of it.
+ * rate > 1: 7 + (7 / rate_arb) * sum_{i < num_stages} 2^-i (the arbitrary stage's 7 input samples; half-band interpolator i adds 7
+ * samples at rate_arb * 2^i times the input rate).  In output samples it is rate times as much.  0 for a null handle. */
 float  msresamp_hip_get_delay(msresamp_hip_t q);
+/* The plan of a rate, host only (no device is looked for): what msresamp_hip_create(rate, As) derives from the rate and uploads.
+ * interp: rate > 1.  num_stages: the half-band stages.  rate_arb: the arbitrary stage's rate, in [1/2, 1] or (1, 2].
+ * step = rint(2^24 / rate_arb): its input samples per output, 24 fractional bits.  per_in, per_out: one period of the phase,
+ * per_in * 2^24 == per_out * step.  delay: msresamp_hip_get_delay.  h1: the half-band branch filter.  hpfb[b]: branch b of the
+ * arbitrary stage, the tap on the OLDEST of its 14 samples first.  Set struct_size = sizeof(msresamp_hip_plan).
+ * MCRX_EINVAL, with msresamp_hip_last_error set, for a null pointer, a wrong struct_size and every rate msresamp_hip_create refuses:
+ * not positive, NaN, above 1024, or below 2^-38 -- more than 37 half-band stages, where the 64-bit sample counters of the first stage
+ * no longer hold a period of the phase and a call (csrc/resamp_plan.hpp). */
+typedef struct msresamp_hip_plan {
+    uint32_t struct_size;
+    uint32_t interp, num_stages, reserved;
+    uint64_t step, per_in, per_out;
+    double   rate_arb;
+    float    delay;
+    float    h1[14];
+    float    hpfb[256][14];
+} msresamp_hip_plan;
+int    msresamp_hip_selftest(float rate, float As, msresamp_hip_plan *plan);
 size_t msresamp_hip_max_output(msresamp_hip_t q, size_t nin);
 int    msresamp_hip_execute_device(msresamp_hip_t q, const void *d_in, size_t nin, void *d_out,
                                    size_t out_cap, size_t *nout, void *stream);

@@ -9,6 +9,7 @@ There is no CPU implementation here: if the HIP library or a GPU is missing, con
 raises.  (The CPU oracle under ``oracle/`` is test infrastructure and is never imported by
 this package.)
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -108,6 +109,7 @@ _EXPORTS = {
     "msresamp_hip_reset": (C.c_int, [C.c_void_p]),
     "msresamp_hip_reset_at": (C.c_int, [C.c_void_p, C.c_uint64]),
     "msresamp_hip_get_delay": (C.c_float, [C.c_void_p]),
+    "msresamp_hip_selftest": (C.c_int, [C.c_float, C.c_float, C.c_void_p]),
     "msresamp_hip_max_output": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "msresamp_hip_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                               C.POINTER(C.c_size_t), C.c_void_p]),
@@ -659,6 +661,26 @@ class multichannelrx(object):
             pass
 
 
+class _MsresampPlanStruct(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("interp", C.c_uint32), ("num_stages", C.c_uint32), ("reserved", C.c_uint32),
+                ("step", C.c_uint64), ("per_in", C.c_uint64), ("per_out", C.c_uint64), ("rate_arb", C.c_double),
+                ("delay", C.c_float), ("h1", C.c_float * 14), ("hpfb", (C.c_float * 14) * 256)]
+
+
+MsresampPlan = collections.namedtuple("MsresampPlan", "interp num_stages rate_arb step per_in per_out delay h1 hpfb")
+
+
+def msresamp_plan(rate, As=60.0):
+    """What a resampler of this rate derives from it and uploads (msresamp_hip_selftest; host only, no device is looked for):
+    interp, num_stages, rate_arb, step, per_in, per_out as Python numbers, delay (get_delay(): in input samples), h1 as float32 [14]
+    and the branch table hpfb as float32 [256, 14], the tap on the oldest sample first.  ValueError for a rate create refuses."""
+    st = _MsresampPlanStruct()
+    st.struct_size = C.sizeof(st)
+    _raise_rc(lib().msresamp_hip_selftest(float(rate), float(As), C.addressof(st)), "msresamp_hip_selftest", lib().msresamp_hip_last_error)
+    return MsresampPlan(bool(st.interp), int(st.num_stages), float(st.rate_arb), int(st.step), int(st.per_in), int(st.per_out),
+                        float(st.delay), np.array(st.h1, np.float32), np.array(st.hpfb, np.float32).reshape(256, 14))
+
+
 class msresamp(object):
     """GPU mirror of liquid's msresamp_crcf as the reference front ends use it
     (src/flexframe_rx.cc:179,240): msresamp(rate, As); execute(x) -> y, with x / y torch
@@ -725,6 +747,7 @@ class msresamp(object):
         return int(n.value)
 
     def get_delay(self):
+        """The delay of the chain in input samples of the resampler (msresamp_plan(rate).delay)."""
         return float(lib().msresamp_hip_get_delay(self._h))
 
     def reset(self, at=0):

@@ -22,6 +22,7 @@
 #include "../../include/mcrx_hip.h"
 #include "design.hpp"
 #include "devscope.hpp"
+#include "resamp_plan.hpp"
 #include "sc16.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -40,6 +41,7 @@ using namespace mcrx;
 
 #define RS_OB 1024                  // outputs per workgroup (256 threads x 4)
 #define RS_HROW 16                  // floats per row of the padded branch table (14 taps + 2): one row = 4 x 16-B loads
+static_assert(RS_M == RSP_M && RS_TAPS == RSP_TAPS && RS_NPFB == RSP_NPFB && RS_PHASE_BITS == RSP_PHASE_BITS, "resamp_plan.hpp plans for these kernels");
 
 // Input formats of the caller's buffer (template parameter FMT of the kernels that can be a first stage; msresamp_hip_set_input_format):
 // IQ_CF32 / IQ_SC16, an sc16 sample as sc16.hpp defines it.  The word stays packed from the load to the store
@@ -159,7 +161,8 @@ __global__ __launch_bounds__(256) void halfband_interp_kernel(RsIn in, float2 *o
 // the strides rational rates produce -- r = 0.8: branches 0, 64, 128, 192 -- do not pile onto one bank) a lane's 14 taps are 14
 // four-byte LDS reads at lane-dependent addresses, conflict-free or nearly, and equal addresses broadcast.  A workgroup stages
 // the table once and works through RS_CHUNKS chunks of 1024 outputs.
-// FIXED (round 6): rates whose 24-bit step has no low 16 bits -- 1/2, 1, 2, 0.8, 1.25, 0.64 ...: every rate k / 2^8 samples per output --
+// FIXED (round 6): rates whose 24-bit step has no low 16 bits -- 1/2, 1, 2, 0.8, 1.25 ...: every rate k / 2^8 samples per output (the float
+// nearest 0.64 is not one: its step is 26214401) --
 // walk the branches with a period that divides 256, so a thread's outputs (1024 n + tid + 256 r) all use ONE branch: its 14 taps sit in
 // registers for the whole workgroup and the table is not staged at all.
 // Both builds request the next chunk's input span (global loads into registers) before they work on the current one.
@@ -376,6 +379,7 @@ struct msresamp_hip_s {
     bool interp = false;
     unsigned num_stages = 0;
     double rate_arb = 1;
+    float delay = 0;            // msresamp_hip_get_delay
     unsigned long long step = 0;
     float *d_h1 = nullptr, *d_hpfb = nullptr;
     std::vector<StageBuf> in;       // decimating: in[0] = resampler input, in[s] = input of half-band s / arbitrary stage;
@@ -456,33 +460,36 @@ static void rs_rebase(msresamp_hip_s *q)
 // in[0] only ever holds the retained tail of the caller's input: the stages read the new samples where they lie
 static inline RsIn stage_in(const StageBuf &b) { return RsIn{ nullptr, 0, b.d, b.base, b.end }; }
 
+// The plan of a rate, without a device: the integers, the taps and the table a handle of that rate uploads (resamp_plan.hpp)
+extern "C" int msresamp_hip_selftest(float rate, float As, msresamp_hip_plan *plan)
+{
+    if (!plan) { g_rs_err = "null pointer"; return MCRX_EINVAL; }
+    if (plan->struct_size != sizeof(msresamp_hip_plan)) { g_rs_err = "msresamp_hip_plan: wrong struct_size"; return MCRX_EINVAL; }
+    if (const char *bad = resamp_rate_check(rate)) { g_rs_err = bad; return MCRX_EINVAL; }
+    const ResampPlan p = resamp_plan(rate, As);
+    plan->interp = p.interp ? 1u : 0u; plan->num_stages = p.num_stages; plan->reserved = 0;
+    plan->step = p.step; plan->per_in = (uint64_t)p.per_in; plan->per_out = (uint64_t)p.per_out;
+    plan->rate_arb = p.rate_arb; plan->delay = p.delay;
+    std::memcpy(plan->h1, p.h1.data(), sizeof(plan->h1));
+    std::memcpy(plan->hpfb, p.hpfb.data(), sizeof(plan->hpfb));
+    return MCRX_OK;
+}
+
 extern "C" int msresamp_hip_create(msresamp_hip_t *out, float rate, float As)
 {
-    if (!out || !(rate > 0.0f) || rate > 1024.0f) { g_rs_err = "msresamp: rate must be in (0, 1024]"; return MCRX_EINVAL; }
+    if (!out) { g_rs_err = "null pointer"; return MCRX_EINVAL; }
+    if (const char *bad = resamp_rate_check(rate)) { g_rs_err = bad; return MCRX_EINVAL; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { g_rs_err = "no HIP device (no CPU fallback)"; return MCRX_EHIP; }
+    const ResampPlan p = resamp_plan(rate, As);
     msresamp_hip_t q = new msresamp_hip_s();
     q->device = current_device();
-    q->rate = rate; q->As = As; q->rate_arb = rate;
-    q->interp = rate > 1.0f;
-    if (q->interp) while (q->rate_arb > 2.0) { q->num_stages++; q->rate_arb *= 0.5; }
-    else           while (q->rate_arb < 0.5) { q->num_stages++; q->rate_arb *= 2.0; }
-    // half-band branch filter: odd taps of a 29-tap Kaiser design with fc = 0.25, reversed
-    std::vector<float> h = firdes_kaiser(4 * RS_M + 1, 0.25f, As), h1(RS_TAPS);
-    unsigned j = 0;
-    for (unsigned i = 1; i < 4 * RS_M + 1; i += 2) h1[j++] = h[4 * RS_M + 1 - i - 1];
-    // arbitrary resampler bank, unity DC gain per branch
-    float fc = 0.515f * (float)q->rate_arb; if (fc > 0.49f) fc = 0.49f;
-    const unsigned n = 2 * RS_M * RS_NPFB + 1;
-    std::vector<float> hf = firdes_kaiser(n, fc / (float)RS_NPFB, As), hp((size_t)RS_NPFB * RS_HROW, 0.0f);
-    double gain = 0; for (float v : hf) gain += v;
-    gain = (double)RS_NPFB / gain;
-    for (unsigned b = 0; b < RS_NPFB; b++)
-        for (unsigned k = 0; k < RS_TAPS; k++)
-            hp[(size_t)b * RS_HROW + (RS_TAPS - 1 - k)] = (float)((double)hf[b + k * RS_NPFB] * gain);
-    q->step = (unsigned long long)std::llrint((double)(1u << RS_PHASE_BITS) / q->rate_arb);
-    const long long g = (long long)std::min<unsigned long long>(q->step & (~q->step + 1), 1ull << RS_PHASE_BITS);     // gcd(step, 2^24): step's lowest set bit
-    q->per_in = (long long)q->step / g; q->per_out = (1ll << RS_PHASE_BITS) / g;
+    q->rate = rate; q->As = As; q->rate_arb = p.rate_arb;
+    q->interp = p.interp; q->num_stages = p.num_stages;
+    q->step = p.step; q->per_in = p.per_in; q->per_out = p.per_out; q->delay = p.delay;
+    const std::vector<float> &h1 = p.h1;
+    std::vector<float> hp((size_t)RS_NPFB * RS_HROW, 0.0f);              // the table's rows padded to 16 floats
+    for (unsigned b = 0; b < RS_NPFB; b++) std::memcpy(&hp[(size_t)b * RS_HROW], &p.hpfb[(size_t)b * RS_TAPS], RS_TAPS * sizeof(float));
     if (hipMalloc((void **)&q->d_h1, h1.size() * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&q->d_hpfb, hp.size() * sizeof(float)) != hipSuccess ||
         hipMemcpy(q->d_h1, h1.data(), h1.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
@@ -528,13 +535,8 @@ extern "C" int msresamp_hip_reset_at(msresamp_hip_t q, uint64_t input_position)
     return MCRX_OK;
 }
 
-extern "C" float msresamp_hip_get_delay(msresamp_hip_t q)
-{
-    if (!q) return 0.f;
-    float d = (float)RS_M;
-    for (unsigned i = 0; i < q->num_stages; i++) d = 2.0f * d + (float)(2 * RS_M - 1);
-    return d;
-}
+// in input samples of the handle (resamp_plan.hpp: resamp_delay)
+extern "C" float msresamp_hip_get_delay(msresamp_hip_t q) { return q ? q->delay : 0.f; }
 
 extern "C" size_t msresamp_hip_max_output(msresamp_hip_t q, size_t nin)
 { return q ? (size_t)((double)nin * q->rate * 1.0001) + (q->interp ? (4u << q->num_stages) : 4) : 0; }

@@ -213,7 +213,7 @@ typedef struct ll_msresamp_s *ll_msresamp;
 ll_msresamp ll_msresamp_create(float rate, float As);
 void  ll_msresamp_destroy(ll_msresamp q);
 void  ll_msresamp_reset(ll_msresamp q);
-float ll_msresamp_get_delay(ll_msresamp q);
+float ll_msresamp_get_delay(ll_msresamp q);    /* in input samples of the resampler */
 void  ll_msresamp_execute(ll_msresamp q, const ll_cf *x, unsigned nx, ll_cf *y, unsigned *ny);
 
 /* ---- reference flows: /root/reference/lib/multichannel{rx,tx}.cc ---------- */

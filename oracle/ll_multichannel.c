@@ -318,6 +318,7 @@ ll_msresamp ll_msresamp_create(float rate, float As)
      * as the transmit applications use it: src/flexframe_tx.cc:170 msresamp_crcf_create(2.0, 60)) */
     if (q->interp) while (q->rate_arb > 2.0) { q->num_stages++; q->rate_arb *= 0.5; }
     else           while (q->rate_arb < 0.5) { q->num_stages++; q->rate_arb *= 2.0; }
+    if (q->num_stages > 20) { free(q); return NULL; }       /* 2u << num_stages samples are buffered between the half-band stages */
     q->hb = (ll_resamp2 *)calloc(q->num_stages ? q->num_stages : 1, sizeof(ll_resamp2));
     for (unsigned i = 0; i < q->num_stages; i++) resamp2_init(&q->hb[i], 7, As);
     q->hb_buf = (ll_cf *)calloc(2u << q->num_stages, sizeof(ll_cf));
@@ -354,8 +355,16 @@ void ll_msresamp_reset(ll_msresamp q)
     memset(q->win, 0, sizeof(ll_cf) * 2 * q->m);
     q->hb_count = 0; q->phase = 0;
 }
+/* in input samples of the resampler.  Decimating: 7 for the arbitrary stage, 2 d + 13 per half-band decimator in front of it.
+ * Interpolating: the arbitrary stage's 7 input samples, then half-band interpolator i passes its input on 7 samples late at
+ * rate_arb * 2^i times the input rate. */
 float ll_msresamp_get_delay(ll_msresamp q)
 {
+    if (q->interp) {
+        double s = 0.0, w = 1.0;
+        for (unsigned i = 0; i < q->num_stages; i++) { s += w; w *= 0.5; }
+        return (float)((double)q->m + ((double)q->m / q->rate_arb) * s);
+    }
     float d = (float)q->m;                       /* arbitrary stage, in its input samples */
     for (unsigned i = 0; i < q->num_stages; i++) d = 2.0f * d + (float)(2 * q->hb[i].m - 1);
     return d;

@@ -129,6 +129,7 @@ def lib():
     sig("ll_msresamp_create", vp, f, f)
     sig("ll_msresamp_destroy", None, vp)
     sig("ll_msresamp_execute", None, vp, vp, u, vp, vp)
+    sig("ll_msresamp_get_delay", f, vp)
     sig("ll_mcrx_create", vp, u, u, u, u, vp, vp, vp)
     sig("ll_mcrx_destroy", None, vp)
     sig("ll_mcrx_reset", None, vp)
@@ -250,6 +251,10 @@ class MsResamp:
         ny = C.c_uint(0)
         lib().ll_msresamp_execute(self.q, _ptr(x), len(x), _ptr(y), C.byref(ny))
         return y[:ny.value].copy()
+
+    def get_delay(self):
+        """in input samples"""
+        return float(lib().ll_msresamp_get_delay(self.q))
 
     def __del__(self):
         try:
