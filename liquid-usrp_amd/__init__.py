@@ -860,8 +860,15 @@ def chanemu_cfo_step(spacings, M, num_channels):
     return int(round(float(spacings) / (M * 2 * num_channels) * 4294967296.0)) % (1 << 32)
 
 
+def _whole(v, name):
+    """v as the uint32 field `name` of a configuration"""
+    if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < (1 << 32):
+        raise ValueError("%s must be a whole number, 0 .. 2^32 - 1" % name)
+    return int(v)
+
+
 class _StreamOp(object):
-    """What the classes of the stream operators share (chanemu, rfchain, cfr, rfcal): the handle of mcrx_hip_<_op>_create, errors through
+    """What the classes of the stream operators share (chanemu, rfchain, cfr, rfcal, dpd, mpd): the handle of mcrx_hip_<_op>_create, errors through
     mcrx_hip_<_op>_last_error, the clip count, close, and what execute checks of x and out.  _what: who takes the samples, and the noun
     of "this ..." in the messages."""
     _op, _what, _h = None, None, None
@@ -918,6 +925,12 @@ class _StreamOp(object):
         """the stream to pass: the one given, or torch's current stream of x's device"""
         import torch
         return _stream_ptr(torch.cuda.current_stream(x.device) if stream is None else stream)
+
+    @staticmethod
+    def _current(stream):
+        """the stream to pass where no tensor names a device: the one given, or torch's current stream"""
+        import torch
+        return _stream_ptr(torch.cuda.current_stream() if stream is None else stream)
 
     def clipped(self, reset=False):
         """Samples clipped by the sc16-out calls since the count was last reset (waits for the last such call only); 0 on a cf32 one."""
@@ -1251,10 +1264,6 @@ class RfcalState(C.Structure):
 def rfcal_config(dc=True, iq=True, period_log2=0, forget_log2=30, gain=1.0, input_format="cf32", output_format="cf32"):
     """The mcrx_hip_rfcal_config of rfcal's arguments.  ValueError for a malformed argument; the values themselves are judged by the
     library (mcrx_hip_rfcal_create, before it looks for a device)."""
-    def whole(v, name):
-        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < (1 << 32):
-            raise ValueError("%s must be a whole number, 0 .. 2^32 - 1" % name)
-        return int(v)
     c = RfcalConfig()
     c.struct_size = C.sizeof(RfcalConfig)
     if not isinstance(dc, (bool, np.bool_)) or not isinstance(iq, (bool, np.bool_)):
@@ -1262,7 +1271,7 @@ def rfcal_config(dc=True, iq=True, period_log2=0, forget_log2=30, gain=1.0, inpu
     c.stages = (RFCAL_DC if dc else 0) | (RFCAL_IQ if iq else 0)
     c.input_format = _format_code(input_format, INPUT_FORMATS, "input_format")
     c.output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
-    c.period_log2, c.forget_log2 = whole(period_log2, "period_log2"), whole(forget_log2, "forget_log2")
+    c.period_log2, c.forget_log2 = _whole(period_log2, "period_log2"), _whole(forget_log2, "forget_log2")
     c.gain = float(gain)
     return c
 
@@ -1323,11 +1332,6 @@ class rfcal(_StreamOp):
             self._call("execute_device", self._h, _dptr(x), n, None, self._stream(stream, x))
         return n
 
-    @staticmethod
-    def _current(stream):
-        import torch
-        return _stream_ptr(torch.cuda.current_stream() if stream is None else stream)
-
     def update(self, stream=None):
         """Make the coefficients of what has been measured (period_log2 = 0 handles only: ValueError otherwise)."""
         self._chk(lib().mcrx_hip_rfcal_update(self._h, self._current(stream)), "mcrx_hip_rfcal_update")
@@ -1360,6 +1364,53 @@ class rfcal(_StreamOp):
         return int(lib().mcrx_hip_rfcal_position(self._h))
 
 
+class _Predistorter(_StreamOp):
+    """What dpd and mpd share: a cf32-in handle with tables that measure and update learn or set_table(s) writes.  _pad: whether learn's
+    execute pads the history."""
+    _what, _pad = ("this predistorter", "predistorter"), {}
+
+    def _measure(self, u, z, stream):
+        """the samples of a measure call on u and z, offered to the library"""
+        n = self._in(u, False)
+        if self._in(z, False) != n:
+            raise ValueError("u and z must hold equally many samples")
+        if n:
+            self._call("measure_device", self._h, _dptr(u), _dptr(z), n, self._stream(stream, u))
+        return n
+
+    def _set(self, name, F, shape, what, stream):
+        """set_table / set_tables: F as complex64 of `shape`, written by the library's `name`"""
+        F = np.ascontiguousarray(F, np.complex64)
+        if F.shape != shape:
+            raise ValueError("the %s complex entries" % (what % shape))
+        self._call(name, self._h, F.ctypes.data, self._current(stream))
+
+    def update(self, stream=None):
+        """Make the table(s) of what has been measured (on the device, no synchronisation)."""
+        self._call("update", self._h, self._current(stream))
+
+    def reset(self):
+        """Tables, sums and counters as after construction; execute copies again (no synchronisation)."""
+        self._call("reset", self._h)
+
+    def learn(self, x, amplifier, rounds=3, first_sample=0, stream=None):
+        """`rounds` times: execute(x) (mpd: with pad=True) -> amplifier.execute(u, first_sample, stream=) -> measure -> update;
+        `amplifier` is any object with such an execute that returns as many cf32 samples as it gets, an rfchain with cf32 in and out
+        for one.  Returns the amplifier's output of the last round, which the table(s) of the round before it shaped."""
+        if self.output_format != OUTPUT_FORMATS["cf32"]:
+            raise ValueError("learn needs a cf32 predistorter: the feedback is the handle's cf32 output")
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        z = None
+        for _ in range(int(rounds)):
+            u = self.execute(x, stream=stream, **self._pad)
+            z = amplifier.execute(u, first_sample, stream=stream)
+            self.measure(u, z, stream=stream)
+            self.update(stream=stream)
+        return z
+
+
 DPD_MIN_LOG2, DPD_MAX_LOG2, DPD_MAX_FORGET, DPD_GUARD_LOG2 = 5, 10, 8, 28
 
 
@@ -1375,16 +1426,12 @@ class DpdState(C.Structure):
 def dpd_config(table_log2=7, full_scale=None, target_gain=None, min_count=8, forget_shift=0, gain=1.0, output_format="cf32"):
     """The mcrx_hip_dpd_config of dpd's arguments.  ValueError for a malformed or missing argument and for every value the library
     refuses (mcrx_hip_dpd_selftest judges them on the host: no device is looked for)."""
-    def whole(v, name):
-        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < (1 << 32):
-            raise ValueError("%s must be a whole number, 0 .. 2^32 - 1" % name)
-        return int(v)
     if full_scale is None or target_gain is None:
         raise ValueError("full_scale and target_gain must be given")
     c = DpdConfig()
     c.struct_size = C.sizeof(DpdConfig)
     c.output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
-    c.table_log2, c.min_count, c.forget_shift = whole(table_log2, "table_log2"), whole(min_count, "min_count"), whole(forget_shift, "forget_shift")
+    c.table_log2, c.min_count, c.forget_shift = _whole(table_log2, "table_log2"), _whole(min_count, "min_count"), _whole(forget_shift, "forget_shift")
     c.full_scale, c.target_gain, c.gain = float(full_scale), float(target_gain), float(gain)
     _raise_rc(lib().mcrx_hip_dpd_selftest(C.addressof(c), None, None, None, None, None, 0, None), "mcrx_hip_dpd_selftest",
               lib().mcrx_hip_dpd_last_error)
@@ -1412,7 +1459,7 @@ def dpd_bins(cfg, u, z):
     return out
 
 
-class dpd(_StreamOp):
+class dpd(_Predistorter):
     """Digital predistortion on the wideband stream (mcrx_hip_dpd_*): between cfr and the amplifier.
 
         dpd(table_log2=7, full_scale=, target_gain=, min_count=8, forget_shift=0, gain=1.0, output_format="cf32")
@@ -1424,17 +1471,12 @@ class dpd(_StreamOp):
     the table of them; set_table writes one.  Until the first of either, execute copies.  Memoryless: a stream may be cut anywhere,
     and `out is x` is allowed on a cf32 handle.  Calls on one handle must be ordered on the device."""
 
-    _op, _what = "dpd", ("this predistorter", "predistorter")
+    _op = "dpd"
 
     def __init__(self, table_log2=7, full_scale=None, target_gain=None, min_count=8, forget_shift=0, gain=1.0, output_format="cf32"):
         c = dpd_config(table_log2, full_scale, target_gain, min_count, forget_shift, gain, output_format)
         self._create(c)
         self.config, self.output_format, self.K = c, int(c.output_format), 1 << int(c.table_log2)
-
-    @staticmethod
-    def _current(stream):
-        import torch
-        return _stream_ptr(torch.cuda.current_stream() if stream is None else stream)
 
     def execute(self, x, out=None, stream=None):
         """x: n samples, a contiguous complex64 CUDA tensor.  out (optional): where they go, in the output format, with room for n;
@@ -1448,23 +1490,11 @@ class dpd(_StreamOp):
     def measure(self, u, z, stream=None):
         """u, z: equally many samples into and out of the amplifier (contiguous complex64 CUDA tensors); returns their number.
         ValueError, nothing measured, where it would take the samples offered since the last reset above 2^28."""
-        n = self._in(u, False)
-        if self._in(z, False) != n:
-            raise ValueError("u and z must hold equally many samples")
-        if n:
-            self._call("measure_device", self._h, _dptr(u), _dptr(z), n, self._stream(stream, u))
-        return n
-
-    def update(self, stream=None):
-        """Make the table of what has been measured (on the device, no synchronisation)."""
-        self._call("update", self._h, self._current(stream))
+        return self._measure(u, z, stream)
 
     def set_table(self, F, stream=None):
         """Write the table: K + 1 finite complex gains F[0 .. K]."""
-        F = np.ascontiguousarray(F, np.complex64)
-        if F.shape != (self.K + 1,):
-            raise ValueError("the table holds %d complex entries" % (self.K + 1))
-        self._call("set_table", self._h, F.ctypes.data, self._current(stream))
+        self._set("set_table", F, (self.K + 1,), "table holds %d", stream)
 
     def read(self, stream=None):
         """The handle's state as a dict (waits for the handle's work on `stream`): F (complex64 [K + 1]), cnt, Sre, Sim, Suu (int64
@@ -1473,26 +1503,6 @@ class dpd(_StreamOp):
         self._call("read", self._h, C.addressof(s), F.ctypes.data, acc.ctypes.data, self._current(stream))
         return dict(F=F, cnt=acc[:, 0].copy(), Sre=acc[:, 1].copy(), Sim=acc[:, 2].copy(), Suu=acc[:, 3].copy(), updates=int(s.updates),
                     skipped=int(s.skipped), degenerate=int(s.degenerate))
-
-    def reset(self):
-        """Table := 1, sums and counters cleared, execute copies again (no synchronisation)."""
-        self._call("reset", self._h)
-
-    def learn(self, x, amplifier, rounds=3, first_sample=0, stream=None):
-        """`rounds` times: execute(x) -> amplifier.execute (an rfchain with cf32 in and out) -> measure -> update.  Returns the
-        amplifier's output of the last round, which the table of the round before it shaped."""
-        if self.output_format != OUTPUT_FORMATS["cf32"]:
-            raise ValueError("learn needs a cf32 predistorter: the feedback is the handle's cf32 output")
-        import torch
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        z = None
-        for _ in range(int(rounds)):
-            u = self.execute(x, stream=stream)
-            z = amplifier.execute(u, first_sample, stream=stream)
-            self.measure(u, z, stream=stream)
-            self.update(stream=stream)
-        return z
 
 
 MPD_MAX_BRANCHES, MPD_MAX_DELAY, MPD_MAX_ORDER, MPD_QB, MPD_GUARD_LOG2, MPD_MAX_WGS = 4, 16, 5, 17, 26, 1024
@@ -1512,23 +1522,19 @@ def mpd_config(branches=None, delays=None, order=5, table_log2=7, full_scale=Non
                forget_shift=0, gain=1.0, output_format="cf32"):
     """The mcrx_hip_mpd_config of mpd's arguments (min_rows: default 64 rows a coefficient).  ValueError for a malformed or missing
     argument and for every value the library refuses (mcrx_hip_mpd_selftest judges them on the host: no device is looked for)."""
-    def whole(v, name):
-        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < (1 << 32):
-            raise ValueError("%s must be a whole number, 0 .. 2^32 - 1" % name)
-        return int(v)
     if branches is None or delays is None or full_scale is None or target_gain is None:
         raise ValueError("branches, delays, full_scale and target_gain must be given")
     c = MpdConfig()
     c.struct_size = C.sizeof(MpdConfig)
     c.output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
-    c.branches, c.order, c.table_log2 = whole(branches, "branches"), whole(order, "order"), whole(table_log2, "table_log2")
-    delays = [whole(d, "a delay") for d in delays]
+    c.branches, c.order, c.table_log2 = _whole(branches, "branches"), _whole(order, "order"), _whole(table_log2, "table_log2")
+    delays = [_whole(d, "a delay") for d in delays]
     if len(delays) != c.branches or not 1 <= len(delays) <= MPD_MAX_BRANCHES:
         raise ValueError("delays: one for each of the 1 .. %d branches" % MPD_MAX_BRANCHES)
     for m, d in enumerate(delays):
         c.delay[m] = d
-    c.min_rows = whole(64 * c.branches * c.order if min_rows is None else min_rows, "min_rows")
-    c.ridge_log2, c.forget_shift = whole(ridge_log2, "ridge_log2"), whole(forget_shift, "forget_shift")
+    c.min_rows = _whole(64 * c.branches * c.order if min_rows is None else min_rows, "min_rows")
+    c.ridge_log2, c.forget_shift = _whole(ridge_log2, "ridge_log2"), _whole(forget_shift, "forget_shift")
     c.full_scale, c.target_gain, c.gain = float(full_scale), float(target_gain), float(gain)
     _raise_rc(lib().mcrx_hip_mpd_selftest(C.addressof(c), None, None, None, None, None, None, 0, None, None, None), "mcrx_hip_mpd_selftest",
               lib().mcrx_hip_mpd_last_error)
@@ -1557,7 +1563,7 @@ def mpd_integers(cfg, u, z):
     return Z, U, good
 
 
-class mpd(_StreamOp):
+class mpd(_Predistorter):
     """Predistortion with memory on the wideband stream (mcrx_hip_mpd_*): between cfr and an amplifier that is not memoryless.
 
         mpd(branches, delays, order=5, table_log2=7, full_scale=, target_gain=, min_rows=None, ridge_log2=30, forget_shift=0, gain=1.0,
@@ -1570,7 +1576,7 @@ class mpd(_StreamOp):
     problem in fp64 and tabulates; set_tables writes tables.  Until the first of either, execute copies.  execute takes lead =
     delays[-1] samples of history in front of the n it returns (pad=True: zeros).  Calls on one handle must be ordered on the device."""
 
-    _op, _what = "mpd", ("this predistorter", "predistorter")
+    _op, _pad = "mpd", dict(pad=True)
 
     def __init__(self, branches=None, delays=None, order=5, table_log2=7, full_scale=None, target_gain=None, min_rows=None, ridge_log2=30,
                  forget_shift=0, gain=1.0, output_format="cf32"):
@@ -1580,11 +1586,6 @@ class mpd(_StreamOp):
         self.M, self.P = int(c.branches), int(c.order)
         self.L = self.M * self.P
         self.lead = int(lib().mcrx_hip_mpd_lead(self._h))
-
-    @staticmethod
-    def _current(stream):
-        import torch
-        return _stream_ptr(torch.cuda.current_stream() if stream is None else stream)
 
     def execute(self, x, out=None, pad=False, stream=None):
         """x: a contiguous complex64 CUDA tensor of lead + n samples, the history in front -- or, with pad=True, n samples, which get
@@ -1608,23 +1609,11 @@ class mpd(_StreamOp):
         """u, z: equally many samples into and out of the amplifier (contiguous complex64 CUDA tensors); the first `lead` are history
         only.  Returns the number of rows offered.  ValueError, nothing measured, where that would take the rows offered since the
         last reset above 2^26."""
-        n = self._in(u, False)
-        if self._in(z, False) != n:
-            raise ValueError("u and z must hold equally many samples")
-        if n:
-            self._call("measure_device", self._h, _dptr(u), _dptr(z), n, self._stream(stream, u))
-        return max(n - self.lead, 0)
-
-    def update(self, stream=None):
-        """Solve for the coefficients of what has been measured and tabulate them (on the device, no synchronisation)."""
-        self._call("update", self._h, self._current(stream))
+        return max(self._measure(u, z, stream) - self.lead, 0)
 
     def set_tables(self, F, stream=None):
         """Write the tables: finite complex gains F[m, 0 .. K]."""
-        F = np.ascontiguousarray(F, np.complex64)
-        if F.shape != (self.M, self.K + 1):
-            raise ValueError("the tables hold %d x %d complex entries" % (self.M, self.K + 1))
-        self._call("set_tables", self._h, F.ctypes.data, self._current(stream))
+        self._set("set_tables", F, (self.M, self.K + 1), "tables hold %d x %d", stream)
 
     def read(self, stream=None):
         """The handle's state as a dict (waits for the handle's work on `stream`): F (complex64 [M, K + 1]), c (complex128 [M, P]), res,
@@ -1644,27 +1633,6 @@ class mpd(_StreamOp):
                 ent += 1
         return dict(F=F, c=c, res=float(s.res), rows=int(s.rows), updates=int(s.updates), skipped=int(s.skipped), degenerate=int(s.degenerate),
                     sums=sums, A=A, b=b, Suu=int(sums[ne - 1, 0]))
-
-    def reset(self):
-        """Tables, coefficients, sums and counters as after construction; execute copies again (no synchronisation)."""
-        self._call("reset", self._h)
-
-    def learn(self, x, amplifier, rounds=3, first_sample=0, stream=None):
-        """`rounds` times: execute(x, pad=True) -> amplifier.execute(u, first_sample, stream=) -> measure -> update; `amplifier` is any
-        object with such an execute that returns as many cf32 samples as it gets.  Returns the amplifier's output of the last round,
-        which the tables of the round before it shaped."""
-        if self.output_format != OUTPUT_FORMATS["cf32"]:
-            raise ValueError("learn needs a cf32 predistorter: the feedback is the handle's cf32 output")
-        import torch
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device)
-        z = None
-        for _ in range(int(rounds)):
-            u = self.execute(x, pad=True, stream=stream)
-            z = amplifier.execute(u, first_sample, stream=stream)
-            self.measure(u, z, stream=stream)
-            self.update(stream=stream)
-        return z
 
 
 USERCHAN_MAX_RAYS, USERCHAN_MAX_DELAY, USERCHAN_MAX_CHANNELS = 4, 255, 1024      # MCRX_USERCHAN_MAX_RAYS, _MAX_DELAY, _MAX_CHANNELS

@@ -6,12 +6,11 @@
 // (four int64 a bin) and the counters.  Nothing of it is read back by a launch's host side: whether there has been an update or a
 // set_table, and how many samples have been offered, the host knows itself.
 //
-// dpd_kernel<FOUT, APPLY>: streaming, rfchain_kernel's lane layout -- a lane owns an index-aligned pair, 16-byte accesses where the
-// address allows, the parity taken from d_in's address.  A workgroup of an APPLY build stages the table's quadruples in LDS once
-// (16 bytes * K), so that a sample's gather is one 16-byte LDS read, and takes K / 32 (at least 4) rounds of 256 consecutive pairs,
-// four rounds' loads in flight at a time: the staging is 1/16 of the bytes it streams.  The build without APPLY has no LDS, no table
-// and no loop (a lane a pair, rfchain_kernel's grid): load, [gain,] convert, store.
-// dpd_measure_kernel: the same lanes over (u, z); a histogram in the workgroup's LDS -- three 64-bit sums and a 32-bit count per bin,
+// execute is pdtable.hpp's pd_stream_kernel<FOUT, APPLY>, the parity taken from d_in's address: a workgroup of an APPLY build takes
+// K / 32 (at least 4) rounds of 256 consecutive pairs, four rounds' loads in flight at a time, so that staging the table is 1/16 of
+// the bytes it streams; the build without APPLY takes one (a lane a pair, rfchain_kernel's grid).  The handle's fields and the bodies
+// of create, destroy, reset and set_table are pdtable.hpp's too.
+// dpd_measure_kernel: the streaming lanes over (u, z); a histogram in the workgroup's LDS -- three 64-bit sums and a 32-bit count per bin,
 // integer LDS atomics -- flushed bin by bin, the non-zero ones only, with 64-bit integer atomics on the handle's accumulators.  The
 // ineligible samples are counted per lane, summed across the wave and added once per wave.
 // dpd_update_kernel: one workgroup; lane 0 runs the update in fp64 with its work arrays (A, o) in LDS, then all lanes write the
@@ -26,65 +25,9 @@
 #include <string>
 #include "../../include/mcrx_hip.h"
 #include "dpd_plan.hpp"
-#include "iqpair.hpp"
-#include "ophost.hpp"
-#include "stream_call.hpp"
+#include "pdtable.hpp"
 
 namespace mcrx {
-
-struct DpdArgs {
-    const void *in; void *out;
-    const float4 *quads;                                    // APPLY builds: K quadruples (F[k].re, F[k].im, dF.re, dF.im)
-    unsigned long long *clip;                               // sc16-out builds: the handle's count of clipped samples
-    uint64_t parity, n;                                     // (address of in[0] / 8) & 1; samples of this launch
-    uint32_t K, rounds; float inv_step, gain;               // rounds: of 256 pairs a workgroup takes (dpd_rounds)
-};
-
-__device__ __forceinline__ float2 dpd_sample(const float4 *tab, float2 x, float inv_step, float Kf, int Km1)
-{
-    const float t = fmaf(x.x, x.x, x.y * x.y), a = sqrtf(t);
-    const float s = fminf(a * inv_step, Kf);
-    const int k = min((int)s, Km1);
-    const float f = s - (float)k;
-    const float4 q = tab[k];
-    const float gr = fmaf(f, q.z, q.x), gi = fmaf(f, q.w, q.y);
-    return make_float2(fmaf(gr, x.x, -(gi * x.y)), fmaf(gr, x.y, gi * x.x));
-}
-
-template <int FOUT, bool APPLY>
-__global__ __launch_bounds__(DPD_WG) void dpd_kernel(DpdArgs a)
-{
-    extern __shared__ float4 dpd_tab[];
-    if (APPLY) {
-        for (uint32_t k = threadIdx.x; k < a.K; k += DPD_WG) dpd_tab[k] = a.quads[k];
-        __syncthreads();
-    }
-    const float Kf = (float)a.K;
-    const int Km1 = (int)a.K - 1;
-    uint32_t nclip = 0;
-    // A workgroup owns a.rounds * 256 consecutive pairs and takes them 256 at a time; an APPLY build has the loads of DPD_UNROLL rounds
-    // in flight before it computes on the first (a pair beyond the launch is masked on both halves: it loads and stores nothing).
-    // The copy build has one round: a lane a pair.
-    constexpr int U = APPLY ? (int)DPD_UNROLL : 1;
-    const uint64_t base = (uint64_t)blockIdx.x * a.rounds * DPD_WG + threadIdx.x;
-    for (uint32_t r = 0; r < a.rounds; r += U) {
-        IqPair p[U];
-        float2 x0[U], x1[U];                                            // (the masked half of an edge pair computes on a zero)
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            p[u] = iq_pair(a.parity, a.n, base + (uint64_t)(r + u) * DPD_WG);
-            load_pair<IQ_CF32>(a.in, p[u], x0[u], x1[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            float2 v0 = x0[u], v1 = x1[u];
-            if (APPLY) { v0 = dpd_sample(dpd_tab, v0, a.inv_step, Kf, Km1); v1 = dpd_sample(dpd_tab, v1, a.inv_step, Kf, Km1); }
-            if (a.gain != 1.0f) { v0 = make_float2(a.gain * v0.x, a.gain * v0.y); v1 = make_float2(a.gain * v1.x, a.gain * v1.y); }
-            nclip += store_pair<FOUT>(a.out, p[u], v0, v1);
-        }
-    }
-    if (FOUT == IQ_SC16) sc16_clip_commit(a.clip, nclip);               // every lane of every wave gets here
-}
 
 struct DpdMeasure {
     const void *u, *z;
@@ -145,15 +88,6 @@ struct DpdUpdate {
     double step, g0;
 };
 
-// quads[k] = (F[k], F[k+1] - F[k]): the same fp32 subtraction the definition writes
-__device__ __forceinline__ void dpd_write_quads(const float2 *F, float4 *quads, uint32_t K)
-{
-    for (uint32_t k = threadIdx.x; k < K; k += DPD_WG) {
-        const float2 f0 = F[k], f1 = F[k + 1];
-        quads[k] = make_float4(f0.x, f0.y, f1.x - f0.x, f1.y - f0.y);
-    }
-}
-
 // the update (include/mcrx_hip.h), lane 0 of one workgroup; Ar, Ai, o: K + 1 doubles each, in LDS
 __device__ void dpd_update_lane(const DpdUpdate &p, double *Ar, double *Ai, double *o)
 {
@@ -201,7 +135,7 @@ __global__ __launch_bounds__(DPD_WG) void dpd_update_kernel(DpdUpdate p)
         __threadfence();
     }
     __syncthreads();
-    dpd_write_quads(p.F, p.quads, p.K);
+    pd_write_quads(p.F, p.quads, 1u, p.K);
     if (p.forget_shift)
         for (uint32_t b = threadIdx.x; b < 4u * (p.K + 1u); b += DPD_WG) p.acc[b] >>= p.forget_shift;      // arithmetic
 }
@@ -216,7 +150,7 @@ __global__ __launch_bounds__(DPD_WG) void dpd_table_kernel(DpdState *state, floa
         __threadfence();
         __syncthreads();
     }
-    dpd_write_quads(F, quads, K);
+    pd_write_quads(F, quads, 1u, K);
 }
 
 }  // namespace mcrx
@@ -225,17 +159,16 @@ using namespace mcrx;
 
 static thread_local std::string g_dpd_err;
 
-struct mcrx_hip_dpd_s {
-    int device = -1;            // the HIP device the handle was created on: every entry point runs with it current (devscope.hpp)
+struct mcrx_hip_dpd_s : PdHandle {
     mcrx_hip_dpd_config cfg;
     DpdConsts k;
-    Sc16ClipCount clip;         // sc16-out handles only
-    char *mem = nullptr;        // device: DpdState, F, quads, acc
-    DpdState *state = nullptr; float2 *F = nullptr; float4 *quads = nullptr; long long *acc = nullptr;
-    uint64_t since = 0;         // samples offered since the last reset, following the updates' shifts (the 2^28 guard)
-    bool trained = false;       // an update or a set_table has been enqueued since the reset: launches carry the apply code
-    bool reset_pending = false; // the next kernel that touches the state clears it first
+    DpdState *state = nullptr; long long *acc = nullptr;    // in mem, with F and quads
 };
+
+static void dpd_launch_table(mcrx_hip_dpd_t q, hipStream_t st, uint32_t reset)
+{
+    hipLaunchKernelGGL(dpd_table_kernel, dim3(1), dim3(DPD_WG), 0, st, q->state, q->F, q->quads, q->acc, q->k.K, reset);
+}
 
 extern "C" const char *mcrx_hip_dpd_last_error(void) { return g_dpd_err.c_str(); }
 
@@ -262,60 +195,23 @@ extern "C" int mcrx_hip_dpd_create(mcrx_hip_dpd_t *out, const mcrx_hip_dpd_confi
     *out = nullptr;
     if (!cfg) { g_dpd_err = "null configuration"; return MCRX_EINVAL; }
     if (const char *bad = dpd_check(cfg)) { g_dpd_err = bad; return MCRX_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { g_dpd_err = "no HIP device (no CPU fallback)"; return MCRX_EHIP; }
     mcrx_hip_dpd_t q = new mcrx_hip_dpd_s();
-    q->device = current_device();
     q->cfg = *cfg;
     q->k = dpd_consts(cfg);
     const size_t K = q->k.K;
-    const size_t o_quads = sizeof(DpdState), o_acc = o_quads + K * sizeof(float4), o_F = o_acc + 4 * (K + 1) * sizeof(long long);
-    const size_t bytes = o_F + (K + 1) * sizeof(float2);
-    hipError_t e = hipMalloc((void **)&q->mem, bytes);
-    if (e == hipSuccess) {
-        q->state = reinterpret_cast<DpdState *>(q->mem);
-        q->quads = reinterpret_cast<float4 *>(q->mem + o_quads);
-        q->acc = reinterpret_cast<long long *>(q->mem + o_acc);
-        q->F = reinterpret_cast<float2 *>(q->mem + o_F);
-        e = hipMemset(q->mem, 0, bytes);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && cfg->output_format == IQ_SC16) e = q->clip.ensure();
-    if (e != hipSuccess) { g_dpd_err = std::string("device state: ") + hipGetErrorString(e); mcrx_hip_dpd_destroy(q); return MCRX_EHIP; }
-    q->reset_pending = true;                                            // the table is 1 before anything reads it
+    const int rc = pd_alloc(q, g_dpd_err, cfg->output_format == IQ_SC16, 1, K, sizeof(DpdState), 4 * (K + 1) * sizeof(long long));
+    if (rc != MCRX_OK) { delete q; return rc; }
+    q->state = reinterpret_cast<DpdState *>(q->mem);
+    q->acc = reinterpret_cast<long long *>(q->quads + K);
     *out = q;
     return MCRX_OK;
 }
 
-extern "C" int mcrx_hip_dpd_destroy(mcrx_hip_dpd_t q)
-{
-    DevScope dev_scope_(q ? q->device : -1);
-    if (!q) return MCRX_OK;
-    (void)hipDeviceSynchronize();
-    if (q->mem) (void)hipFree(q->mem);
-    q->clip.release();
-    delete q;
-    return MCRX_OK;
-}
+extern "C" int mcrx_hip_dpd_destroy(mcrx_hip_dpd_t q) { return pd_destroy(q); }
 
 extern "C" unsigned mcrx_hip_dpd_output_format(mcrx_hip_dpd_t q) { return q ? q->cfg.output_format : 0u; }
 
-extern "C" int mcrx_hip_dpd_reset(mcrx_hip_dpd_t q)
-{
-    if (!q) { g_dpd_err = "null handle"; return MCRX_EINVAL; }
-    q->since = 0; q->trained = false; q->reset_pending = true;
-    return MCRX_OK;
-}
-
-// the state cleared if a reset is pending: in front of every kernel that reads or writes table, accumulators or counters
-static hipError_t dpd_serve_reset(mcrx_hip_dpd_t q, hipStream_t st)
-{
-    if (!q->reset_pending) return hipSuccess;
-    hipLaunchKernelGGL(dpd_table_kernel, dim3(1), dim3(DPD_WG), 0, st, q->state, q->F, q->quads, q->acc, q->k.K, 1u);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) q->reset_pending = false;
-    return e;
-}
+extern "C" int mcrx_hip_dpd_reset(mcrx_hip_dpd_t q) { return pd_reset(q, g_dpd_err); }
 
 extern "C" int mcrx_hip_dpd_execute_device(mcrx_hip_dpd_t q, const void *d_in, size_t n, void *d_out, void *stream)
 {
@@ -327,19 +223,8 @@ extern "C" int mcrx_hip_dpd_execute_device(mcrx_hip_dpd_t q, const void *d_in, s
     if (bad) { g_dpd_err = bad; return MCRX_EINVAL; }
     if (n == 0) return MCRX_OK;
     hipStream_t st = (hipStream_t)stream;
-    const bool apply = q->trained;                                      // (a reset still pending means not trained: the stale table is not read)
-    DpdArgs a = {};
-    a.in = d_in; a.out = d_out; a.quads = q->quads; a.clip = q->clip.device();
-    a.parity = (reinterpret_cast<uintptr_t>(d_in) >> 3) & 1u; a.n = n;
-    a.K = q->k.K; a.inv_step = q->k.inv_step; a.gain = q->cfg.gain;
-    a.rounds = apply ? dpd_rounds(a.K) : 1u;
-    const dim3 grid(dpd_apply_grid(a.parity, n, a.rounds)), wg(DPD_WG);
-    const uint32_t lds = apply ? dpd_apply_lds(a.K) : 0u;
-    if (apply) { if (out16) hipLaunchKernelGGL((dpd_kernel<IQ_SC16, true>), grid, wg, lds, st, a);
-                 else       hipLaunchKernelGGL((dpd_kernel<IQ_CF32, true>), grid, wg, lds, st, a); }
-    else       { if (out16) hipLaunchKernelGGL((dpd_kernel<IQ_SC16, false>), grid, wg, lds, st, a);
-                 else       hipLaunchKernelGGL((dpd_kernel<IQ_CF32, false>), grid, wg, lds, st, a); }
-    MCRX_OP_CHK(g_dpd_err, hipGetLastError());
+    // (a reset still pending means not trained: the stale table is not read)
+    MCRX_OP_CHK(g_dpd_err, pd_stream_launch(out16, q->trained, d_in, d_out, n, q->quads, q->clip.device(), q->k.K, q->k.inv_step, q->cfg.gain, st));
     if (out16) MCRX_OP_CHK(g_dpd_err, q->clip.mark(st));
     return MCRX_OK;
 }
@@ -348,14 +233,11 @@ extern "C" int mcrx_hip_dpd_measure_device(mcrx_hip_dpd_t q, const void *d_u, co
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_dpd_err = "null handle"; return MCRX_EINVAL; }
-    // two inputs, nothing written: the call check once per buffer (an overlap of u and z harms nothing)
-    const char *bad = stream_call_check(reinterpret_cast<uintptr_t>(d_u), 0, n, 8u, 8u, 0, false, true, "");
-    if (!bad) bad = stream_call_check(reinterpret_cast<uintptr_t>(d_z), 0, n, 8u, 8u, 0, false, true, "");
-    if (!bad && !dpd_guard_ok(q->since, n)) bad = "more than 2^28 samples offered since the last reset: the int64 sums could overflow";
+    const char *bad = pd_measure_check(q, d_u, d_z, n, n, DPD_GUARD_LOG2, "more than 2^28 samples offered since the last reset: the int64 sums could overflow");
     if (bad) { g_dpd_err = bad; return MCRX_EINVAL; }
     if (n == 0) return MCRX_OK;
     hipStream_t st = (hipStream_t)stream;
-    MCRX_OP_CHK(g_dpd_err, dpd_serve_reset(q, st));
+    MCRX_OP_CHK(g_dpd_err, pd_serve_reset(q, st, dpd_launch_table));
     DpdMeasure m = {};
     m.u = d_u; m.z = d_z; m.acc = reinterpret_cast<unsigned long long *>(q->acc); m.skipped = &q->state->skipped;
     m.parity = (reinterpret_cast<uintptr_t>(d_u) >> 3) & 1u; m.n = n;
@@ -371,34 +253,21 @@ extern "C" int mcrx_hip_dpd_update(mcrx_hip_dpd_t q, void *stream)
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_dpd_err = "null handle"; return MCRX_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
-    MCRX_OP_CHK(g_dpd_err, dpd_serve_reset(q, st));
+    MCRX_OP_CHK(g_dpd_err, pd_serve_reset(q, st, dpd_launch_table));
     DpdUpdate p = {};
     p.state = q->state; p.F = q->F; p.quads = q->quads; p.acc = q->acc;
     p.K = q->k.K; p.min_count = q->cfg.min_count; p.forget_shift = q->cfg.forget_shift;
     p.step = q->k.step; p.g0 = (double)q->cfg.target_gain;
     hipLaunchKernelGGL(dpd_update_kernel, dim3(1), dim3(DPD_WG), 0, st, p);
     MCRX_OP_CHK(g_dpd_err, hipGetLastError());
-    q->since = dpd_guard_after_update(q->since, q->cfg.forget_shift);
+    q->since = pd_guard_after_update(q->since, q->cfg.forget_shift);
     q->trained = true;
     return MCRX_OK;
 }
 
 extern "C" int mcrx_hip_dpd_set_table(mcrx_hip_dpd_t q, const float *F, void *stream)
 {
-    DevScope dev_scope_(q ? q->device : -1);
-    if (!q) { g_dpd_err = "null handle"; return MCRX_EINVAL; }
-    if (!F) { g_dpd_err = "null pointer"; return MCRX_EINVAL; }
-    const size_t nf = 2 * ((size_t)q->k.K + 1);
-    for (size_t i = 0; i < nf; i++)
-        if (!std::isfinite(F[i])) { g_dpd_err = "the table must be finite"; return MCRX_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    MCRX_OP_CHK(g_dpd_err, dpd_serve_reset(q, st));
-    MCRX_OP_CHK(g_dpd_err, hipMemcpyAsync(q->F, F, nf * sizeof(float), hipMemcpyHostToDevice, st));
-    MCRX_OP_CHK(g_dpd_err, hipStreamSynchronize(st));                    // F is the caller's: it has been read when this returns
-    hipLaunchKernelGGL(dpd_table_kernel, dim3(1), dim3(DPD_WG), 0, st, q->state, q->F, q->quads, q->acc, q->k.K, 0u);
-    MCRX_OP_CHK(g_dpd_err, hipGetLastError());
-    q->trained = true;
-    return MCRX_OK;
+    return pd_set_tables(q, g_dpd_err, "the table must be finite", F, 1, q ? q->k.K : 0, stream, dpd_launch_table);
 }
 
 extern "C" int mcrx_hip_dpd_read(mcrx_hip_dpd_t q, mcrx_hip_dpd_state *state, float *F, int64_t *acc, void *stream)
@@ -406,7 +275,7 @@ extern "C" int mcrx_hip_dpd_read(mcrx_hip_dpd_t q, mcrx_hip_dpd_state *state, fl
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_dpd_err = "null handle"; return MCRX_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
-    MCRX_OP_CHK(g_dpd_err, dpd_serve_reset(q, st));
+    MCRX_OP_CHK(g_dpd_err, pd_serve_reset(q, st, dpd_launch_table));
     const size_t K = q->k.K;
     DpdState s = {};
     if (state) MCRX_OP_CHK(g_dpd_err, hipMemcpyAsync(&s, q->state, sizeof(s), hipMemcpyDeviceToHost, st));

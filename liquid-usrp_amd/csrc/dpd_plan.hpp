@@ -1,11 +1,13 @@
 // dpd_plan.hpp -- the host arithmetic of the digital predistorter (dpd.hip: mcrx_hip_dpd_*) that needs no
 // device: the configuration check, the constants made of a configuration (inv_step, step, e and what follows from e), the bin and the
-// eligibility of one (u, z) pair -- the very function the measuring kernel calls --, the guard of the int64 accumulators and the launch
-// grids.  selftest, create and measure all call it; host/dpd_plan_test.cc compiles it with a main of its own.
+// eligibility of one (u, z) pair -- the very function the measuring kernel calls --, the bound of the int64 accumulators' guard and the
+// measuring launch's grid.  What a table and a streaming launch are it takes from pdtable.hpp.  selftest, create and measure all call it;
+// host/dpd_plan_test.cc compiles it with a main of its own.
 #pragma once
 #include <cmath>
 #include <stdint.h>
 #include "../../include/mcrx_hip.h"
+#include "pdtable.hpp"
 
 #if defined(__HIPCC__)
 #define DPD_HD __host__ __device__
@@ -15,9 +17,8 @@
 
 namespace mcrx {
 
-enum { DPD_WG = 256,                // lanes of a workgroup; a lane owns index-aligned sample pairs
+enum { DPD_WG = PD_WG,              // lanes of a workgroup; a lane owns index-aligned sample pairs
        DPD_MAX_WGS = 2048,          // the most workgroups of a measure launch (8 per CU): a lane loops grid * 256 pairs apart
-       DPD_UNROLL = 4,              // rounds an apply lane has in flight; dpd_rounds() is a multiple of it
        DPD_MIN_LOG2 = 5, DPD_MAX_LOG2 = 10, DPD_MAX_FORGET = 8,
        DPD_GUARD_LOG2 = 28 };       // at most 2^28 samples offered between two resets (derived below)
 
@@ -37,25 +38,17 @@ static inline const char *dpd_check(const mcrx_hip_dpd_config *c)
     return nullptr;
 }
 
-// What apply, measure and update use of a (checked) configuration.
-//   K = 2^table_log2; inv_step = fp32(K / full_scale) and step = full_scale / K, both quotients made in double;
-//   e: E = 2^e is the least power of two that is >= full_scale;
+// What apply, measure and update use of a (checked) configuration: the table's constants (pd_table_consts) and
 //   scale = 2^(32 - 2e): what a product of two amplitudes is multiplied with before it is rounded to an integer (exact in double:
 //           e lies in -149 .. 128, so the exponent in -224 .. 330);
 //   zmax2 = fp32(16 E^2) = 2^(2e + 4): the largest |z|^2 of an eligible sample; +inf where 2e + 4 > 127 (finiteness is the bound
 //           then), 0 where 2e + 4 < -149.
-struct DpdConsts { uint32_t K; float inv_step, Kf, zmax2; double step, scale; int e; };
+struct DpdConsts : PdTableConsts { float zmax2; double scale; };
 
 static inline DpdConsts dpd_consts(const mcrx_hip_dpd_config *c)
 {
     DpdConsts k;
-    k.K = 1u << c->table_log2;
-    k.Kf = (float)k.K;
-    k.inv_step = (float)((double)k.K / (double)c->full_scale);
-    k.step = (double)c->full_scale / (double)k.K;
-    int ex = 0;
-    const double m = std::frexp((double)c->full_scale, &ex);            // full_scale = m 2^ex, 0.5 <= m < 1
-    k.e = m == 0.5 ? ex - 1 : ex;
+    static_cast<PdTableConsts &>(k) = pd_table_consts(c->table_log2, c->full_scale);
     k.scale = std::ldexp(1.0, 32 - 2 * k.e);
     k.zmax2 = (float)std::ldexp(1.0, 2 * k.e + 4);
     return k;
@@ -88,37 +81,17 @@ DPD_HD static inline void dpd_terms(float ur, float ui, float zr, float zi, doub
 // (where 16 E^2 is not an fp32, E >= 2^62 and a finite |z|^2_32 means |z| < 2^64 <= 4 E as well).  So a term is at most
 //     |z| |u| 2^32 / E^2 + 1/2 < 4.07 * 2^32 < 2^34.03         (Suu: 1.04 * 2^32)
 // in magnitude, and M samples move an accumulator by less than M 2^34.03: M <= 2^28 keeps it below 2^62.03 < 2^63.  The count is a
-// 32-bit word in a workgroup's LDS and an int64 on the handle; 2^28 fits both.  An arithmetic shift right by s maps |a| to at most
-// ceil(|a| / 2^s), so the host's count follows an update as ceil(count / 2^s) and stays an upper bound of |a| / 2^34.03.
+// 32-bit word in a workgroup's LDS and an int64 on the handle; 2^28 fits both.  Across an update the host's count follows the shift
+// (pd_guard_after_update) and stays an upper bound of |a| / 2^34.03.
 static inline double dpd_term_bound(uint32_t K) { return 4.0 * 1.0000002 * (1.0 + 0.5 / (double)K) * 1.000001 * 4294967296.0 + 0.5; }
-static inline bool dpd_guard_ok(uint64_t since, uint64_t n)
-{
-    const uint64_t most = (uint64_t)1 << DPD_GUARD_LOG2;
-    return since <= most && n <= most - since;
-}
-static inline uint64_t dpd_guard_after_update(uint64_t since, uint32_t forget_shift)
-{
-    return (since + (((uint64_t)1 << forget_shift) - 1)) >> forget_shift;
-}
 
-// lane pairs of a launch over n >= 1 samples whose first lies at an odd (1) or even (0) multiple of 8 bytes: iqpair.hpp's pairs
-static inline uint64_t dpd_pairs(uint64_t parity, uint64_t n) { return ((parity & 1u) + n + 1) >> 1; }
-// rounds of 256 pairs a workgroup of an apply launch takes: its table (16 K bytes from L2) is 1/16 of the 2 * 8 * 512 bytes a round streams
-static inline uint32_t dpd_rounds(uint32_t K) { return K / 32u > (uint32_t)DPD_UNROLL ? K / 32u : (uint32_t)DPD_UNROLL; }
-// the workgroups of an execute launch: `rounds` * 256 pairs each (the copy build: 1 round; at most 2^31 + 1 pairs of 2^32 samples)
-static inline uint32_t dpd_apply_grid(uint64_t parity, uint64_t n, uint32_t rounds)
-{
-    const uint64_t per_wg = (uint64_t)DPD_WG * rounds;
-    return (uint32_t)((dpd_pairs(parity, n) + per_wg - 1) / per_wg);
-}
 // the workgroups of a measure launch: a workgroup owns a histogram, so the grid is capped and a lane loops over pairs grid * 256 apart
 static inline uint32_t dpd_measure_grid(uint64_t parity, uint64_t n)
 {
-    const uint64_t wgs = (dpd_pairs(parity, n) + DPD_WG - 1) / DPD_WG;
+    const uint64_t wgs = (pd_pairs(parity, n) + DPD_WG - 1) / DPD_WG;
     return (uint32_t)(wgs > (uint64_t)DPD_MAX_WGS ? (uint64_t)DPD_MAX_WGS : wgs);
 }
-// LDS of a launch: the table's K quadruples (apply), three 8-byte sums and a 4-byte count per bin (measure)
-static inline uint32_t dpd_apply_lds(uint32_t K) { return K * 16u; }
+// LDS of a measure launch: three 8-byte sums and a 4-byte count per bin
 static inline uint32_t dpd_measure_lds(uint32_t K) { return (K + 1u) * 28u; }           // (the sums first: they stay 8-byte aligned)
 
 }  // namespace mcrx

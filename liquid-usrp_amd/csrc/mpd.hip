@@ -5,11 +5,15 @@
 // The handle owns, in device memory, the state (counters, rows, res, c), the M tables F_m[0 .. K], the same tables as M K quadruples
 // (F[k], F[k+1] - F[k]) and the (L + 1)(L + 2) / 2 complex int64 sums.  Nothing of it is read back by a launch's host side.
 //
-// mpd_apply_kernel<M, FOUT>: dpd_kernel's lane layout -- a lane owns an index-aligned pair of outputs.  A workgroup stages the
-// quadruples of all M tables in LDS once and takes mpd_rounds() rounds of 256 pairs.  M = 1 is dpd's loop, four rounds' loads in
-// flight, no window.  With M > 1 a round stages its 512 + lead samples in LDS as (x.re, x.im, f, k): amplitude, index and fraction
-// are computed once a sample, and a branch is two 16-byte LDS reads (the staged sample, the quadruple), two fmaf and the product.
-// mpd_copy_kernel<FOUT>: the handle that has learned nothing: load in[lead + i], [gain,] convert, store.
+// A trained handle of one branch runs pdtable.hpp's pd_stream_kernel as dpd does.  The handle's fields and the bodies of create,
+// destroy, reset and set_tables are pdtable.hpp's too.
+// mpd_apply_kernel<M, FOUT>, M = 2 .. 4: pd_stream_kernel's lane layout -- a lane owns an index-aligned pair of outputs.  A workgroup
+// stages the quadruples of all M tables in LDS once and takes mpd_rounds() rounds of 256 pairs.  A round stages its 512 + lead samples
+// in LDS as (x.re, x.im, f, k): amplitude, index and fraction are computed once a sample (pd_stage), and a branch is two 16-byte LDS
+// reads (the staged sample, the quadruple), two fmaf and the product (pd_branch).
+// mpd_copy_kernel<FOUT>: the handle that has learned nothing: load in[lead + i], [gain,] convert, store.  It is pd_stream_kernel's copy
+// build without the loop, and stays because it is the faster of the two (0.540 against 0.558 ms on 207.7 M samples:
+// profiles/pd_bench_ab.jsonl).
 // mpd_measure_kernel: a workgroup stages a tile of 256 rows -- the 256 + lead feedback samples' regressors and the 256 targets as
 // int32 pairs, one flag a row -- then lane t < (L + 1)(L + 2) / 2 owns the sum S_pq and loops over the tile's eligible rows: two
 // 8-byte LDS reads and four 32 x 32 -> 64-bit multiply-adds a row.  The lane keeps its sum in registers over all the workgroup's tiles
@@ -26,34 +30,17 @@
 #include <string>
 #include "../../include/mcrx_hip.h"
 #include "mpd_plan.hpp"
-#include "iqpair.hpp"
-#include "ophost.hpp"
-#include "stream_call.hpp"
+#include "pdtable.hpp"
 
 namespace mcrx {
 
-struct MpdArgs {
+struct MpdArgs {                                             // a launch of the window kernel (M > 1) or of the copy kernel
     const void *in; void *out;                              // in: the sample of output 0 (lead samples behind the call's d_in)
     const float4 *quads;                                    // M K quadruples (F[k].re, F[k].im, dF.re, dF.im), table after table
     unsigned long long *clip;                               // sc16-out builds: the handle's count of clipped samples
     uint64_t parity, n;                                     // (address of in[0] / 8) & 1; outputs of this launch
     uint32_t K, rounds, lead, delay[MPD_MAX_BRANCHES]; float inv_step, gain;
 };
-
-// dpd_sample's arithmetic, in its two halves: what depends on the sample alone, and one branch's gain and product
-__device__ __forceinline__ float4 mpd_stage(float2 x, float inv_step, float Kf, int Km1)
-{
-    const float t = fmaf(x.x, x.x, x.y * x.y), a = sqrtf(t);
-    const float s = fminf(a * inv_step, Kf);
-    const int k = min((int)s, Km1);
-    return make_float4(x.x, x.y, s - (float)k, __int_as_float(k));
-}
-__device__ __forceinline__ float2 mpd_branch(const float4 *tab, float4 w)
-{
-    const float4 q = tab[__float_as_int(w.w)];
-    const float gr = fmaf(w.z, q.z, q.x), gi = fmaf(w.z, q.w, q.y);
-    return make_float2(fmaf(gr, w.x, -(gi * w.y)), fmaf(gr, w.y, gi * w.x));
-}
 
 template <int M, int FOUT>
 __global__ __launch_bounds__(MPD_WG) void mpd_apply_kernel(MpdArgs a)
@@ -66,57 +53,38 @@ __global__ __launch_bounds__(MPD_WG) void mpd_apply_kernel(MpdArgs a)
     const int Km1 = (int)a.K - 1;
     uint32_t nclip = 0;
     const uint64_t base = (uint64_t)blockIdx.x * a.rounds * MPD_WG + threadIdx.x;
-    if (M == 1) {                                                       // dpd_kernel's loop
-        constexpr int U = (int)DPD_UNROLL;
-        for (uint32_t r = 0; r < a.rounds; r += U) {
-            IqPair p[U];
-            float2 x0[U], x1[U];
+    // win[s] is the staged sample wbase + s of the launch, wbase = (the round's first pair's m0) - lead; a sample outside
+    // -lead .. n - 1 is staged as a zero and used by masked outputs only
+    float4 *win = mpd_lds + (uint32_t)M * a.K;
+    const float2 *cur = reinterpret_cast<const float2 *>(a.in);
+    const long long lead = (long long)a.lead, n = (long long)a.n;
+    for (uint32_t r = 0; r < a.rounds; r++) {
+        const IqPair p = iq_pair(a.parity, a.n, base + (uint64_t)r * MPD_WG);
+        // the lane's pair as the window needs it: a half in front of the launch's first output is history, not masked
+        float2 x0 = make_float2(0.f, 0.f), x1 = x0;
+        const bool in0 = p.m0 >= -lead && p.m0 < n, in1 = p.m0 + 1 >= -lead && p.m0 + 1 < n;
+        if (in0 && in1 && (reinterpret_cast<uintptr_t>(cur + p.m0) & 15u) == 0) {
+            const float4 v = *reinterpret_cast<const float4 *>(cur + p.m0);
+            x0 = make_float2(v.x, v.y); x1 = make_float2(v.z, v.w);
+        } else { if (in0) x0 = cur[p.m0]; if (in1) x1 = cur[p.m0 + 1]; }
+        float2 h = make_float2(0.f, 0.f);
+        const long long j = p.m0 - 2ll * threadIdx.x - lead + (long long)threadIdx.x;      // lane t < lead: history sample wbase + t
+        if ((long long)threadIdx.x < lead && j >= -lead && j < n) h = cur[j];
+        const uint32_t mine = a.lead + 2u * threadIdx.x;
+        win[mine] = pd_stage(x0, a.inv_step, Kf, Km1);
+        win[mine + 1u] = pd_stage(x1, a.inv_step, Kf, Km1);
+        if ((long long)threadIdx.x < lead) win[threadIdx.x] = pd_stage(h, a.inv_step, Kf, Km1);
+        __syncthreads();
+        float2 v0 = pd_branch(tab, win[mine]), v1 = pd_branch(tab, win[mine + 1u]);
 #pragma unroll
-            for (int u = 0; u < U; u++) {
-                p[u] = iq_pair(a.parity, a.n, base + (uint64_t)(r + u) * MPD_WG);
-                load_pair<IQ_CF32>(a.in, p[u], x0[u], x1[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                float2 v0 = mpd_branch(tab, mpd_stage(x0[u], a.inv_step, Kf, Km1)), v1 = mpd_branch(tab, mpd_stage(x1[u], a.inv_step, Kf, Km1));
-                if (a.gain != 1.0f) { v0 = make_float2(a.gain * v0.x, a.gain * v0.y); v1 = make_float2(a.gain * v1.x, a.gain * v1.y); }
-                nclip += store_pair<FOUT>(a.out, p[u], v0, v1);
-            }
+        for (int m = 1; m < M; m++) {
+            const float2 p0 = pd_branch(tab + (uint32_t)m * a.K, win[mine - a.delay[m]]);
+            const float2 p1 = pd_branch(tab + (uint32_t)m * a.K, win[mine + 1u - a.delay[m]]);
+            v0 = make_float2(v0.x + p0.x, v0.y + p0.y); v1 = make_float2(v1.x + p1.x, v1.y + p1.y);
         }
-    } else {
-        // win[s] is the staged sample wbase + s of the launch, wbase = (the round's first pair's m0) - lead; a sample outside
-        // -lead .. n - 1 is staged as a zero and used by masked outputs only
-        float4 *win = mpd_lds + (uint32_t)M * a.K;
-        const float2 *cur = reinterpret_cast<const float2 *>(a.in);
-        const long long lead = (long long)a.lead, n = (long long)a.n;
-        for (uint32_t r = 0; r < a.rounds; r++) {
-            const IqPair p = iq_pair(a.parity, a.n, base + (uint64_t)r * MPD_WG);
-            // the lane's pair as the window needs it: a half in front of the launch's first output is history, not masked
-            float2 x0 = make_float2(0.f, 0.f), x1 = x0;
-            const bool in0 = p.m0 >= -lead && p.m0 < n, in1 = p.m0 + 1 >= -lead && p.m0 + 1 < n;
-            if (in0 && in1 && (reinterpret_cast<uintptr_t>(cur + p.m0) & 15u) == 0) {
-                const float4 v = *reinterpret_cast<const float4 *>(cur + p.m0);
-                x0 = make_float2(v.x, v.y); x1 = make_float2(v.z, v.w);
-            } else { if (in0) x0 = cur[p.m0]; if (in1) x1 = cur[p.m0 + 1]; }
-            float2 h = make_float2(0.f, 0.f);
-            const long long j = p.m0 - 2ll * threadIdx.x - lead + (long long)threadIdx.x;      // lane t < lead: history sample wbase + t
-            if ((long long)threadIdx.x < lead && j >= -lead && j < n) h = cur[j];
-            const uint32_t mine = a.lead + 2u * threadIdx.x;
-            win[mine] = mpd_stage(x0, a.inv_step, Kf, Km1);
-            win[mine + 1u] = mpd_stage(x1, a.inv_step, Kf, Km1);
-            if ((long long)threadIdx.x < lead) win[threadIdx.x] = mpd_stage(h, a.inv_step, Kf, Km1);
-            __syncthreads();
-            float2 v0 = mpd_branch(tab, win[mine]), v1 = mpd_branch(tab, win[mine + 1u]);
-#pragma unroll
-            for (int m = 1; m < M; m++) {
-                const float2 p0 = mpd_branch(tab + (uint32_t)m * a.K, win[mine - a.delay[m]]);
-                const float2 p1 = mpd_branch(tab + (uint32_t)m * a.K, win[mine + 1u - a.delay[m]]);
-                v0 = make_float2(v0.x + p0.x, v0.y + p0.y); v1 = make_float2(v1.x + p1.x, v1.y + p1.y);
-            }
-            if (a.gain != 1.0f) { v0 = make_float2(a.gain * v0.x, a.gain * v0.y); v1 = make_float2(a.gain * v1.x, a.gain * v1.y); }
-            nclip += store_pair<FOUT>(a.out, p, v0, v1);
-            __syncthreads();                                            // the window is restaged by the next round
-        }
+        if (a.gain != 1.0f) { v0 = make_float2(a.gain * v0.x, a.gain * v0.y); v1 = make_float2(a.gain * v1.x, a.gain * v1.y); }
+        nclip += store_pair<FOUT>(a.out, p, v0, v1);
+        __syncthreads();                                            // the window is restaged by the next round
     }
     if (FOUT == IQ_SC16) sc16_clip_commit(a.clip, nclip);               // every lane of every wave gets here
 }
@@ -210,16 +178,6 @@ struct MpdUpdate {
     uint32_t M, P, L, K, min_rows, forget_shift;
     double step, ridge, inv_E;                              // 2^-ridge_log2, 2^-e
 };
-
-// quads[m K + k] = (F_m[k], F_m[k+1] - F_m[k]): the fp32 subtraction the definition writes
-__device__ __forceinline__ void mpd_write_quads(const float2 *F, float4 *quads, uint32_t M, uint32_t K)
-{
-    for (uint32_t i = threadIdx.x; i < M * K; i += MPD_WG) {
-        const uint32_t m = i / K, k = i - m * K;
-        const float2 f0 = F[m * (K + 1u) + k], f1 = F[m * (K + 1u) + k + 1u];
-        quads[i] = make_float4(f0.x, f0.y, f1.x - f0.x, f1.y - f0.y);
-    }
-}
 
 __device__ __forceinline__ bool mpd_finite(double v) { return v - v == 0.0; }
 
@@ -323,7 +281,7 @@ __global__ __launch_bounds__(MPD_WG) void mpd_update_kernel(MpdUpdate u)
     }
     __threadfence();
     __syncthreads();
-    mpd_write_quads(u.F, u.quads, u.M, u.K);
+    pd_write_quads(u.F, u.quads, u.M, u.K);
     if (u.forget_shift)
         for (uint32_t b = threadIdx.x; b < (u.L + 1u) * (u.L + 2u); b += MPD_WG) u.sums[b] >>= u.forget_shift;
 }
@@ -342,7 +300,7 @@ __global__ __launch_bounds__(MPD_WG) void mpd_table_kernel(MpdState *state, floa
         __threadfence();
         __syncthreads();
     }
-    mpd_write_quads(F, quads, M, K);
+    pd_write_quads(F, quads, M, K);
 }
 
 }  // namespace mcrx
@@ -351,17 +309,16 @@ using namespace mcrx;
 
 static thread_local std::string g_mpd_err;
 
-struct mcrx_hip_mpd_s {
-    int device = -1;            // the HIP device the handle was created on: every entry point runs with it current (devscope.hpp)
+struct mcrx_hip_mpd_s : PdHandle {
     mcrx_hip_mpd_config cfg;
     MpdConsts k;
-    Sc16ClipCount clip;         // sc16-out handles only
-    char *mem = nullptr;        // device: MpdState, quads, sums, F
-    MpdState *state = nullptr; float2 *F = nullptr; float4 *quads = nullptr; long long *sums = nullptr;
-    uint64_t since = 0;         // rows offered since the last reset, following the updates' shifts (the 2^26 guard)
-    bool trained = false;       // an update or a set_tables has been enqueued since the reset: launches carry the apply code
-    bool reset_pending = false; // the next kernel that touches the state clears it first
+    MpdState *state = nullptr; long long *sums = nullptr;   // in mem, with F and quads
 };
+
+static void mpd_launch_table(mcrx_hip_mpd_t q, hipStream_t st, uint32_t reset)
+{
+    hipLaunchKernelGGL(mpd_table_kernel, dim3(1), dim3(MPD_WG), 0, st, q->state, q->F, q->quads, q->sums, q->k.M, q->k.K, q->k.L, reset);
+}
 
 extern "C" const char *mcrx_hip_mpd_last_error(void) { return g_mpd_err.c_str(); }
 
@@ -391,67 +348,29 @@ extern "C" int mcrx_hip_mpd_create(mcrx_hip_mpd_t *out, const mcrx_hip_mpd_confi
     *out = nullptr;
     if (!cfg) { g_mpd_err = "null configuration"; return MCRX_EINVAL; }
     if (const char *bad = mpd_check(cfg)) { g_mpd_err = bad; return MCRX_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { g_mpd_err = "no HIP device (no CPU fallback)"; return MCRX_EHIP; }
     mcrx_hip_mpd_t q = new mcrx_hip_mpd_s();
-    q->device = current_device();
     q->cfg = *cfg;
     q->k = mpd_consts(cfg);
     const size_t K = q->k.K, M = q->k.M;
-    const size_t o_quads = (sizeof(MpdState) + 15u) & ~(size_t)15u, o_sums = o_quads + M * K * sizeof(float4);
-    const size_t o_F = o_sums + 2 * (size_t)q->k.sums * sizeof(long long), bytes = o_F + M * (K + 1) * sizeof(float2);
-    hipError_t e = hipMalloc((void **)&q->mem, bytes);
-    if (e == hipSuccess) {
-        q->state = reinterpret_cast<MpdState *>(q->mem);
-        q->quads = reinterpret_cast<float4 *>(q->mem + o_quads);
-        q->sums = reinterpret_cast<long long *>(q->mem + o_sums);
-        q->F = reinterpret_cast<float2 *>(q->mem + o_F);
-        e = hipMemset(q->mem, 0, bytes);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && cfg->output_format == IQ_SC16) e = q->clip.ensure();
-    if (e != hipSuccess) { g_mpd_err = std::string("device state: ") + hipGetErrorString(e); mcrx_hip_mpd_destroy(q); return MCRX_EHIP; }
-    q->reset_pending = true;                                            // the tables are (1, 0 ...) before anything reads them
+    const int rc = pd_alloc(q, g_mpd_err, cfg->output_format == IQ_SC16, M, K, sizeof(MpdState), 2 * (size_t)q->k.sums * sizeof(long long));
+    if (rc != MCRX_OK) { delete q; return rc; }
+    q->state = reinterpret_cast<MpdState *>(q->mem);
+    q->sums = reinterpret_cast<long long *>(q->quads + M * K);
     *out = q;
     return MCRX_OK;
 }
 
-extern "C" int mcrx_hip_mpd_destroy(mcrx_hip_mpd_t q)
-{
-    DevScope dev_scope_(q ? q->device : -1);
-    if (!q) return MCRX_OK;
-    (void)hipDeviceSynchronize();
-    if (q->mem) (void)hipFree(q->mem);
-    q->clip.release();
-    delete q;
-    return MCRX_OK;
-}
+extern "C" int mcrx_hip_mpd_destroy(mcrx_hip_mpd_t q) { return pd_destroy(q); }
 
 extern "C" unsigned mcrx_hip_mpd_output_format(mcrx_hip_mpd_t q) { return q ? q->cfg.output_format : 0u; }
 extern "C" unsigned mcrx_hip_mpd_lead(mcrx_hip_mpd_t q) { return q ? q->k.lead : 0u; }
 
-extern "C" int mcrx_hip_mpd_reset(mcrx_hip_mpd_t q)
-{
-    if (!q) { g_mpd_err = "null handle"; return MCRX_EINVAL; }
-    q->since = 0; q->trained = false; q->reset_pending = true;
-    return MCRX_OK;
-}
-
-// the state cleared if a reset is pending: in front of every kernel that reads or writes tables, sums or counters
-static hipError_t mpd_serve_reset(mcrx_hip_mpd_t q, hipStream_t st)
-{
-    if (!q->reset_pending) return hipSuccess;
-    hipLaunchKernelGGL(mpd_table_kernel, dim3(1), dim3(MPD_WG), 0, st, q->state, q->F, q->quads, q->sums, q->k.M, q->k.K, q->k.L, 1u);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) q->reset_pending = false;
-    return e;
-}
+extern "C" int mcrx_hip_mpd_reset(mcrx_hip_mpd_t q) { return pd_reset(q, g_mpd_err); }
 
 template <int FOUT> static void mpd_launch_apply(uint32_t M, dim3 grid, uint32_t lds, hipStream_t st, const MpdArgs &a)
 {
     const dim3 wg(MPD_WG);
     switch (M) {
-    case 1: hipLaunchKernelGGL((mpd_apply_kernel<1, FOUT>), grid, wg, lds, st, a); break;
     case 2: hipLaunchKernelGGL((mpd_apply_kernel<2, FOUT>), grid, wg, lds, st, a); break;
     case 3: hipLaunchKernelGGL((mpd_apply_kernel<3, FOUT>), grid, wg, lds, st, a); break;
     default: hipLaunchKernelGGL((mpd_apply_kernel<4, FOUT>), grid, wg, lds, st, a); break;
@@ -470,22 +389,27 @@ extern "C" int mcrx_hip_mpd_execute_device(mcrx_hip_mpd_t q, const void *d_in, s
     if (bad) { g_mpd_err = bad; return MCRX_EINVAL; }
     if (n == 0) return MCRX_OK;
     hipStream_t st = (hipStream_t)stream;
+    const float2 *in = reinterpret_cast<const float2 *>(d_in) + lead;  // the sample of output 0
     const bool apply = q->trained;                                      // (a reset still pending means not trained: the stale tables are not read)
-    MpdArgs a = {};
-    a.in = reinterpret_cast<const float2 *>(d_in) + lead; a.out = d_out; a.quads = q->quads; a.clip = q->clip.device();
-    a.parity = (reinterpret_cast<uintptr_t>(a.in) >> 3) & 1u; a.n = n;
-    a.K = q->k.K; a.lead = lead; a.inv_step = q->k.inv_step; a.gain = q->cfg.gain;
-    for (uint32_t m = 0; m < q->k.M; m++) a.delay[m] = q->k.delay[m];
-    a.rounds = apply ? mpd_rounds(q->k.M, a.K) : 1u;
-    const dim3 grid(dpd_apply_grid(a.parity, n, a.rounds));
-    if (apply) {
-        const uint32_t lds = mpd_apply_lds(q->k.M, a.K, lead);
-        if (out16) mpd_launch_apply<IQ_SC16>(q->k.M, grid, lds, st, a); else mpd_launch_apply<IQ_CF32>(q->k.M, grid, lds, st, a);
+    if (apply && q->k.M == 1u) {
+        MCRX_OP_CHK(g_mpd_err, pd_stream_launch(out16, true, in, d_out, n, q->quads, q->clip.device(), q->k.K, q->k.inv_step, q->cfg.gain, st));
     } else {
-        if (out16) hipLaunchKernelGGL((mpd_copy_kernel<IQ_SC16>), grid, dim3(MPD_WG), 0, st, a);
-        else       hipLaunchKernelGGL((mpd_copy_kernel<IQ_CF32>), grid, dim3(MPD_WG), 0, st, a);
+        MpdArgs a = {};
+        a.in = in; a.out = d_out; a.quads = q->quads; a.clip = q->clip.device();
+        a.parity = (reinterpret_cast<uintptr_t>(a.in) >> 3) & 1u; a.n = n;
+        a.K = q->k.K; a.lead = lead; a.inv_step = q->k.inv_step; a.gain = q->cfg.gain;
+        for (uint32_t m = 0; m < q->k.M; m++) a.delay[m] = q->k.delay[m];
+        a.rounds = apply ? mpd_rounds(q->k.M, a.K) : 1u;
+        const dim3 grid(pd_stream_grid(a.parity, n, a.rounds));
+        if (apply) {
+            const uint32_t lds = mpd_apply_lds(q->k.M, a.K, lead);
+            if (out16) mpd_launch_apply<IQ_SC16>(q->k.M, grid, lds, st, a); else mpd_launch_apply<IQ_CF32>(q->k.M, grid, lds, st, a);
+        } else {
+            if (out16) hipLaunchKernelGGL((mpd_copy_kernel<IQ_SC16>), grid, dim3(MPD_WG), 0, st, a);
+            else       hipLaunchKernelGGL((mpd_copy_kernel<IQ_CF32>), grid, dim3(MPD_WG), 0, st, a);
+        }
+        MCRX_OP_CHK(g_mpd_err, hipGetLastError());
     }
-    MCRX_OP_CHK(g_mpd_err, hipGetLastError());
     if (out16) MCRX_OP_CHK(g_mpd_err, q->clip.mark(st));
     return MCRX_OK;
 }
@@ -494,15 +418,12 @@ extern "C" int mcrx_hip_mpd_measure_device(mcrx_hip_mpd_t q, const void *d_u, co
 {
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_mpd_err = "null handle"; return MCRX_EINVAL; }
-    // two inputs, nothing written: the call check once per buffer (an overlap of u and z harms nothing)
-    const char *bad = stream_call_check(reinterpret_cast<uintptr_t>(d_u), 0, n, 8u, 8u, 0, false, true, "");
-    if (!bad) bad = stream_call_check(reinterpret_cast<uintptr_t>(d_z), 0, n, 8u, 8u, 0, false, true, "");
     const uint64_t rows = mpd_rows(n, q->k.lead);
-    if (!bad && !mpd_guard_ok(q->since, rows)) bad = "more than 2^26 rows offered since the last reset: the int64 sums could overflow";
+    const char *bad = pd_measure_check(q, d_u, d_z, n, rows, MPD_GUARD_LOG2, "more than 2^26 rows offered since the last reset: the int64 sums could overflow");
     if (bad) { g_mpd_err = bad; return MCRX_EINVAL; }
     if (rows == 0) return MCRX_OK;
     hipStream_t st = (hipStream_t)stream;
-    MCRX_OP_CHK(g_mpd_err, mpd_serve_reset(q, st));
+    MCRX_OP_CHK(g_mpd_err, pd_serve_reset(q, st, mpd_launch_table));
     MpdMeasure m = {};
     m.u = reinterpret_cast<const float2 *>(d_u); m.z = reinterpret_cast<const float2 *>(d_z);
     m.sums = reinterpret_cast<unsigned long long *>(q->sums); m.state = q->state;
@@ -520,34 +441,21 @@ extern "C" int mcrx_hip_mpd_update(mcrx_hip_mpd_t q, void *stream)
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_mpd_err = "null handle"; return MCRX_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
-    MCRX_OP_CHK(g_mpd_err, mpd_serve_reset(q, st));
+    MCRX_OP_CHK(g_mpd_err, pd_serve_reset(q, st, mpd_launch_table));
     MpdUpdate p = {};
     p.state = q->state; p.F = q->F; p.quads = q->quads; p.sums = q->sums;
     p.M = q->k.M; p.P = q->k.P; p.L = q->k.L; p.K = q->k.K; p.min_rows = q->cfg.min_rows; p.forget_shift = q->cfg.forget_shift;
     p.step = q->k.step; p.ridge = std::ldexp(1.0, -(int)q->cfg.ridge_log2); p.inv_E = std::ldexp(1.0, -q->k.e);
     hipLaunchKernelGGL(mpd_update_kernel, dim3(1), dim3(MPD_WG), 0, st, p);
     MCRX_OP_CHK(g_mpd_err, hipGetLastError());
-    q->since = mpd_guard_after_update(q->since, q->cfg.forget_shift);
+    q->since = pd_guard_after_update(q->since, q->cfg.forget_shift);
     q->trained = true;
     return MCRX_OK;
 }
 
 extern "C" int mcrx_hip_mpd_set_tables(mcrx_hip_mpd_t q, const float *F, void *stream)
 {
-    DevScope dev_scope_(q ? q->device : -1);
-    if (!q) { g_mpd_err = "null handle"; return MCRX_EINVAL; }
-    if (!F) { g_mpd_err = "null pointer"; return MCRX_EINVAL; }
-    const size_t nf = 2 * (size_t)q->k.M * ((size_t)q->k.K + 1);
-    for (size_t i = 0; i < nf; i++)
-        if (!std::isfinite(F[i])) { g_mpd_err = "the tables must be finite"; return MCRX_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    MCRX_OP_CHK(g_mpd_err, mpd_serve_reset(q, st));
-    MCRX_OP_CHK(g_mpd_err, hipMemcpyAsync(q->F, F, nf * sizeof(float), hipMemcpyHostToDevice, st));
-    MCRX_OP_CHK(g_mpd_err, hipStreamSynchronize(st));                    // F is the caller's: it has been read when this returns
-    hipLaunchKernelGGL(mpd_table_kernel, dim3(1), dim3(MPD_WG), 0, st, q->state, q->F, q->quads, q->sums, q->k.M, q->k.K, q->k.L, 0u);
-    MCRX_OP_CHK(g_mpd_err, hipGetLastError());
-    q->trained = true;
-    return MCRX_OK;
+    return pd_set_tables(q, g_mpd_err, "the tables must be finite", F, q ? q->k.M : 0, q ? q->k.K : 0, stream, mpd_launch_table);
 }
 
 extern "C" int mcrx_hip_mpd_read(mcrx_hip_mpd_t q, mcrx_hip_mpd_state *state, float *F, double *c, int64_t *sums, void *stream)
@@ -555,7 +463,7 @@ extern "C" int mcrx_hip_mpd_read(mcrx_hip_mpd_t q, mcrx_hip_mpd_state *state, fl
     DevScope dev_scope_(q ? q->device : -1);
     if (!q) { g_mpd_err = "null handle"; return MCRX_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
-    MCRX_OP_CHK(g_mpd_err, mpd_serve_reset(q, st));
+    MCRX_OP_CHK(g_mpd_err, pd_serve_reset(q, st, mpd_launch_table));
     MpdState s = {};
     if (state || c) MCRX_OP_CHK(g_mpd_err, hipMemcpyAsync(&s, q->state, sizeof(s), hipMemcpyDeviceToHost, st));
     if (F) MCRX_OP_CHK(g_mpd_err, hipMemcpyAsync(F, q->F, 2 * (size_t)q->k.M * (q->k.K + 1) * sizeof(float), hipMemcpyDeviceToHost, st));

@@ -1,7 +1,7 @@
 // mpd_plan.hpp -- the arithmetic of the memory-polynomial predistorter (mpd.hip: mcrx_hip_mpd_*) that needs no
 // device: the configuration check, the constants made of a configuration, the integers one feedback sample and one amplifier-input
-// sample turn into -- the very functions the measuring kernel calls --, the guard of the int64 sums, the grids and the LDS sizes.
-// selftest, create and measure all call it; host/mpd_plan_test.cc compiles it with a main of its own.
+// sample turn into -- the very functions the measuring kernel calls --, the bound of the int64 sums' guard, the grids and the LDS sizes.
+// What a table and a streaming launch are it takes from pdtable.hpp.  selftest, create and measure all call it; host/mpd_plan_test.cc compiles it with a main of its own.
 #pragma once
 #include <cmath>
 #include <stdint.h>
@@ -16,7 +16,7 @@
 
 namespace mcrx {
 
-enum { MPD_WG = 256,                // lanes of a workgroup
+enum { MPD_WG = PD_WG,               // lanes of a workgroup
        MPD_TILE = 256,              // rows a measuring workgroup stages at a time
        MPD_MAX_WGS = 1024,          // the most workgroups of a measure launch (4 per CU): a workgroup loops over tiles grid apart
        MPD_MAX_BRANCHES = 4, MPD_MAX_DELAY = 16, MPD_MAX_ORDER = 5, MPD_MAX_COEFFS = 20,
@@ -51,17 +51,14 @@ static inline const char *mpd_check(const mcrx_hip_mpd_config *c)
     return nullptr;
 }
 
-// What apply, measure and update use of a (checked) configuration: K, inv_step, step and e exactly as dpd_consts makes them;
+// What apply, measure and update use of a (checked) configuration: the table's constants (pd_table_consts);
 // inv_g0 = fp32(1 / g0), the quotient made in double; M, P, L = M P, the delays and lead = delay[M - 1]; sums = (L + 1)(L + 2) / 2.
-struct MpdConsts { uint32_t K, M, P, L, lead, sums, delay[MPD_MAX_BRANCHES]; float inv_step, Kf, inv_g0; double step; int e; };
+struct MpdConsts : PdTableConsts { uint32_t M, P, L, lead, sums, delay[MPD_MAX_BRANCHES]; float inv_g0; };
 
 static inline MpdConsts mpd_consts(const mcrx_hip_mpd_config *c)
 {
-    mcrx_hip_dpd_config d = {};
-    d.struct_size = sizeof(d); d.table_log2 = c->table_log2; d.full_scale = c->full_scale; d.target_gain = c->target_gain;
-    const DpdConsts dk = dpd_consts(&d);
     MpdConsts k = {};
-    k.K = dk.K; k.Kf = dk.Kf; k.inv_step = dk.inv_step; k.step = dk.step; k.e = dk.e;
+    static_cast<PdTableConsts &>(k) = pd_table_consts(c->table_log2, c->full_scale);
     k.inv_g0 = (float)(1.0 / (double)c->target_gain);
     k.M = c->branches; k.P = c->order; k.L = k.M * k.P; k.sums = (k.L + 1u) * (k.L + 2u) / 2u;
     for (uint32_t m = 0; m < k.M; m++) k.delay[m] = c->delay[m];
@@ -107,18 +104,9 @@ MPD_HD static inline bool mpd_target(float ur, float ui, int e, int32_t *Ure, in
 // and the imaginary part of conj(V_p) V_q are at most |V_p| |V_q| in magnitude:
 //     A_pq: 2^34.01        b_l: 2^35.01        Suu: 2^36.01
 // Each is one or two products of int32 values summed in an int64, exactly.  R rows move a sum by less than R 2^36.01: R <= 2^26 keeps
-// every sum below 2^62.01 < 2^63, in a lane's register, in a workgroup's flush and on the handle.  An arithmetic shift right by s maps
-// |a| to at most ceil(|a| / 2^s), so the host's count follows an update as ceil(count / 2^s) and stays an upper bound of |a| / 2^36.01.
+// every sum below 2^62.01 < 2^63, in a lane's register, in a workgroup's flush and on the handle.  Across an update the host's count
+// follows the shift (pd_guard_after_update) and stays an upper bound of |a| / 2^36.01.
 static inline double mpd_term_bound() { const double U = 262144.0 * (1.0 + 1.2e-7) + 0.71; return U * U; }
-static inline bool mpd_guard_ok(uint64_t since, uint64_t rows)
-{
-    const uint64_t most = (uint64_t)1 << MPD_GUARD_LOG2;
-    return since <= most && rows <= most - since;
-}
-static inline uint64_t mpd_guard_after_update(uint64_t since, uint32_t forget_shift)
-{
-    return (since + (((uint64_t)1 << forget_shift) - 1)) >> forget_shift;
-}
 
 // rows of a measure call on n samples; its tiles of 256 rows; its workgroups (capped: a workgroup takes tiles grid apart)
 static inline uint64_t mpd_rows(uint64_t n, uint32_t lead) { return n > lead ? n - lead : 0; }
@@ -128,10 +116,10 @@ static inline uint32_t mpd_measure_grid(uint64_t rows)
     const uint64_t t = mpd_tiles(rows);
     return (uint32_t)(t > (uint64_t)MPD_MAX_WGS ? (uint64_t)MPD_MAX_WGS : t);
 }
-// rounds of 256 pairs an apply workgroup takes: dpd's rule on all M tables (their 16 M K bytes are 1/16 of what the rounds stream)
-static inline uint32_t mpd_rounds(uint32_t M, uint32_t K) { return dpd_rounds(M * K); }
+// rounds of 256 pairs an apply workgroup takes: pd_rounds' rule on all M tables (their 16 M K bytes are 1/16 of what the rounds stream)
+static inline uint32_t mpd_rounds(uint32_t M, uint32_t K) { return pd_rounds(M * K); }
 // LDS of an apply launch: M K quadruples, and with M > 1 the round's window of 512 + lead staged samples, 16 bytes each
-static inline uint32_t mpd_apply_lds(uint32_t M, uint32_t K, uint32_t lead) { return M * K * 16u + (M > 1u ? (2u * MPD_WG + lead) * 16u : 0u); }
+static inline uint32_t mpd_apply_lds(uint32_t M, uint32_t K, uint32_t lead) { return pd_stream_lds(M * K) + (M > 1u ? (2u * MPD_WG + lead) * 16u : 0u); }
 // LDS of a measure launch: (256 + lead) samples' P regressors and 256 targets, 8 bytes each; (256 + lead) + 256 flags
 static inline uint32_t mpd_measure_lds(uint32_t P, uint32_t lead) { return ((MPD_TILE + lead) * P + MPD_TILE) * 8u + (2u * MPD_TILE + lead) * 4u; }
 

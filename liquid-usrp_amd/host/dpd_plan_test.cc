@@ -109,21 +109,22 @@ int main()
             CHECK(dpd_term_bound(w.K) * (double)(1ull << DPD_GUARD_LOG2) < 9223372036854775807.0 / 1.5, "K %u: 2^28 terms overflow", w.K);
         }
     const uint64_t most = 1ull << DPD_GUARD_LOG2;
-    CHECK(dpd_guard_ok(0, most) && !dpd_guard_ok(0, most + 1) && dpd_guard_ok(most - 1, 1) && !dpd_guard_ok(most, 1) && dpd_guard_ok(most, 0)
-          && !dpd_guard_ok(1, ~0ull) && !dpd_guard_ok(~0ull, 1), "the guard at its edge");
-    CHECK(dpd_guard_after_update(most, 0) == most && dpd_guard_after_update(most, 2) == most / 4 && dpd_guard_after_update(5, 2) == 2
-          && dpd_guard_after_update(1, 8) == 1 && dpd_guard_after_update(0, 8) == 0 && dpd_guard_after_update(257, 8) == 2, "the guard across an update");
+    const auto guard_ok = [](uint64_t since, uint64_t n) { return pd_guard_ok(since, n, DPD_GUARD_LOG2); };
+    CHECK(guard_ok(0, most) && !guard_ok(0, most + 1) && guard_ok(most - 1, 1) && !guard_ok(most, 1) && guard_ok(most, 0)
+          && !guard_ok(1, ~0ull) && !guard_ok(~0ull, 1), "the guard at its edge");
+    CHECK(pd_guard_after_update(most, 0) == most && pd_guard_after_update(most, 2) == most / 4 && pd_guard_after_update(5, 2) == 2
+          && pd_guard_after_update(1, 8) == 1 && pd_guard_after_update(0, 8) == 0 && pd_guard_after_update(257, 8) == 2, "the guard across an update");
     // grids and LDS
-    CHECK(dpd_pairs(0, 1) == 1 && dpd_pairs(1, 1) == 1 && dpd_pairs(0, 2) == 1 && dpd_pairs(1, 2) == 2 && dpd_pairs(1, 3) == 2, "pairs");
+    CHECK(pd_pairs(0, 1) == 1 && pd_pairs(1, 1) == 1 && pd_pairs(0, 2) == 1 && pd_pairs(1, 2) == 2 && pd_pairs(1, 3) == 2, "pairs");
     CHECK(dpd_measure_grid(0, 1) == 1 && dpd_measure_grid(0, 512) == 1 && dpd_measure_grid(0, 513) == 2 && dpd_measure_grid(1, 512) == 2
           && dpd_measure_grid(0, 1048576) == 2048 && dpd_measure_grid(0, 1049089) == 2048 && dpd_measure_grid(1, 1ull << 32) == 2048, "measure grid");
-    CHECK(dpd_rounds(32) == 4 && dpd_rounds(128) == 4 && dpd_rounds(256) == 8 && dpd_rounds(1024) == 32, "rounds");
-    for (uint32_t L = DPD_MIN_LOG2; L <= (uint32_t)DPD_MAX_LOG2; L++) CHECK(dpd_rounds(1u << L) % DPD_UNROLL == 0, "rounds of K = 2^%u", L);
-    CHECK(dpd_apply_grid(0, 1, 1) == 1 && dpd_apply_grid(1, 512, 1) == 2 && dpd_apply_grid(0, 1049089, 1) == 2050 && dpd_apply_grid(0, 1ull << 32, 1) == (1u << 23)
-          && dpd_apply_grid(1, 1ull << 32, 1) == (1u << 23) + 1, "copy grid");
-    CHECK(dpd_apply_grid(0, 1, 4) == 1 && dpd_apply_grid(0, 2048, 4) == 1 && dpd_apply_grid(1, 2048, 4) == 2 && dpd_apply_grid(0, 2049, 4) == 2
-          && dpd_apply_grid(0, 1ull << 32, 32) == (1u << 18) && dpd_apply_grid(1, 1ull << 32, 32) == (1u << 18) + 1, "apply grid");
-    CHECK(dpd_apply_lds(1024) == 16384 && dpd_measure_lds(1024) == 28700 && dpd_measure_lds(1024) < 29 * 1024 && dpd_measure_lds(32) == 924, "LDS");
+    CHECK(pd_rounds(32) == 4 && pd_rounds(128) == 4 && pd_rounds(256) == 8 && pd_rounds(1024) == 32, "rounds");
+    for (uint32_t L = DPD_MIN_LOG2; L <= (uint32_t)DPD_MAX_LOG2; L++) CHECK(pd_rounds(1u << L) % PD_UNROLL == 0, "rounds of K = 2^%u", L);
+    CHECK(pd_stream_grid(0, 1, 1) == 1 && pd_stream_grid(1, 512, 1) == 2 && pd_stream_grid(0, 1049089, 1) == 2050 && pd_stream_grid(0, 1ull << 32, 1) == (1u << 23)
+          && pd_stream_grid(1, 1ull << 32, 1) == (1u << 23) + 1, "copy grid");
+    CHECK(pd_stream_grid(0, 1, 4) == 1 && pd_stream_grid(0, 2048, 4) == 1 && pd_stream_grid(1, 2048, 4) == 2 && pd_stream_grid(0, 2049, 4) == 2
+          && pd_stream_grid(0, 1ull << 32, 32) == (1u << 18) && pd_stream_grid(1, 1ull << 32, 32) == (1u << 18) + 1, "apply grid");
+    CHECK(pd_stream_lds(1024) == 16384 && dpd_measure_lds(1024) == 28700 && dpd_measure_lds(1024) < 29 * 1024 && dpd_measure_lds(32) == 924, "LDS");
     if (g_bad) { fprintf(stderr, "dpd_plan_test: %d failures\n", g_bad); return 1; }
     printf("dpd_plan_test ok\n");
     return 0;

@@ -89,15 +89,16 @@ int main()
     CHECK(2.0 * (double)br[0] * br[0] <= mpd_term_bound() / 4.0 * 1.0001, "the modulus bounds the term, not the component: %d", br[0]);
     CHECK(mpd_term_bound() < 68956000000.0 && mpd_term_bound() * (double)(1ull << MPD_GUARD_LOG2) < 9223372036854775807.0 / 1.9, "2^26 terms of 2^36.01");
     const uint64_t most = 1ull << MPD_GUARD_LOG2;
-    CHECK(mpd_guard_ok(0, most) && !mpd_guard_ok(0, most + 1) && mpd_guard_ok(most - 1, 1) && !mpd_guard_ok(most, 1) && mpd_guard_ok(most, 0)
-          && !mpd_guard_ok(1, ~0ull) && !mpd_guard_ok(~0ull, 1), "the guard at its edge");
-    CHECK(mpd_guard_after_update(most, 0) == most && mpd_guard_after_update(most, 2) == most / 4 && mpd_guard_after_update(5, 2) == 2
-          && mpd_guard_after_update(1, 8) == 1 && mpd_guard_after_update(0, 8) == 0 && mpd_guard_after_update(257, 8) == 2, "the guard across an update");
+    const auto guard_ok = [](uint64_t since, uint64_t n) { return pd_guard_ok(since, n, MPD_GUARD_LOG2); };
+    CHECK(guard_ok(0, most) && !guard_ok(0, most + 1) && guard_ok(most - 1, 1) && !guard_ok(most, 1) && guard_ok(most, 0)
+          && !guard_ok(1, ~0ull) && !guard_ok(~0ull, 1), "the guard at its edge");
+    CHECK(pd_guard_after_update(most, 0) == most && pd_guard_after_update(most, 2) == most / 4 && pd_guard_after_update(5, 2) == 2
+          && pd_guard_after_update(1, 8) == 1 && pd_guard_after_update(0, 8) == 0 && pd_guard_after_update(257, 8) == 2, "the guard across an update");
     // rows, tiles, grids, LDS
     CHECK(mpd_rows(0, 0) == 0 && mpd_rows(5, 5) == 0 && mpd_rows(6, 5) == 1 && mpd_rows(3, 16) == 0 && mpd_rows(1ull << 32, 16) == (1ull << 32) - 16, "rows");
     CHECK(mpd_tiles(1) == 1 && mpd_tiles(256) == 1 && mpd_tiles(257) == 2, "tiles");
     CHECK(mpd_measure_grid(1) == 1 && mpd_measure_grid(256 * 1024) == 1024 && mpd_measure_grid(256 * 1024 + 1) == 1024 && mpd_measure_grid(1ull << 26) == 1024, "measure grid");
-    CHECK(mpd_rounds(1, 32) == dpd_rounds(32) && mpd_rounds(1, 1024) == dpd_rounds(1024) && mpd_rounds(4, 128) == 16 && mpd_rounds(2, 32) == 4, "rounds");
+    CHECK(mpd_rounds(1, 32) == pd_rounds(32) && mpd_rounds(1, 1024) == pd_rounds(1024) && mpd_rounds(4, 128) == 16 && mpd_rounds(2, 32) == 4, "rounds");
     CHECK(mpd_apply_lds(1, 1024, 0) == 16384 && mpd_apply_lds(4, 512, 16) == 32768 + 528 * 16 && mpd_apply_lds(2, 1024, 1) == 32768 + 513 * 16, "apply LDS");
     CHECK(mpd_measure_lds(5, 16) == (272 * 5 + 256) * 8 + (512 + 16) * 4 && mpd_measure_lds(5, 16) < 16 * 1024 && mpd_measure_lds(1, 0) == 512 * 8 + 512 * 4, "measure LDS");
     if (g_bad) { fprintf(stderr, "mpd_plan_test: %d failures\n", g_bad); return 1; }

@@ -75,6 +75,56 @@ def test_untouched_handle_is_a_copy(product, fout):
     d.close()
 
 
+@pytest.mark.parametrize("gain", [1.0, 0.5])
+@pytest.mark.parametrize("delays", [(0, 3), (0, 16)], ids=["lead3", "lead16"])
+@pytest.mark.parametrize("fout", ["cf32", "sc16"])
+def test_untouched_copy_from_either_parity(product, fout, delays, gain):
+    """The untouched handle with branches copies from in + lead, the pair parity taken from that address: an odd lead flips it, so odd
+    and even leads meet x at even and odd elements of a larger tensor, around one workgroup's 512 samples, to even and odd offsets.
+    cf32: gain * x[lead:] exactly (gain 1: bit for bit, NaN payloads and -0.0 kept; 0.5 on finite normal values is exact);
+    sc16: the quantiser's model of the same, the clip count with it; nothing written in front of or behind the output."""
+    torch = _torch()
+    out16 = fout == "sc16"
+    d = product.mpd(2, delays, 5, 7, 1.0, 1.0, gain=gain, output_format=fout)
+    lead, sizes = d.lead, (1, 2, 511, 512, 513)
+    assert lead == delays[-1]
+    if gain == 1.0:
+        src = odd_words(lead + 513, seed=23)
+    else:
+        rng = np.random.RandomState(29)
+        src = (1.5 * (rng.standard_normal(lead + 513) + 1j * rng.standard_normal(lead + 513))).astype(np.complex64)
+    scaled = src if gain == 1.0 else (np.float32(gain) * src).astype(np.complex64)
+    clips = 0
+    for shift_in in (0, 1):
+        x = placed(src, shift_in)
+        for shift_out in (0, 1):
+            total = sum(n + 4 for n in sizes) + 4
+            if out16:
+                dst = torch.full((total, 2), SENTINEL, dtype=torch.int16, device="cuda")
+            else:
+                dst = torch.zeros(total, dtype=torch.complex64, device="cuda")
+                torch.view_as_real(dst).view(torch.int32).fill_(SENTINEL_WORD)
+            at, cur = [], 2
+            for n in sizes:
+                cur += (cur + shift_out) % 2
+                assert int(d.execute(x[:lead + n], out=dst[cur:]).shape[0]) == n
+                at.append(cur)
+                cur += n + 2
+            got = host(dst) if out16 else words(dst)
+            mask = np.ones(len(got), bool)
+            for n, a in zip(sizes, at):
+                mask[a:a + n] = False
+                want = scaled[lead:lead + n]
+                if out16:
+                    assert np.array_equal(got[a:a + n], q16.quantise_iq(want)), (n, shift_in, shift_out)
+                    clips += q16.clipped_samples(want)
+                else:
+                    assert np.array_equal(got[a:a + n].view(np.uint32), bits(want)), (n, shift_in, shift_out)
+            assert np.all(got[mask] == (SENTINEL if out16 else SENTINEL_WORD)), "written outside the output"
+    assert d.clipped() == clips and (clips > 0) == out16
+    d.close()
+
+
 # ---------------------------------------------------------------------------------------------- 2. one branch is dpd
 @pytest.mark.parametrize("fout", ["cf32", "sc16"])
 @pytest.mark.parametrize("log2", [5, 10])
