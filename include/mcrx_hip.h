@@ -1201,6 +1201,103 @@ int      mcrx_hip_mpd_selftest(const mcrx_hip_mpd_config *cfg, float *inv_step, 
                                const float *z, size_t n, int32_t *Z, int32_t *U, int32_t *good);
 const char *mcrx_hip_mpd_last_error(void);
 
+/* ---- Feedback alignment for the predistorters: delay, gain and phase ----
+ * The stage between an observation receiver and mcrx_hip_dpd_measure_device / mcrx_hip_mpd_measure_device.  The receiver returns the
+ * amplifier's output late by some samples and a fraction of one, at its own gain and phase, as cf32 or sc16; this operator undoes the
+ * three.  Stateful, with the predistorters' three parts -- apply, measure, update -- and no host synchronisation between them.
+ * The handle holds, in device memory: tau_fp, an int64 in Q32 samples (how much the capture lags u); a complex fp64 scale s; the 32
+ * fp32 coefficients, the whole-sample offset and the fp32 scale that follow from the two.  After create and after reset tau_fp = 0,
+ * s = 1 and launches carry no filter code.
+ * Configuration: max_lag Lm in 8 .. 64; full_scale finite and positive, e and E = 2^e made of it exactly as for mcrx_hip_dpd_*;
+ * target_gain g0 finite and positive; min_rows >= 1; input_format 0 = cf32, 1 = sc16 (the shared codec: a word means (re, im) 2^-15).
+ * Derived: H = 8; R = Lm + H; halo = Lm + 17; the differentiator h_k = fp32((-1)^k / k (0.54 + 0.46 cos(pi k / 9))), k = 1 .. 8, made
+ * in double; h_-k = -h_k, h_0 = 0.
+ * APPLY, fp32, stateless in the samples: the input is n + 2 halo capture samples, in[halo + i] the sample of output i; the output is
+ * n cf32 samples.  With mcrx_hip_userclock_*'s table W (mcrx_hip_userclock_table):
+ *     d = -tau_fp;  nd = d >> 32 (floor);  mu = d & 0xffffffff;  r = mu >> 26;  f = ((mu >> 2) & 0xffffff) 2^-24
+ *     c_j = fmaf(f, W[r+1][j] - W[r][j], W[r][j])                             j = 0 .. 31, the difference one fp32 subtraction
+ *     acc = 0;  acc.re = fmaf(c_j, x.re, acc.re), acc.im = fmaf(c_j, x.im, acc.im) with x = in[halo + i - nd + 15 - j], j ascending
+ *     out.re = fmaf(s.re, acc.re, -(s.im * acc.im));  out.im = fmaf(s.re, acc.im, s.im * acc.re)         s rounded to fp32
+ *   |tau_fp| <= (Lm + 1) 2^32 always, so every tap lies inside the call's input.  A stream cut anywhere, each piece with its halos,
+ *   gives the bits of one call.  Until a handle has had an update or a set its launches carry no filter code: load in[halo + i],
+ *   convert, store; NaN payloads and -0.0 are kept.  Input and output must not overlap at all.
+ * MEASURE: two cf32 streams of n samples, u what went into the amplifier and zh the aligned capture that apply wrote.  Per component
+ *     Q15(v) = clamp(llrint(ldexpf(v, 15 - e)), -32768, 32767)               ties to even; a NaN gives 0
+ *   U[i] = Q15 of u[i], Z[i] = Q15 of zh[i].  The ROWS are i = R .. n - R - 1 (n <= 2 R: MCRX_OK, nothing measured); no row is
+ *   skipped.  u[i] and zh[i] of a row each add 1 to `clamped` when a component clamps or is not finite.  To int64 sums, exactly:
+ *     C[l] += conj(U[i]) Z[i + l]   l = -R .. R        A[l] += conj(U[i]) U[i + l]   l = 0 .. 2 H        Szz += |Z[i]|^2        rows += 1
+ *   with conj(X) Y = (X.re Y.re + X.im Y.im, X.re Y.im - X.im Y.re).  Integer atomics only: order, grid and cuts that keep the same
+ *   rows cannot change a bit.  A term is at most 2^31; the host counts the rows offered since the last update or reset and refuses a
+ *   call that would take the count above 2^31 -- such a call measures nothing.
+ * UPDATE: one lane on the device in fp64, + - * / and comparisons and conversions only, nothing contracted.  c(l) = (double) C[l],
+ *   a(l) = (double) A[l] per component (the conversion rounds); hd_k = (double) h_k.  In this order:
+ *     rows < min_rows: DEGENERATE.
+ *     best = -1;  for l = -Lm .. Lm ascending:  p = c(l).re * c(l).re + c(l).im * c(l).im;  p > best:  best = p, D = l.
+ *     best is not > 0: DEGENERATE.      bu = c(D)
+ *     bd = 0;  for k = 1 .. 8:  t = c(D + k) - c(D - k);  bd.re = bd.re + hd_k * t.re;  bd.im = bd.im + hd_k * t.im
+ *     Guu = a(0).re
+ *     g = 0;  for k = 1 .. 8:  g = g + hd_k * a(k).im;      Gud = (0, -2 g)        (a(-k) = conj(a(k)): the real parts cancel)
+ *     Gdd = 0;  for k = -8 .. 8 without 0, in it m = -8 .. 8 without 0:  Gdd = Gdd + (hs_k * hs_m) * a(|k - m|).re
+ *                                                                       hs_k = hd_k for k > 0, -hd_-k for k < 0
+ *     det = Guu * Gdd - Gud.im * Gud.im;      det is not > 0: DEGENERATE
+ *     alpha = ((Gdd * bu.re + Gud.im * bd.im) / det,  (Gdd * bu.im - Gud.im * bd.re) / det)          (Gdd bu - Gud bd) / det
+ *     beta  = ((Guu * bd.re - Gud.im * bu.im) / det,  (Guu * bd.im + Gud.im * bu.re) / det)          (Guu bd - conj(Gud) bu) / det
+ *     m2 = alpha.re * alpha.re + alpha.im * alpha.im
+ *     delta = -((beta.re * alpha.re + beta.im * alpha.im) / m2)                                      -Re(beta / alpha)
+ *     x = (s.re * g0, s.im * g0);  s' = ((x.re * alpha.re + x.im * alpha.im) / m2,  (x.im * alpha.re - x.re * alpha.im) / m2)
+ *     res' = Szz - (alpha.re * bu.re + alpha.im * bu.im)
+ *     inc = (int64) rint(((double)D + delta) * 2^32), ties to even;  tau' = tau_fp + inc
+ *     DEGENERATE if delta, s', res' or fp32(s') is not finite, if delta > 1 or delta < -1, or if |tau'| > (Lm + 1) 2^32.
+ *     Otherwise tau_fp = tau', s = s', res = res', and the coefficients, nd and the fp32 scale are made anew.
+ *   A degenerate update keeps tau_fp, s, res and the coefficients and adds 1 to `degenerate`.  Last, always: every sum and `rows` are
+ *   cleared and `updates` goes up.  This is one Gauss-Newton step on zh ~ alpha u - alpha delta u', u' = sum_k h_k u[i - k].
+ * A correlation aligner attributes the amplifier's own group delay to the path: behind an amplifier with memory the cascade keeps that
+ * residual delay (a few hundredths of a sample), and an error figure against g0 x that does not remove delay first is meaningless.
+ * Judge by the power outside the band, by the error after delay and gain removal and by the decoded frames.
+ * Calls on ONE handle must be ordered on the device (one stream, or events of the caller's). */
+typedef struct mcrx_hip_fbalign_s *mcrx_hip_fbalign_t;
+typedef struct {
+    uint32_t struct_size, max_lag;                      /* sizeof(mcrx_hip_fbalign_config); Lm: 8 .. 64 */
+    float    full_scale, target_gain;                   /* E = 2^e is the least power of two >= full_scale; g0 */
+    uint32_t min_rows, input_format;                    /* >= 1; 0 = cf32, 1 = sc16 */
+} mcrx_hip_fbalign_config;
+typedef struct {
+    int64_t  tau_fp;                                    /* Q32 samples */
+    double   s_re, s_im, res;                           /* the scale; Szz - Re(conj(alpha) bu) of the last update that was not degenerate */
+    uint64_t updates, degenerate, clamped;              /* updates run; those that left the state as it was; row samples that clamped */
+    int64_t  rows;                                      /* rows in the sums */
+    uint64_t offered;                                   /* the host's count of the guard: rows offered since the last update or reset */
+} mcrx_hip_fbalign_state;
+/* MCRX_EINVAL before a device is looked for, *out cleared: null pointers, a wrong struct_size, and every value outside the ranges above */
+int      mcrx_hip_fbalign_create(mcrx_hip_fbalign_t *out, const mcrx_hip_fbalign_config *cfg);
+int      mcrx_hip_fbalign_destroy(mcrx_hip_fbalign_t q);
+unsigned mcrx_hip_fbalign_halo(mcrx_hip_fbalign_t q);                                /* Lm + 17; 0 for a null handle */
+unsigned mcrx_hip_fbalign_input_format(mcrx_hip_fbalign_t q);                        /* 0 for a null handle */
+/* n + 2 halo samples at d_in (the handle's input format) -> n cf32 samples at d_out, asynchronously on `stream`.  n == 0: MCRX_OK,
+ * nothing done.  MCRX_EINVAL, nothing written: a null handle or buffer, a cf32 buffer not 8-byte aligned, an sc16 input not 4-byte
+ * aligned, n + 2 halo above 2^32, ranges that overlap in any way. */
+int      mcrx_hip_fbalign_execute_device(mcrx_hip_fbalign_t q, const void *d_in, size_t n, void *d_out, void *stream);
+/* n cf32 pairs (d_u[i], d_zh[i]); rows R .. n - R - 1 into the sums.  MCRX_EINVAL, nothing measured, the count as before: a null
+ * handle or buffer, a buffer not 8-byte aligned, more than 2^32 samples, a call that would take the rows offered since the last update
+ * or reset above 2^31. */
+int      mcrx_hip_fbalign_measure_device(mcrx_hip_fbalign_t q, const void *d_u, const void *d_zh, size_t n, void *stream);
+int      mcrx_hip_fbalign_update(mcrx_hip_fbalign_t q, void *stream);
+/* a known path: tau_fp and s written, coefficients made of them; sums and counters stay.  MCRX_EINVAL, nothing written:
+ * |tau_fp| > (Lm + 1) 2^32, s or fp32(s) not finite.  No synchronisation. */
+int      mcrx_hip_fbalign_set(mcrx_hip_fbalign_t q, int64_t tau_fp, double s_re, double s_im, void *stream);
+/* waits for the handle's work on `stream`.  coef: 35 floats -- c_0 .. c_31, fp32(s.re), fp32(s.im), (float) nd; sums: 2 (2 R + 19)
+ * int64, (re, im) of C[-R] .. C[R], A[0] .. A[16], (Szz, 0).  Any of the three pointers may be null. */
+int      mcrx_hip_fbalign_read(mcrx_hip_fbalign_t q, mcrx_hip_fbalign_state *state, float *coef, int64_t *sums, void *stream);
+/* state, coefficients, sums, counters and the host's count as after create -- without synchronising the device: the next kernel of
+ * the handle that touches them clears them.  Launches carry no filter code again. */
+int      mcrx_hip_fbalign_reset(mcrx_hip_fbalign_t q);
+/* host, no GPU: checks cfg as create does; *e and taps[8] = h_1 .. h_8 of it (each may be null); for the n floats v: q15[i] = Q15(v[i])
+ * and bad[i] = 1 where it clamps or v[i] is not finite (n == 0: v, q15 and bad are not looked at); and, where coef is not null, the 32
+ * coefficients and *nd of tau_fp (MCRX_EINVAL for |tau_fp| > (Lm + 1) 2^32; nd may be null). */
+int      mcrx_hip_fbalign_selftest(const mcrx_hip_fbalign_config *cfg, int *e, float *taps, const float *v, size_t n, int32_t *q15,
+                                   int32_t *bad, int64_t tau_fp, float *coef, int *nd);
+const char *mcrx_hip_fbalign_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

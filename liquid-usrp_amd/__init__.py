@@ -259,6 +259,19 @@ _EXPORTS = {
     "mcrx_hip_mpd_selftest": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcrx_hip_mpd_last_error": (C.c_char_p, []),
+    "mcrx_hip_fbalign_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcrx_hip_fbalign_destroy": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_fbalign_halo": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_fbalign_input_format": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_fbalign_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_fbalign_measure_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mcrx_hip_fbalign_update": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mcrx_hip_fbalign_set": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p]),
+    "mcrx_hip_fbalign_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_fbalign_reset": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_fbalign_selftest": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.POINTER(C.c_int)]),
+    "mcrx_hip_fbalign_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -1393,10 +1406,12 @@ class _Predistorter(_StreamOp):
         """Tables, sums and counters as after construction; execute copies again (no synchronisation)."""
         self._call("reset", self._h)
 
-    def learn(self, x, amplifier, rounds=3, first_sample=0, stream=None):
+    def learn(self, x, amplifier, rounds=3, first_sample=0, stream=None, aligner=None):
         """`rounds` times: execute(x) (mpd: with pad=True) -> amplifier.execute(u, first_sample, stream=) -> measure -> update;
         `amplifier` is any object with such an execute that returns as many cf32 samples as it gets, an rfchain with cf32 in and out
-        for one.  Returns the amplifier's output of the last round, which the table(s) of the round before it shaped."""
+        for one.  Returns the amplifier's output of the last round, which the table(s) of the round before it shaped.  With an
+        `aligner` (an fbalign) the amplifier's output is what an observation receiver returned, as many samples in the aligner's input
+        format: measure gets aligner.align(u, z, stream=)'s trimmed u and aligned capture instead of (u, z)."""
         if self.output_format != OUTPUT_FORMATS["cf32"]:
             raise ValueError("learn needs a cf32 predistorter: the feedback is the handle's cf32 output")
         import torch
@@ -1406,7 +1421,10 @@ class _Predistorter(_StreamOp):
         for _ in range(int(rounds)):
             u = self.execute(x, stream=stream, **self._pad)
             z = amplifier.execute(u, first_sample, stream=stream)
-            self.measure(u, z, stream=stream)
+            if aligner is None:
+                self.measure(u, z, stream=stream)
+            else:
+                self.measure(*aligner.align(u, z, stream=stream), stream=stream)
             self.update(stream=stream)
         return z
 
@@ -1633,6 +1651,161 @@ class mpd(_Predistorter):
                 ent += 1
         return dict(F=F, c=c, res=float(s.res), rows=int(s.rows), updates=int(s.updates), skipped=int(s.skipped), degenerate=int(s.degenerate),
                     sums=sums, A=A, b=b, Suu=int(sums[ne - 1, 0]))
+
+
+FBALIGN_MIN_LAG, FBALIGN_MAX_LAG, FBALIGN_H, FBALIGN_TAPS, FBALIGN_GUARD_LOG2, FBALIGN_MAX_WGS = 8, 64, 8, 32, 31, 256
+
+
+class FbalignConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_lag", C.c_uint32), ("full_scale", C.c_float), ("target_gain", C.c_float),
+                ("min_rows", C.c_uint32), ("input_format", C.c_uint32)]
+
+
+class FbalignState(C.Structure):
+    _fields_ = [("tau_fp", C.c_int64), ("s_re", C.c_double), ("s_im", C.c_double), ("res", C.c_double), ("updates", C.c_uint64),
+                ("degenerate", C.c_uint64), ("clamped", C.c_uint64), ("rows", C.c_int64), ("offered", C.c_uint64)]
+
+
+def fbalign_config(max_lag=32, full_scale=None, target_gain=None, min_rows=1024, input_format="cf32"):
+    """The mcrx_hip_fbalign_config of fbalign's arguments.  ValueError for a malformed or missing argument and for every value the
+    library refuses (mcrx_hip_fbalign_selftest judges them on the host: no device is looked for)."""
+    if full_scale is None or target_gain is None:
+        raise ValueError("full_scale and target_gain must be given")
+    c = FbalignConfig()
+    c.struct_size = C.sizeof(FbalignConfig)
+    c.input_format = _format_code(input_format, INPUT_FORMATS, "input_format")
+    c.max_lag, c.min_rows = _whole(max_lag, "max_lag"), _whole(min_rows, "min_rows")
+    c.full_scale, c.target_gain = float(full_scale), float(target_gain)
+    _raise_rc(lib().mcrx_hip_fbalign_selftest(C.addressof(c), None, None, None, 0, None, None, 0, None, None), "mcrx_hip_fbalign_selftest",
+              lib().mcrx_hip_fbalign_last_error)
+    return c
+
+
+def fbalign_constants(cfg):
+    """(e, taps) of an FbalignConfig as the library makes them: the exponent of the least power of two that is at least full_scale and
+    the differentiator's h_1 .. h_8 (float32 array).  Host only."""
+    e, taps = C.c_int(), np.zeros(FBALIGN_H, np.float32)
+    _raise_rc(lib().mcrx_hip_fbalign_selftest(C.addressof(cfg), C.byref(e), taps.ctypes.data, None, 0, None, None, 0, None, None),
+              "mcrx_hip_fbalign_selftest", lib().mcrx_hip_fbalign_last_error)
+    return int(e.value), taps
+
+
+def fbalign_q15(cfg, v):
+    """(q15, bad) as the measuring kernel makes them of the float32 components v: int32 arrays.  Host only."""
+    v = np.ascontiguousarray(v, np.float32).reshape(-1)
+    q, bad = np.zeros(len(v), np.int32), np.zeros(len(v), np.int32)
+    if len(v):
+        _raise_rc(lib().mcrx_hip_fbalign_selftest(C.addressof(cfg), None, None, v.ctypes.data, len(v), q.ctypes.data, bad.ctypes.data, 0, None, None),
+                  "mcrx_hip_fbalign_selftest", lib().mcrx_hip_fbalign_last_error)
+    return q, bad
+
+
+def fbalign_coefficients(cfg, tau_fp):
+    """(c, nd): the 32 fp32 coefficients and the whole-sample offset apply uses at the delay tau_fp (Q32 samples).  Host only."""
+    c, nd = np.zeros(FBALIGN_TAPS, np.float32), C.c_int()
+    _raise_rc(lib().mcrx_hip_fbalign_selftest(C.addressof(cfg), None, None, None, 0, None, None, int(tau_fp), c.ctypes.data, C.byref(nd)),
+              "mcrx_hip_fbalign_selftest", lib().mcrx_hip_fbalign_last_error)
+    return c, int(nd.value)
+
+
+class fbalign(_StreamOp):
+    """Feedback alignment for the predistorters (mcrx_hip_fbalign_*): between an observation receiver and dpd.measure / mpd.measure.
+
+        fbalign(max_lag=32, full_scale=, target_gain=, min_rows=1024, input_format="cf32")
+
+    The receiver returns the amplifier's output late by up to max_lag samples and a fraction, at its own gain and phase, as cf32 or
+    sc16.  execute(z) delays the capture by -tau through a 32-tap interpolator and scales it by s; measure(u, zh) correlates the
+    amplifier's input with the aligned capture into exact integer sums; update() moves tau and s by one Gauss-Newton step on the
+    device; set writes a known path.  Until the first update or set, execute copies.  Stateless in the samples and non-causal:
+    execute takes n + 2 halo samples and returns the n in the middle.  The aligner counts the amplifier's own group delay as the
+    path's.  Calls on one handle must be ordered on the device."""
+
+    _op, _what = "fbalign", ("this aligner", "aligner")
+
+    def __init__(self, max_lag=32, full_scale=None, target_gain=None, min_rows=1024, input_format="cf32"):
+        c = fbalign_config(max_lag, full_scale, target_gain, min_rows, input_format)
+        self._create(c)
+        self.config, self.input_format, self.output_format, self.max_lag = c, int(c.input_format), OUTPUT_FORMATS["cf32"], int(c.max_lag)
+        self.R = self.max_lag + FBALIGN_H
+        self.halo = int(lib().mcrx_hip_fbalign_halo(self._h))
+
+    def execute(self, z, out=None, pad=False, stream=None):
+        """z: a contiguous CUDA tensor of n + 2 halo capture samples (complex64, or on an sc16-in handle int16 of shape (n, 2)) -- or,
+        with pad=True, n samples, which get `halo` zeros on either side.  out (optional): where the n complex64 samples go; it must not
+        overlap z.  Returns the n samples written.  Asynchronous on `stream` (default: torch's current stream of z's device)."""
+        import torch
+        in16 = self.input_format == INPUT_FORMATS["sc16"]
+        m = self._in(z, in16)
+        if pad:
+            padded = torch.zeros((m + 2 * self.halo, 2), dtype=torch.int16, device=z.device) if in16 else \
+                torch.zeros(m + 2 * self.halo, dtype=torch.complex64, device=z.device)
+            padded[self.halo:self.halo + m].copy_(z.view(-1, 2) if in16 else z.view(-1))
+            z, m = padded, m + 2 * self.halo
+        n = m - 2 * self.halo
+        if n < 0:
+            raise ValueError("z must hold the halo on either side: at least %d samples" % (2 * self.halo))
+        out, view = self._out(n, out, False, z.device)
+        if n:
+            self._call("execute_device", self._h, _dptr(z), n, _dptr(out), self._stream(stream, z))
+        return view
+
+    def measure(self, u, zh, stream=None):
+        """u, zh: equally many complex64 samples -- the amplifier's input and the aligned capture that execute wrote.  Returns the
+        number of rows offered (the first and last R = max_lag + 8 samples are no rows).  ValueError, nothing measured, where that
+        would take the rows offered since the last update or reset above 2^31."""
+        n = self._in(u, False)
+        if self._in(zh, False) != n:
+            raise ValueError("u and zh must hold equally many samples")
+        if n:
+            self._call("measure_device", self._h, _dptr(u), _dptr(zh), n, self._stream(stream, u))
+        return max(n - 2 * self.R, 0)
+
+    def update(self, stream=None):
+        """Move tau and s by what has been measured (on the device, no synchronisation) and clear the sums."""
+        self._call("update", self._h, self._current(stream))
+
+    def set(self, tau_fp, s=1.0, stream=None):
+        """Write a known path: tau_fp (an integer, Q32 samples: the capture lags u by tau_fp / 2^32) and the complex scale s."""
+        s = complex(s)
+        if isinstance(tau_fp, bool) or int(tau_fp) != tau_fp or abs(int(tau_fp)) >= 1 << 63:
+            raise ValueError("tau_fp is an integer in Q32 samples")
+        self._call("set", self._h, int(tau_fp), s.real, s.imag, self._current(stream))
+
+    def clipped(self, reset=False):
+        """0: the output is cf32 (samples that clamp in measure are read()'s `clamped`)."""
+        return 0
+
+    def reset(self):
+        """tau = 0, s = 1, sums and counters cleared; execute copies again (no synchronisation)."""
+        self._call("reset", self._h)
+
+    def read(self, stream=None):
+        """The handle's state as a dict (waits for the handle's work on `stream`): tau_fp (int), tau (float samples), s (complex), res,
+        rows, updates, degenerate, clamped, offered (the guard's count of rows since the last update or reset), coef (float32 [32]), scale (the fp32 s as complex), nd, and the sums as int64 arrays of
+        (re, im): C [2 R + 1, 2] (lags -R .. R), A [17, 2], and Szz (int)."""
+        ns = 2 * self.R + 19
+        s, coef, sums = FbalignState(), np.zeros(FBALIGN_TAPS + 3, np.float32), np.zeros((ns, 2), np.int64)
+        self._call("read", self._h, C.addressof(s), coef.ctypes.data, sums.ctypes.data, self._current(stream))
+        return dict(tau_fp=int(s.tau_fp), tau=float(s.tau_fp) * 2.0 ** -32, s=complex(s.s_re, s.s_im), res=float(s.res), rows=int(s.rows),
+                    updates=int(s.updates), degenerate=int(s.degenerate), clamped=int(s.clamped), offered=int(s.offered), coef=coef[:FBALIGN_TAPS].copy(),
+                    scale=complex(coef[FBALIGN_TAPS], coef[FBALIGN_TAPS + 1]), nd=int(coef[FBALIGN_TAPS + 2]), C=sums[:2 * self.R + 1].copy(),
+                    A=sums[2 * self.R + 1:ns - 1].copy(), Szz=int(sums[ns - 1, 0]), sums=sums)
+
+    def align(self, u, z, rounds=3, stream=None):
+        """u: n complex64 samples into the amplifier; z: the n capture samples the receiver returned for them, in the input format.
+        `rounds` times execute(z) -> measure -> update, then execute once more.  Returns (u[halo : n - halo], the aligned capture):
+        n - 2 halo samples each, ready for dpd.measure or mpd.measure."""
+        in16 = self.input_format == INPUT_FORMATS["sc16"]
+        n = self._in(u, False)
+        if self._in(z, in16) != n:
+            raise ValueError("u and z must hold equally many samples")
+        if n < 2 * self.halo:
+            raise ValueError("u and z must hold the halo on either side: at least %d samples" % (2 * self.halo))
+        ut = u.view(-1)[self.halo:n - self.halo]
+        for _ in range(int(rounds)):
+            self.measure(ut, self.execute(z, stream=stream), stream=stream)
+            self.update(stream=stream)
+        return ut, self.execute(z, stream=stream)
 
 
 USERCHAN_MAX_RAYS, USERCHAN_MAX_DELAY, USERCHAN_MAX_CHANNELS = 4, 255, 1024      # MCRX_USERCHAN_MAX_RAYS, _MAX_DELAY, _MAX_CHANNELS

@@ -53,6 +53,7 @@
 #include "devmath.h"
 #include "fadegen.hpp"
 #include "design.hpp"
+#include "interp_table.hpp"
 #include "ophost.hpp"
 #include "span_plan.hpp"
 
@@ -212,8 +213,7 @@ struct UserclockArgs {
     uint32_t skip;                  // output blocks below this one are written as zeros and read nothing
 };
 
-// h_j(mu) from the two rows of W around the fraction: the definition's one fused multiply-add, the same on the host and on the device
-__host__ __device__ __forceinline__ float userclock_coef(float w0, float w1, float f) { return fmaf(f, w1 - w0, w0); }
+// h_j(mu) from the two rows of W around the fraction: userclock_coef (interp_table.hpp)
 // tau_fp(b): the product wraps where the host has not checked it (blocks below `skip` never get here)
 __host__ __device__ __forceinline__ int64_t userclock_tau(int64_t delay_fp, int64_t sco, int64_t origin, int64_t b)
 {
@@ -599,27 +599,6 @@ extern "C" int mcrx_hip_userfade_gains(mcrx_hip_userchan_t q, long long first_ro
 }
 
 // ---- each user's own sample clock and fractional timing (mcrx_hip_userclock_*) ----
-static void userclock_make_table(float *W)
-{
-    const double ib = besseli0(6.0);
-    for (int p = 0; p <= MCRX_USERCLOCK_PHASES; p++)
-        for (int j = 0; j < MCRX_USERCLOCK_TAPS; j++) {
-            const double t = (double)(j - 15) - (double)p / MCRX_USERCLOCK_PHASES;
-            const double x = M_PI * t, sn = std::fabs(t) < 1e-12 ? 1.0 : std::sin(x) / x;
-            const double r = t / 16.0, w = 1.0 - r * r;
-            float v = (float)(sn * besseli0(6.0 * std::sqrt(w < 0.0 ? 0.0 : w)) / ib);
-            if (p == 0) v = j == 15 ? 1.f : 0.f;                        // the two ends are whole-sample delays: exact unit vectors
-            if (p == MCRX_USERCLOCK_PHASES) v = j == 16 ? 1.f : 0.f;
-            W[p * MCRX_USERCLOCK_TAPS + j] = v;
-        }
-}
-
-static const float *userclock_table()
-{
-    static const std::vector<float> W = [] { std::vector<float> w((MCRX_USERCLOCK_PHASES + 1) * MCRX_USERCLOCK_TAPS); userclock_make_table(w.data()); return w; }();
-    return W.data();
-}
-
 static const char *userclock_check_config(const mcrx_hip_userclock_config *f)
 {
     if (f->struct_size != sizeof(mcrx_hip_userclock_config)) return "mcrx_hip_userclock_config: wrong struct_size";
