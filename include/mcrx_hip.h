@@ -1201,6 +1201,68 @@ int      mcrx_hip_mpd_selftest(const mcrx_hip_mpd_config *cfg, float *inv_step, 
                                const float *z, size_t n, int32_t *Z, int32_t *U, int32_t *good);
 const char *mcrx_hip_mpd_last_error(void);
 
+/* ---- Amplifier with memory on the wideband stream: parallel Hammerstein branches ----
+ * The amplifier that mcrx_hip_mpd_* exists to straighten: one that is NOT memoryless.  B = 1 .. 4 branches, branch b the RF front
+ * end's memoryless amplifier A_b with its own saturation amplitude, smoothness, small-signal gain and AM/PM, behind it a sparse complex
+ * FIR of T_b = 1 .. 8 taps (d, h): delays d in 0 .. 16, strictly increasing within a branch, weights h complex fp32 (zero allowed).
+ *     y[i] = gain * sum_{b < B} sum_{k < T_b} h_{b,k} * A_b(u[i - d_{b,k}])                       lead = the largest delay, 0 .. 16
+ * STATELESS and time-invariant, cf32 or sc16 in (a word means (re, im) * 2^-15), cf32 or sc16 out: the input is n + lead samples, the
+ * history in front; in[lead + i] is the sample of output i.  A stream cut anywhere into calls that each carry their lead samples of
+ * history gives the bits of one call; the operator does not depend on position, so no call takes one.  All fp32:
+ *   a_b[s] = A_b(u[s]), once a sample and branch, the amplifier of mcrx_hip_rfchain_* line for line with A = sat, p = smooth:
+ *     t = fmaf(z.re, z.re, z.im * z.im) * r_b           r_b = fp32(1 / A_b^2), made on the host (the division in double)
+ *     q = 1 + t (p = 1);  sqrtf(fmaf(t, t, 1)) (p = 2);  sqrtf(sqrtf(fmaf(t2, t2, 1))), t2 = t * t (p = 4)
+ *     G = amp_gain / sqrtf(q);  w = (G z.re, G z.im)
+ *     phi = ampm * (t / (1 + t)) turns; p32 = (uint32_t)(int32_t)rintf(phi * 2^32); (sn, cs) = sincos of the 32-bit phase p32
+ *     a.re = fmaf(w.re, cs, -(w.im * sn)),  a.im = fmaf(w.re, sn, w.im * cs)                      ampm == 0: skipped, a = w
+ *   the sum, in the fixed order b ascending, then k ascending, a = a_b[lead + i - d_{b,k}], h = h_{b,k}:
+ *     the first term (b = 0, k = 0), a plain complex product, not an accumulation onto zero:
+ *       y.re = fmaf(h.re, a.re, -(h.im * a.im));   y.im = fmaf(h.re, a.im, h.im * a.re)
+ *     every later term, two nested fmaf a component onto the accumulator:
+ *       y.re = fmaf(h.re, a.re, fmaf(-h.im, a.im, y.re));   y.im = fmaf(h.re, a.im, fmaf(h.im, a.re, y.im))
+ *   v = gain * y (one multiply a component; skipped when gain == 1);  out = v (cf32) or Q(v) (sc16: the shared quantiser as it stands,
+ *   with the shared clip count).  The integers of an sc16-out handle are Q of a cf32-out handle's floats exactly; an sc16-in handle
+ *   gives the bits of a cf32-in handle on (re, im) * 2^-15.  With B = 1 and the one tap (0, 1 + 0i) the output equals that of the
+ *   mcrx_hip_rfchain_* handle with the amplifier alone as numbers for every finite input (the sign of a zero may differ).
+ * Input and output must not overlap at all: a lane reads its neighbours' samples. */
+#define MCRX_PAMEM_MAX_BRANCHES 4
+#define MCRX_PAMEM_MAX_TAPS     8
+#define MCRX_PAMEM_MAX_DELAY    16
+typedef struct mcrx_hip_pamem_s *mcrx_hip_pamem_t;
+typedef struct {
+    float    sat, amp_gain, ampm;                       /* A > 0; small-signal gain; AM/PM at full compression, turns */
+    uint32_t smooth, taps;                              /* 1, 2 or 4; T: 1 .. 8 */
+    uint32_t delay[MCRX_PAMEM_MAX_TAPS];                /* 0 .. 16, strictly increasing; entries >= taps are not looked at */
+    float    h_re[MCRX_PAMEM_MAX_TAPS], h_im[MCRX_PAMEM_MAX_TAPS];
+} mcrx_hip_pamem_branch;
+typedef struct {
+    uint32_t struct_size, branches;                     /* sizeof(mcrx_hip_pamem_config); B: 1 .. 4 */
+    uint32_t input_format, output_format;               /* 0 = cf32, 1 = sc16 */
+    float    gain;
+    mcrx_hip_pamem_branch branch[MCRX_PAMEM_MAX_BRANCHES];
+} mcrx_hip_pamem_config;
+/* MCRX_EINVAL before a device is looked for, *out cleared: null pointers, a wrong struct_size, branches outside 1 .. 4, a format that
+ * is not 0 or 1, a gain that is not finite; in a branch taps outside 1 .. 8, a delay above 16 or not strictly increasing, a weight that
+ * is not finite, and sat, smooth, amp_gain, ampm judged exactly as mcrx_hip_rfchain_create judges amp_sat, amp_smooth, amp_gain and
+ * amp_ampm.  Fields of branches at index >= branches are not looked at. */
+int      mcrx_hip_pamem_create(mcrx_hip_pamem_t *out, const mcrx_hip_pamem_config *cfg);
+int      mcrx_hip_pamem_destroy(mcrx_hip_pamem_t q);
+unsigned mcrx_hip_pamem_lead(mcrx_hip_pamem_t q);                                      /* 0 for a null handle */
+unsigned mcrx_hip_pamem_input_format(mcrx_hip_pamem_t q);                              /* 0 for a null handle */
+unsigned mcrx_hip_pamem_output_format(mcrx_hip_pamem_t q);                             /* 0 for a null handle */
+/* n + lead samples at d_in (the handle's input format) -> n samples at d_out (its output format), asynchronously on `stream` (NULL =
+ * the default stream).  n == 0: MCRX_OK, nothing done.  MCRX_EINVAL, nothing written: a null handle or buffer, a cf32 buffer not 8-byte
+ * aligned, an sc16 buffer not 4-byte aligned, n + lead above 2^32, ranges that overlap in any way. */
+int      mcrx_hip_pamem_execute_device(mcrx_hip_pamem_t q, const void *d_in, size_t n, void *d_out, void *stream);
+/* mctx_hip_clipped's semantics; counter and event exist only on a handle with sc16 output; always 0 on a cf32 one */
+int      mcrx_hip_pamem_clipped(mcrx_hip_pamem_t q, uint64_t *samples, int reset);
+/* host, no GPU: checks cfg as create does; *lead; inv_a2[b] = r_b, b < branches; and the taps flattened in the order the sum runs
+ * (branch ascending, then tap ascending): *num_taps of them, tap i of branch tap_branch[i] at delay tap_delay[i] with the weight
+ * (tap_h[2 i], tap_h[2 i + 1]).  Room for 4 and 32 entries; each of the six pointers may be null. */
+int      mcrx_hip_pamem_selftest(const mcrx_hip_pamem_config *cfg, uint32_t *lead, float *inv_a2, uint32_t *num_taps, uint32_t *tap_branch,
+                                 uint32_t *tap_delay, float *tap_h);
+const char *mcrx_hip_pamem_last_error(void);
+
 /* ---- Feedback alignment for the predistorters: delay, gain and phase ----
  * The stage between an observation receiver and mcrx_hip_dpd_measure_device / mcrx_hip_mpd_measure_device.  The receiver returns the
  * amplifier's output late by some samples and a fraction of one, at its own gain and phase, as cf32 or sc16; this operator undoes the

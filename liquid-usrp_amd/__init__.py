@@ -259,6 +259,15 @@ _EXPORTS = {
     "mcrx_hip_mpd_selftest": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcrx_hip_mpd_last_error": (C.c_char_p, []),
+    "mcrx_hip_pamem_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "mcrx_hip_pamem_destroy": (C.c_int, [C.c_void_p]),
+    "mcrx_hip_pamem_lead": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_pamem_input_format": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_pamem_output_format": (C.c_uint, [C.c_void_p]),
+    "mcrx_hip_pamem_execute_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_pamem_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
+    "mcrx_hip_pamem_selftest": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcrx_hip_pamem_last_error": (C.c_char_p, []),
     "mcrx_hip_fbalign_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
     "mcrx_hip_fbalign_destroy": (C.c_int, [C.c_void_p]),
     "mcrx_hip_fbalign_halo": (C.c_uint, [C.c_void_p]),
@@ -881,7 +890,7 @@ def _whole(v, name):
 
 
 class _StreamOp(object):
-    """What the classes of the stream operators share (chanemu, rfchain, cfr, rfcal, dpd, mpd): the handle of mcrx_hip_<_op>_create, errors through
+    """What the classes of the stream operators share (chanemu, rfchain, cfr, rfcal, dpd, mpd, pamem): the handle of mcrx_hip_<_op>_create, errors through
     mcrx_hip_<_op>_last_error, the clip count, close, and what execute checks of x and out.  _what: who takes the samples, and the noun
     of "this ..." in the messages."""
     _op, _what, _h = None, None, None
@@ -1651,6 +1660,112 @@ class mpd(_Predistorter):
                 ent += 1
         return dict(F=F, c=c, res=float(s.res), rows=int(s.rows), updates=int(s.updates), skipped=int(s.skipped), degenerate=int(s.degenerate),
                     sums=sums, A=A, b=b, Suu=int(sums[ne - 1, 0]))
+
+
+PAMEM_MAX_BRANCHES, PAMEM_MAX_TAPS, PAMEM_MAX_DELAY = 4, 8, 16     # MCRX_PAMEM_MAX_*
+
+
+class PamemBranch(C.Structure):
+    _fields_ = [("sat", C.c_float), ("amp_gain", C.c_float), ("ampm", C.c_float), ("smooth", C.c_uint32), ("taps", C.c_uint32),
+                ("delay", C.c_uint32 * PAMEM_MAX_TAPS), ("h_re", C.c_float * PAMEM_MAX_TAPS), ("h_im", C.c_float * PAMEM_MAX_TAPS)]
+
+
+class PamemConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("branches", C.c_uint32), ("input_format", C.c_uint32), ("output_format", C.c_uint32),
+                ("gain", C.c_float), ("branch", PamemBranch * PAMEM_MAX_BRANCHES)]
+
+
+def pamem_config(branches=None, gain=1.0, input_format="cf32", output_format="cf32"):
+    """The mcrx_hip_pamem_config of pamem's arguments.  ValueError for a malformed or missing argument and for every value the library
+    refuses (mcrx_hip_pamem_selftest judges them on the host: no device is looked for)."""
+    required, optional = ("sat",), dict(smooth=2, gain=1.0, ampm_deg=0.0, taps=((0, 1.0),))
+    if not isinstance(branches, (list, tuple)) or not 1 <= len(branches) <= PAMEM_MAX_BRANCHES:
+        raise ValueError("branches: a list of 1 .. %d dicts" % PAMEM_MAX_BRANCHES)
+    c = PamemConfig()
+    c.struct_size, c.branches, c.gain = C.sizeof(PamemConfig), len(branches), float(gain)
+    c.input_format = _format_code(input_format, INPUT_FORMATS, "input_format")
+    c.output_format = _format_code(output_format, OUTPUT_FORMATS, "output_format")
+    for b, d in enumerate(branches):
+        if not isinstance(d, dict) or any(k not in required and k not in optional for k in d) or any(k not in d for k in required):
+            raise ValueError("a branch is a dict with %s and optionally %s" % (required, tuple(optional)))
+        d, br = dict(optional, **d), c.branch[b]
+        br.sat, br.amp_gain, br.ampm, br.smooth = float(d["sat"]), float(d["gain"]), float(d["ampm_deg"]) / 360.0, _whole(d["smooth"], "smooth")
+        taps = list(d["taps"]) if isinstance(d["taps"], (list, tuple)) else None
+        if taps is None or not 1 <= len(taps) <= PAMEM_MAX_TAPS or any(not isinstance(t, (list, tuple)) or len(t) != 2 for t in taps):
+            raise ValueError("taps: 1 .. %d pairs (delay, weight)" % PAMEM_MAX_TAPS)
+        br.taps = len(taps)
+        for k, (delay, weight) in enumerate(taps):
+            br.delay[k], weight = _whole(delay, "a delay"), complex(weight)
+            br.h_re[k], br.h_im[k] = weight.real, weight.imag
+    _raise_rc(lib().mcrx_hip_pamem_selftest(C.addressof(c), None, None, None, None, None, None), "mcrx_hip_pamem_selftest",
+              lib().mcrx_hip_pamem_last_error)
+    return c
+
+
+def pamem_constants(cfg):
+    """(lead, [r_b], [(branch, delay, weight), ...]) of a PamemConfig as the library makes them: r_b = fp32(1 / sat_b^2) and the taps in
+    the order the sum runs (mcrx_hip_pamem_selftest; host only)."""
+    most = PAMEM_MAX_BRANCHES * PAMEM_MAX_TAPS
+    lead, count, r = C.c_uint32(), C.c_uint32(), (C.c_float * PAMEM_MAX_BRANCHES)()
+    tb, td, th = (C.c_uint32 * most)(), (C.c_uint32 * most)(), (C.c_float * (2 * most))()
+    _raise_rc(lib().mcrx_hip_pamem_selftest(C.addressof(cfg), C.byref(lead), r, C.byref(count), tb, td, th), "mcrx_hip_pamem_selftest",
+              lib().mcrx_hip_pamem_last_error)
+    return (int(lead.value), [float(v) for v in r[:int(cfg.branches)]],
+            [(int(tb[i]), int(td[i]), complex(th[2 * i], th[2 * i + 1])) for i in range(int(count.value))])
+
+
+def pamem_small_signal(branches):
+    """The complex taps H[0 .. lead] of the linear regime of pamem(branches), float64 on the host: H[d] = the sum over the taps (b, k)
+    at delay d of gain_b * h_{b,k}, with the fp32 values the handle holds.  Far below saturation the operator is this FIR (times its
+    gain); its group delay is what fbalign counts as the path's."""
+    c = pamem_config(branches)
+    lead, _, taps = pamem_constants(c)
+    H = np.zeros(lead + 1, np.complex128)
+    for b, d, h in taps:
+        H[d] += float(c.branch[b].amp_gain) * h
+    return H
+
+
+class pamem(_StreamOp):
+    """Amplifier with memory on the wideband stream (mcrx_hip_pamem_*): a parallel Hammerstein model, the amplifier mpd straightens.
+
+        pamem(branches=[dict(sat, smooth=2, gain=1.0, ampm_deg=0.0, taps=[(delay, weight), ...]), ...], gain=1.0,
+              input_format="cf32", output_format="cf32")
+
+    1 .. 4 branches, each rfchain's amplifier (Rapp AM/AM of smoothness 1, 2 or 4 that saturates at `sat`, AM/PM that tends to ampm_deg)
+    behind it 1 .. 8 taps: delays 0 .. 16, strictly increasing, complex weights.  y[i] = gain * sum_b sum_k h_bk A_b(u[i - d_bk]).
+    Stateless and time-invariant; lead = the largest delay.  sc16 tensors are contiguous int16 of shape (n, 2).  A pamem is directly
+    the `amplifier` of dpd.learn / mpd.learn."""
+
+    _op, _what = "pamem", ("this amplifier", "amplifier")
+
+    def __init__(self, branches=None, gain=1.0, input_format="cf32", output_format="cf32"):
+        c = pamem_config(branches, gain, input_format, output_format)
+        self._create(c)
+        self.config, self.input_format, self.output_format = c, int(c.input_format), int(c.output_format)
+        self.lead = int(lib().mcrx_hip_pamem_lead(self._h))
+
+    def execute(self, x, first_sample=0, out=None, pad=True, stream=None):
+        """x: n samples, which get `lead` zeros in front (pad=True, the default: as many samples out as in) -- or, with pad=False,
+        lead + n samples, the history in front.  A contiguous CUDA tensor: complex64, or on an sc16-in handle int16 of shape (n, 2).
+        first_sample is accepted and ignored: the operator does not depend on position.  out (optional): where the n samples go, in
+        the output format; it must not overlap x.  Returns the n samples written.  Asynchronous on `stream` (default: torch's current
+        stream of x's device)."""
+        import torch
+        in16 = self.input_format == INPUT_FORMATS["sc16"]
+        m = self._in(x, in16)
+        if pad and self.lead:
+            padded = torch.zeros((m + self.lead, 2), dtype=torch.int16, device=x.device) if in16 else \
+                torch.zeros(m + self.lead, dtype=torch.complex64, device=x.device)
+            padded[self.lead:].copy_(x.view(-1, 2) if in16 else x.view(-1))
+            x = padded
+        n = (m if pad else m - self.lead)
+        if n < 0:
+            raise ValueError("x must hold the history in front: at least %d samples" % self.lead)
+        out, view = self._out(n, out, self.output_format == OUTPUT_FORMATS["sc16"], x.device)
+        if n:
+            self._call("execute_device", self._h, _dptr(x), n, _dptr(out), self._stream(stream, x))
+        return view
 
 
 FBALIGN_MIN_LAG, FBALIGN_MAX_LAG, FBALIGN_H, FBALIGN_TAPS, FBALIGN_GUARD_LOG2, FBALIGN_MAX_WGS = 8, 64, 8, 32, 31, 256

@@ -30,6 +30,7 @@
 #include "fadegen.hpp"
 #include "iqpair.hpp"
 #include "ophost.hpp"
+#include "rapp.hpp"
 #include "rfchain_plan.hpp"
 #include "span_plan.hpp"
 #include "stream_call.hpp"
@@ -72,38 +73,15 @@ __global__ __launch_bounds__(256) void rfchain_phase_kernel(RfchainPhase t, floa
     table[row] = acc;
 }
 
-// (uint32_t)(int32_t)rintf(turns * 2^32): the hardware's conversion, as sc16_round's (it saturates and turns NaN into 0, where the C cast
-// is undefined -- an infinite input sample reaches this through the amplifier's phi)
-__device__ __forceinline__ uint32_t rfchain_phase_word(float turns)
-{
-    const float r = __builtin_rintf(turns * 4294967296.0f);
-    int i;
-    asm("v_cvt_i32_f32_e32 %0, %1" : "=v"(i) : "v"(r));
-    return (uint32_t)i;
-}
-// z e(p), chanemu_sample's shape
-__device__ __forceinline__ float2 rfchain_rotate(float2 z, uint32_t p)
-{
-    float sn, cs;
-    sincos_u32(p, sn, cs);
-    return make_float2(fmaf(z.x, cs, -(z.y * sn)), fmaf(z.x, sn, z.y * cs));
-}
 __device__ __forceinline__ float2 rfchain_mixer(const RfchainArgs &a, float2 z)
 {
     return make_float2(fmaf(a.ar, z.x, fmaf(-a.ai, z.y, fmaf(a.br, z.x, fmaf(a.bi, z.y, a.dr)))),
                        fmaf(a.ar, z.y, fmaf(a.ai, z.x, fmaf(a.bi, z.x, fmaf(-a.br, z.y, a.di)))));
 }
+// the amplifier is rapp.hpp's, which pamem.hip's branches share
 __device__ __forceinline__ float2 rfchain_amplifier(const RfchainArgs &a, float2 z)
 {
-    const float t = fmaf(z.x, z.x, z.y * z.y) * a.inv_a2;
-    float q;
-    if (a.smooth == 1u) q = 1.0f + t;
-    else if (a.smooth == 2u) q = sqrtf(fmaf(t, t, 1.0f));
-    else { const float t2 = t * t; q = sqrtf(sqrtf(fmaf(t2, t2, 1.0f))); }
-    const float G = a.amp_gain / sqrtf(q);
-    const float2 w = make_float2(G * z.x, G * z.y);
-    if (a.ampm == 0.f) return w;
-    return rfchain_rotate(w, rfchain_phase_word(a.ampm * (t / (1.0f + t))));
+    return rapp_amplifier(a.inv_a2, a.smooth, a.amp_gain, a.ampm, z);
 }
 
 template <int STAGES>

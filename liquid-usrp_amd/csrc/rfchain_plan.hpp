@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include "../../include/mcrx_hip.h"
 #include "fadegen.hpp"
+#include "rapp_plan.hpp"
 
 namespace mcrx {
 
@@ -22,8 +23,8 @@ static inline const char *rfchain_osc_check(const mcrx_hip_rfchain_config *c)
     return nullptr;
 }
 
-// fp32(1 / A^2), the division in double
-static inline float rfchain_inv_sat2(float amp_sat) { return (float)(1.0 / ((double)amp_sat * (double)amp_sat)); }
+// fp32(1 / A^2), the division in double: rapp_plan.hpp's, which the amplifier with memory shares
+static inline float rfchain_inv_sat2(float amp_sat) { return rapp_inv_sat2(amp_sat); }
 
 // the whole configuration, as create sees it: nullptr or what is wrong
 static inline const char *rfchain_check(const mcrx_hip_rfchain_config *c)
@@ -41,12 +42,7 @@ static inline const char *rfchain_check(const mcrx_hip_rfchain_config *c)
     if (c->stages & MCRX_RFCHAIN_OSCILLATOR)
         if (const char *bad = rfchain_osc_check(c)) return bad;
     if (c->stages & MCRX_RFCHAIN_AMPLIFIER) {
-        if (c->amp_smooth != 1u && c->amp_smooth != 2u && c->amp_smooth != 4u) return "amp_smooth must be 1, 2 or 4";
-        if (!std::isfinite(c->amp_sat) || !(c->amp_sat > 0.f)) return "amp_sat must be finite and positive";
-        const float r = rfchain_inv_sat2(c->amp_sat);
-        if (!std::isfinite(r) || !(r > 0.f)) return "1 / amp_sat^2 is not a finite positive fp32";
-        if (!std::isfinite(c->amp_gain)) return "amp_gain must be finite";
-        if (!std::isfinite(c->amp_ampm) || std::fabs(c->amp_ampm) > 0.25f) return "amp_ampm must be finite, at most 1/4 turn";
+        if (const char *bad = rapp_check(c->amp_sat, c->amp_smooth, c->amp_gain, c->amp_ampm)) return bad;
     }
     return nullptr;
 }
